@@ -10,8 +10,13 @@ in HBM): the interval the reference prints as "Constructed the suffix array"
 quoted on, C3: 3,000,000,000 random bases + the trailing newline the CLI remaps to 'C'
 (src/main.cpp:61-70), 32-bit indices, 8000 subproblems.  Prints ONE JSON line (rank 0).
 
-The result of the LAST timed step is always checked by the exact device verifier
-(permutation + adjacent order + exact LCP on the raw bytes): `verify_errors` in the line.
+A plain run sets up, warms up, times the --steps builds and prints the line; the kernel families,
+phases and roofline in it come from the timed builds' own statistics.  --full adds the checks and
+measurements that take work of their own: the exact device verifier on the last timed step's result
+(permutation + adjacent order + exact LCP on the raw bytes: `verify_errors`), the CPU baseline
+(`cpu_baseline`; on the whole text, compared entry by entry, when the host allows) and the
+host-buffer entry point (`pcie_inclusive`).  --dump-outputs DIR writes the last timed step's SA
+and LCP (a seeded sample of them: dump_outputs) for comparing two builds output for output.
 """
 import argparse
 import json
@@ -25,6 +30,8 @@ for _p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tools")):
         sys.path.insert(0, _p)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_SAMPLE = 1 << 21          # --dump-outputs: entries kept per array of a longer text
+DUMP_SEED = 1234               # ... and the seed of their positions
 WORKLOADS = {
     # name: (bases, kind, description)
     # "uniform" = the reference's generator itself: utils/gen_rand_seq.py <seed> <N> (CPython's MT19937 stream, reproduced bit for bit by
@@ -290,23 +297,56 @@ def parse_args(argv=None):
     ap.add_argument("--bases", type=int, default=0, help="override the number of bases (debugging)")
     ap.add_argument("--p", type=int, default=8000)
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the device verifier, the CPU baseline and the host-buffer path (each can be left out with its --no-* "
+                         "option); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's SA and LCP to DIR/SA.npy and DIR/LCP.npy (float64; a seeded sample of "
+                         f"{DUMP_SAMPLE} entries each when the text is longer)")
     ap.add_argument("--cpu-sample", type=int, default=256 * 1024 * 1024 + 1)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-full", action="store_true",
                     help="time the oracle on the WHOLE text (minutes, ~(1 + 4w) n bytes of host memory) and compare its SA / LCP with the "
-                         "GPU's entry by entry, whatever the projection says (the default does this when host memory and time allow)")
+                         "GPU's entry by entry, whatever the projection says (implies --full, which does this when host memory and time "
+                         "allow)")
     ap.add_argument("--cpu-sample-only", action="store_true",
                     help="CPU baseline on the --cpu-sample prefix only (also: CAPS_BENCH_CPU_FULL=0)")
     ap.add_argument("--cpu-full-budget-s", type=float, default=float(os.environ.get("CAPS_BENCH_CPU_FULL_BUDGET_S", "330")),
-                    help="the default run times the oracle on the whole text only when the sample's rate projects it under this many seconds")
-    ap.add_argument("--no-verify", action="store_true", help="skip the device verifier after the timed steps")
-    ap.add_argument("--verify", action="store_true", help="(default; kept for old command lines)")
-    ap.add_argument("--no-host-path", action="store_true", help="skip timing the host-buffer entry point (PCIe inclusive)")
+                    help="--full times the oracle on the whole text only when the sample's rate projects it under this many seconds")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the device verifier after the timed steps")
+    ap.add_argument("--verify", action="store_true", help="(kept for old command lines: --full runs the verifier)")
+    ap.add_argument("--no-host-path", action="store_true", help="--full: skip timing the host-buffer entry point (PCIe inclusive)")
     ap.add_argument("--shard-mode", default="auto", choices=["local", "exchange", "auto"],
                     help="N > 1: how the direct path is sharded (caps_sa_dist.bench_main); auto times both in the warm-up and keeps the faster")
     ap.add_argument("--text-file", default="", help="read the workload's text from this .npy file (tools/make_text.py wrote it) instead of "
                     "generating it: the genome-like generators launch ~1e6 tiny kernels, which rocprofv3 --pmc does not survive")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.cpu_full:
+        args.full = True
+    if not args.full:
+        args.no_verify = args.no_cpu_baseline = args.no_host_path = True
+    return args
+
+
+def dump_outputs(torch, out_dir, SA, LCP, idx_bits):
+    """--dump-outputs: the SA and LCP the last timed step left in HBM, as float64 (exact: every entry is below 2^53).  A longer
+    text is sampled at the same DUMP_SAMPLE sorted positions on every run (drawn from a fixed seed, so that two builds of the
+    project can be compared entry for entry; 2 x 16 MiB in all)."""
+    n = SA.numel()
+    if n > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        pos = torch.randint(0, n, (DUMP_SAMPLE,), generator=g, dtype=torch.int64).sort().values.to(SA.device)
+    else:
+        pos = torch.arange(n, device=SA.device)
+    os.makedirs(out_dir, exist_ok=True)
+    import numpy as np
+    for name, a in (("SA", SA), ("LCP", LCP)):
+        v = a[pos].to(torch.int64)
+        if idx_bits == 32:
+            v &= 0xFFFFFFFF                          # u32 results live in int32 tensors
+        np.save(os.path.join(out_dir, f"{name}.npy"), v.to(torch.float64).cpu().numpy())
 
 
 def main():
@@ -327,6 +367,8 @@ def main():
     if world > 1 or os.environ.get("CAPS_SA_FORCE_SHARDED") == "1":
         # sharded path (one process per GPU, RCCL exchange); CAPS_SA_FORCE_SHARDED=1 runs it at world
         # size 1 too (smoke test of the multi-GPU driver on a 1-GPU box)
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: single-GPU runs only (the sharded path leaves a slice of SA and LCP on each rank)")
         import caps_sa_dist
         return caps_sa_dist.bench_main(args, rank, local_rank, world)
 
@@ -375,6 +417,8 @@ def main():
     elapsed = time.perf_counter() - t0
     ms_per_step = 1e3 * elapsed / args.steps
     value = n / (elapsed / args.steps)
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, SA, LCP, idx_bits)
     verify_errors = None if args.no_verify else L.verify_device(T.data_ptr(), n, SA.data_ptr(), LCP.data_ptr(), idx_bits=idx_bits)
 
     # kernel families of the timed steps (HIP events on the build's stream around every launch, summed in caps_sa_stats)

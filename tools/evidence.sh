@@ -2,9 +2,9 @@
 # tools/evidence.sh -- every measurement of profiles/ comes from one of these sub-commands, run on the GPU box:
 #   gpurun -- 'bash tools/evidence.sh <cmd> [args] && bash tools/evidence.sh <cmd> ...'
 # TAG (default r04_a) prefixes the files written under gpurun_out/ (copy the ones to be judged into profiles/).
-#   bench [wl ...]      bench lines (--no-cpu-baseline --no-host-path unless EXTRA overrides; STEPS, WARMUP)
+#   bench [wl ...]      bench lines with the device verifier (--full --no-cpu-baseline --no-host-path unless EXTRA overrides; STEPS, WARMUP)
 #   default             `python bench.py` exactly as the driver runs it
-#   cpufull             `python bench.py --cpu-full`: the oracle on the whole C3 text + entry-by-entry comparison
+#   cpufull             `python bench.py --full --cpu-full`: the oracle on the whole C3 text + entry-by-entry comparison
 #   prof <wl>           rocprofv3 --kernel-trace --stats of 3 builds (caps kernels only)
 #   pmc <wl> [groups]   PMC passes (tools/pmc.sh) + traffic figures into profiles/traffic.json
 #   phase <wl ...>      phase clock of the tile sorts (variant `phase`)
@@ -33,14 +33,14 @@ PY
 case $cmd in
   bench)
     for wl in "${@:-c3}"; do
-      timeout -k 10 ${TMO:-420} python3 bench.py --workload $wl --steps ${STEPS:-3} --warmup ${WARMUP:-1} ${EXTRA---no-cpu-baseline --no-host-path} > $O/${T}_${wl}_bench.json.log 2> $O/${T}_${wl}_bench.err
+      timeout -k 10 ${TMO:-420} python3 bench.py --full --workload $wl --steps ${STEPS:-3} --warmup ${WARMUP:-1} ${EXTRA---no-cpu-baseline --no-host-path} > $O/${T}_${wl}_bench.json.log 2> $O/${T}_${wl}_bench.err
       rc=$?; echo "bench $wl rc=$rc"; summ $O/${T}_${wl}_bench.json.log
       [ $rc -eq 124 ] || [ $rc -eq 137 ] && exit 1
     done ;;
   default)
     timeout -k 10 560 python3 bench.py > $O/${T}_c3_bench.json.log 2> $O/${T}_c3_bench.err; rc=$?; echo "default rc=$rc"; summ $O/${T}_c3_bench.json.log; exit $rc ;;
   cpufull)
-    timeout -k 10 ${TMO:-1000} python3 bench.py --cpu-full --no-host-path --steps 3 > $O/${T}_c3_cpu_full_bench.json.log 2> $O/${T}_c3_cpu_full_bench.err; rc=$?
+    timeout -k 10 ${TMO:-1000} python3 bench.py --full --cpu-full --no-host-path --steps 3 > $O/${T}_c3_cpu_full_bench.json.log 2> $O/${T}_c3_cpu_full_bench.err; rc=$?
     echo "cpufull rc=$rc"; python3 -c "
 import json;d=json.loads([l for l in open('$O/${T}_c3_cpu_full_bench.json.log') if l.startswith('{')][-1]);print(round(d['ms_per_step'],2),d['verify_errors'],json.dumps(d['cpu_baseline'])[:900],d.get('cpu_baseline_full_skipped'))"; exit $rc ;;
   prof)
@@ -72,7 +72,7 @@ PY
     wl=$1; shift
     for v in "$@"; do
       lib=$PWD/variants/libcaps_sa_hip_$v.so; [ "$v" = base ] && lib=$PWD/caps-sa_amd/libcaps_sa_hip.so
-      CAPS_SA_LIB=$lib timeout -k 10 ${TMO:-420} python3 bench.py --workload $wl --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-host-path > $O/${T}_var_${v}_${wl}.json.log 2> $O/${T}_var_${v}_${wl}.err
+      CAPS_SA_LIB=$lib timeout -k 10 ${TMO:-420} python3 bench.py --full --workload $wl --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-host-path > $O/${T}_var_${v}_${wl}.json.log 2> $O/${T}_var_${v}_${wl}.err
       rc=$?; echo "variant $v $wl rc=$rc"; summ $O/${T}_var_${v}_${wl}.json.log
       [ $rc -eq 124 ] || [ $rc -eq 137 ] && exit 1
     done ;;
