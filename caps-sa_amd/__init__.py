@@ -49,11 +49,14 @@ class SuffixArray:
 
     ``SuffixArray(T, subproblem_count=0, max_context=0)``; ``construct()``; ``SA()``;
     ``LCP()``; ``T()``; ``n()``; ``dump(path)``.  Index width follows src/main.cpp:76-87
-    unless ``idx_bits`` is given.
+    unless ``idx_bits`` is given.  ``bwt=True``: ``construct()`` also returns the Burrows-Wheeler
+    transform, ``BWT()`` (np.uint8) and ``primary()`` (include/caps_sa_hip.h; one device only).
     """
 
     def __init__(self, T, subproblem_count: int = 0, max_context: int = 0, idx_bits: int | None = None, device: int = 0,
-                 devices: list[int] | None = None, pinned: bool = False):
+                 devices: list[int] | None = None, pinned: bool = False, bwt: bool = False):
+        if bwt and devices:
+            raise ValueError("bwt=True is built on one device: the sharded build (devices=[...]) has no BWT output")
         self._T = CapsLib._text(T)
         self._n = int(self._T.size)
         self._p = int(subproblem_count)
@@ -62,8 +65,11 @@ class SuffixArray:
         self._device = device
         self._devices = list(devices) if devices else None      # several GPUs from this process (caps_sa_hip_build_multi_*)
         self._pinned = pinned                                    # page-locked result arrays (what the C++ mirror allocates)
+        self._bwt = bool(bwt)
         self._SA = None
         self._LCP = None
+        self._BWT = None
+        self._primary: int | None = None
         self.stats: dict | None = None
 
     def T(self) -> np.ndarray:
@@ -73,7 +79,10 @@ class SuffixArray:
         return self._n
 
     def construct(self) -> None:
-        if self._devices:
+        if self._bwt:
+            self._SA, self._LCP, self._BWT, self._primary, self.stats = lib().build_bwt(self._T, self._p, self._ctx, self._bits,
+                                                                                       self._device, self._pinned)
+        elif self._devices:
             self._SA, self._LCP, self.stats = lib().build_multi(self._T, self._devices, self._p, self._ctx, self._bits, self._pinned)
         else:
             self._SA, self._LCP, self.stats = lib().build(self._T, self._p, self._ctx, self._bits, self._device, self._pinned)
@@ -87,6 +96,22 @@ class SuffixArray:
         if self._LCP is None:
             raise RuntimeError("construct() has not been called")
         return self._LCP
+
+    def BWT(self) -> np.ndarray:
+        """BWT[k] = T[(SA[k] + n - 1) mod n] (needs bwt=True)."""
+        if not self._bwt:
+            raise RuntimeError("the BWT was not asked for: SuffixArray(..., bwt=True)")
+        if self._BWT is None:
+            raise RuntimeError("construct() has not been called")
+        return self._BWT
+
+    def primary(self) -> int:
+        """The k with SA[k] == 0 (needs bwt=True)."""
+        if not self._bwt:
+            raise RuntimeError("the BWT was not asked for: SuffixArray(..., bwt=True)")
+        if self._primary is None:
+            raise RuntimeError("construct() has not been called")
+        return self._primary
 
     def dump(self, path: str) -> None:
         """Suffix_Array::dump format (src/Suffix_Array.cpp:497-509): u64 n, SA, LCP."""

@@ -124,7 +124,7 @@ EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_b
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
     for name in ("build", "build_multi", "build_device", "verify_device", "verify_slice_device", "sort_suffixes", "sort_segments", "merge",
-                 "upper_bound", "lcp")
+                 "upper_bound", "lcp", "build_bwt", "bwt_device")
 ]
 
 
@@ -175,6 +175,10 @@ class CapsLib:
             f(f"build_multi_{sfx}").argtypes = [_vp, _u64, _u64, _u64, _vp, _vp, _vp, _ci, ctypes.POINTER(Stats)]
             f(f"build_device_{sfx}").restype = _ci
             f(f"build_device_{sfx}").argtypes = [_vp, _u64, _u64, _u64, _vp, _vp, _vp, _u64, _vp, ctypes.POINTER(Stats)]
+            f(f"build_bwt_{sfx}").restype = _ci
+            f(f"build_bwt_{sfx}").argtypes = [_vp, _u64, _u64, _u64, _vp, _vp, _vp, ctypes.POINTER(_u64), _ci, ctypes.POINTER(Stats)]
+            f(f"bwt_device_{sfx}").restype = _ci
+            f(f"bwt_device_{sfx}").argtypes = [_vp, _u64, _vp, _u64, _u64, _vp, _vp, ctypes.POINTER(_u64)]
             f(f"verify_device_{sfx}").restype = _ci
             f(f"verify_device_{sfx}").argtypes = [_vp, _u64, _vp, _vp, _vp, ctypes.POINTER(_u64)]
             f(f"verify_slice_device_{sfx}").restype = _ci
@@ -295,6 +299,20 @@ class CapsLib:
                                             device, ctypes.byref(st)))
         return st.as_dict()
 
+    def build_bwt(self, T, p: int = 0, max_context: int = 0, idx_bits: int = 32, device: int = 0, pinned: bool = False):
+        """construct() plus the Burrows-Wheeler transform (include/caps_sa_hip.h) -> (SA, LCP, BWT, primary, stats dict).
+        BWT[k] = T[(SA[k] + n - 1) mod n] (np.uint8); primary = the k with SA[k] == 0 (2**64 - 1 when n = 0)."""
+        T = self._text(T)
+        sfx, dt = _sfx(idx_bits)
+        SA = self.pinned_empty(T.size, dt) if pinned else np.empty(T.size, dtype=dt)
+        LCP = self.pinned_empty(T.size, dt) if pinned else np.empty(T.size, dtype=dt)
+        BWT = self.pinned_empty(T.size, np.uint8) if pinned else np.empty(T.size, dtype=np.uint8)
+        primary = _u64(0)
+        st = Stats()
+        self._check(self._f(f"build_bwt_{sfx}")(T.ctypes.data, T.size, p, max_context, SA.ctypes.data, LCP.ctypes.data, BWT.ctypes.data,
+                                                ctypes.byref(primary), device, ctypes.byref(st)))
+        return SA, LCP, BWT, primary.value, st.as_dict()
+
     def build_multi(self, T, devices, p: int = 0, max_context: int = 0, idx_bits: int = 32, pinned: bool = False):
         """construct() on several GPUs from this process (caps_sa_hip_build_multi_*) -> (SA, LCP, stats dict)."""
         T = self._text(T)
@@ -329,6 +347,16 @@ class CapsLib:
         self._check(self._f(f"verify_slice_device_{sfx}")(dT_ptr, n, dSA_ptr, dLCP_ptr, cnt, 1 if is_head else 0, stream or None,
                                                           ctypes.byref(err)))
         return err.value
+
+    def bwt_device(self, dT_ptr: int, n: int, dSA_ptr: int, first: int, cnt: int, dBWT_ptr: int, idx_bits: int = 32,
+                   stream: int = 0) -> int:
+        """BWT of the suffix-array slice at dSA_ptr (ranks first .. first + cnt) into dBWT_ptr (cnt bytes, device) -> primary
+        (first + k for the k with SA == 0 in the slice, else 2**64 - 1)."""
+        sfx, _ = _sfx(idx_bits)
+        primary = _u64(0)
+        self._check(self._f(f"bwt_device_{sfx}")(dT_ptr or None, n, dSA_ptr or None, first, cnt, dBWT_ptr or None, stream or None,
+                                                 ctypes.byref(primary)))
+        return primary.value
 
     # ------------------------------------------------------------------ kernel-level entry points
     def sort_suffixes(self, T, idx, idx_bits: int = 32, device: int = 0):

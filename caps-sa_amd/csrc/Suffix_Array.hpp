@@ -15,7 +15,9 @@
 //  * SA_ / LCP_ are page-locked (caps_sa_hip_host_alloc) when the driver grants it, plain malloc otherwise: the
 //    results then leave the GPU at the PCIe link rate (C2: 38 ms instead of 88 ms for the two arrays) -- like the
 //    reference's mallocs (src/Suffix_Array.cpp:20-21) the allocation belongs to the constructor, not to construct();
-//  * an optional list of devices: construct() then shards the build over them (caps_sa_hip_build_multi_*).
+//  * an optional list of devices: construct() then shards the build over them (caps_sa_hip_build_multi_*);
+//  * construct_bwt() (not in the reference): construct() plus the Burrows-Wheeler transform (include/caps_sa_hip.h), one device;
+//    its n-byte buffer is allocated by the first construct_bwt(), so construct() callers pay nothing for it.
 #ifndef CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 #define CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 
@@ -50,7 +52,7 @@ public:
 
     // devices: HIP device ordinals the build is sharded over (one: the single-GPU build)
     Suffix_Array(const char* T, idx_t n, idx_t subproblem_count, idx_t max_context, const std::vector<int>& devices)
-        : T_(T), n_(n), SA_(nullptr), LCP_(nullptr), pinned_(false),
+        : T_(T), n_(n), SA_(nullptr), LCP_(nullptr), pinned_(false), BWT_(nullptr), bwt_pinned_(false), primary_(UINT64_MAX),
           subproblem_count_(subproblem_count), max_context_(max_context), devices_(devices), stats_()
     {
         if (devices_.empty()) throw std::invalid_argument("Suffix_Array: no devices");
@@ -75,6 +77,8 @@ public:
     {
         if (pinned_) { caps_sa_hip_host_free(SA_); caps_sa_hip_host_free(LCP_); }
         else { std::free(SA_); std::free(LCP_); }
+        if (bwt_pinned_) caps_sa_hip_host_free(BWT_);
+        else std::free(BWT_);
     }
 
     const char* T() const { return T_; }                        // hpp:165
@@ -97,6 +101,31 @@ public:
             throw std::runtime_error(std::string("caps_sa_hip_build: ") + caps_sa_hip_last_error());
     }
 
+    // construct() plus the BWT: BWT()[k] = T[(SA[k] + n - 1) mod n], primary() = the k with SA[k] == 0 (UINT64_MAX for n = 0).
+    // One device only (the sharded build has no BWT output): throws std::invalid_argument with more.
+    void construct_bwt()
+    {
+        if (devices_.size() != 1) throw std::invalid_argument("Suffix_Array::construct_bwt: one device only (the sharded build has no BWT)");
+        if (!BWT_) {                                          // on first use, page-locked when the driver grants it (like SA_ / LCP_)
+            const std::size_t bytes = n_ ? static_cast<std::size_t>(n_) : 1;
+            BWT_ = static_cast<uint8_t*>(caps_sa_hip_host_alloc(bytes));
+            bwt_pinned_ = BWT_ != nullptr;
+            if (!BWT_) BWT_ = static_cast<uint8_t*>(std::malloc(bytes));
+            if (!BWT_) throw std::bad_alloc();
+        }
+        int rc;
+        if (std::is_same<idx_t, uint32_t>::value)
+            rc = caps_sa_hip_build_bwt_u32(T_, n_, subproblem_count_, max_context_, reinterpret_cast<uint32_t*>(SA_),
+                                           reinterpret_cast<uint32_t*>(LCP_), BWT_, &primary_, devices_[0], &stats_);
+        else
+            rc = caps_sa_hip_build_bwt_u64(T_, n_, subproblem_count_, max_context_, reinterpret_cast<uint64_t*>(SA_),
+                                           reinterpret_cast<uint64_t*>(LCP_), BWT_, &primary_, devices_[0], &stats_);
+        if (rc != CAPS_SA_OK)
+            throw std::runtime_error(std::string("caps_sa_hip_build_bwt: ") + caps_sa_hip_last_error());
+    }
+    const uint8_t* BWT() const { return BWT_; }                 // null before the first construct_bwt()
+    uint64_t primary() const { return primary_; }
+
     // Reference: src/Suffix_Array.cpp:497-509 -- u64 n, then SA, then LCP, native endianness.
     void dump(std::ofstream& output)
     {
@@ -115,6 +144,9 @@ private:
     idx_t* SA_;
     idx_t* LCP_;
     bool pinned_;
+    uint8_t* BWT_;
+    bool bwt_pinned_;
+    uint64_t primary_;
     const idx_t subproblem_count_;
     const idx_t max_context_;
     const std::vector<int> devices_;

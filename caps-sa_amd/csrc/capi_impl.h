@@ -134,6 +134,7 @@ int build_device(const void* dT, uint64_t n, uint64_t p_arg, uint64_t max_contex
             } else scratch_elems = 0;
         }
         b.set_waves(waves, sink, scratch, scratch_elems);
+        if (sink) sink->text(pl.P, pl.lut);
         if (max_context != 0 && max_context < n && pl.p < 2)
             return fail(CAPS_SA_EUNSUPPORTED, "bounded max_context needs at least two subproblems (the reference divides by zero there)");
         b.build(static_cast<const uint8_t*>(dT), static_cast<idx_t*>(dSA), static_cast<idx_t*>(dLCP), stats, max_context);
@@ -186,6 +187,16 @@ inline void widen_bytes(const uint8_t* in, uint32_t* out, uint64_t cnt)
     for (; i < cnt; ++i) out[i] = in[i];
 }
 
+// BWT of the suffix-array slice dSA[0 .. cnt) (ranks first .. first + cnt) into out[0 .. cnt), on be's stream (kernels.h bwt_kernel).
+// *dprimary is written only when the slice holds the entry 0: the caller arms it with UINT64_MAX.
+template <typename idx_t>
+void launch_bwt(Backend& be, const uint8_t* dT, uint64_t n, const idx_t* dSA, uint64_t first, uint64_t cnt, uint8_t* out, uint64_t* dprimary)
+{
+    if (!cnt) return;
+    const uint64_t rounds = (cnt + 256ull * BWT_PER - 1) / (256ull * BWT_PER);
+    CAPS_LAUNCH((bwt_kernel<idx_t>), capped_grid(std::min<uint64_t>(rounds, 8192), 256), 256, be, dT, n, dSA, first, cnt, out, dprimary);
+}
+
 template <typename idx_t> struct HostCopySink : WaveSink {
     decltype(Backend::stream) copy_stream;
     idx_t *SA, *LCP;
@@ -213,6 +224,19 @@ template <typename idx_t> struct HostCopySink : WaveSink {
     bool closing = false, busy = false;
     std::thread dispatcher;
     std::exception_ptr failure;
+    // the BWT (null: not asked for): every slice gathered from the build's packed text on the copy stream (bwt_packed_kernel), then
+    // copied to BWT + base; the paths that stream nothing gather once from the raw text dT after the build.  Its own device bytes
+    // (dBWT, dprimary), apart from the LCP bytes above.
+    uint64_t n = 0;
+    uint8_t* dBWT = nullptr;
+    uint64_t* dprimary = nullptr;
+    uint8_t* BWT = nullptr;
+    // the packed text and its byte -> code table (WaveSink::text); pbits = 0 until the first slice has made code2byte from the table
+    const uint32_t* Ptext = nullptr;
+    const uint8_t* dlut = nullptr;
+    int pbits = 0;
+    uint32_t code2byte = 0;
+    void text(const uint32_t* P, const uint8_t* lut) override { Ptext = P; dlut = lut; }
 
     bool narrow() const { return d8 != nullptr; }
     // f(chunk pointer + offset, position, length) for the pieces of [base, base + cnt) chunk by chunk
@@ -294,6 +318,27 @@ template <typename idx_t> struct HostCopySink : WaveSink {
     void wave_done(Backend& be, uint64_t base, uint64_t cnt) override
     {
         Backend::stream_wait(copy_stream, be.record());
+        if (dBWT) {
+            Backend cb(copy_stream);
+            if (!pbits) {                                   // code -> byte from the build's table (written by prepare_text, long before the first slice):
+                                                            // 2-bit tables hold codes 0..3 and 0xFF (absent bytes), 8-bit ones 256 distinct codes
+                uint8_t lut[256];
+                Backend::d2h_on(copy_stream, lut, dlut, 256);
+                Backend::sync_stream(copy_stream);
+                int distinct = 0;
+                bool seen[256] = {false};
+                for (int c = 0; c < 256; ++c) if (!seen[lut[c]]) { seen[lut[c]] = true; ++distinct; }
+                pbits = distinct > 5 ? 8 : 2;
+                code2byte = 0;
+                if (pbits == 2) for (int c = 0; c < 256; ++c) if (lut[c] < 4) code2byte |= (uint32_t)c << (8 * lut[c]);
+            }
+            const uint64_t rounds = (cnt + 256ull * BWT_PER - 1) / (256ull * BWT_PER);
+            const uint32_t g = capped_grid(std::min<uint64_t>(rounds, 8192), 256);
+            if (cnt && pbits == 2)
+                CAPS_LAUNCH((bwt_packed_kernel<idx_t, 2>), g, 256, cb, Ptext, n, dSA + base, base, cnt, dBWT + base, dprimary, code2byte);
+            else if (cnt)
+                CAPS_LAUNCH((bwt_packed_kernel<idx_t, 8>), g, 256, cb, Ptext, n, dSA + base, base, cnt, dBWT + base, dprimary, code2byte);
+        }
         if (narrow()) {
             Backend cb(copy_stream);
             const uint64_t rounds = (cnt + 256ull * NARROW_PER - 1) / (256ull * NARROW_PER);
@@ -316,6 +361,7 @@ template <typename idx_t> struct HostCopySink : WaveSink {
             Backend::d2h_on(copy_stream, SA + base, dSA + base, cnt * sizeof(idx_t));
             Backend::d2h_on(copy_stream, LCP + base, dLCP + base, cnt * sizeof(idx_t));
         }
+        if (dBWT) Backend::d2h_on(copy_stream, BWT + base, dBWT + base, cnt);
         copied += cnt;
     }
     void reset(Backend&) override
@@ -323,6 +369,7 @@ template <typename idx_t> struct HostCopySink : WaveSink {
         Backend::sync_stream(copy_stream);                  // nothing reads the device arrays any more
         drain();
         if (narrow()) { Backend::memset_on(copy_stream, dexc_count, 0, sizeof(uint64_t)); Backend::sync_stream(copy_stream); }
+        if (dprimary) { Backend::memset_on(copy_stream, dprimary, 0xFF, sizeof(uint64_t)); Backend::sync_stream(copy_stream); }   // the slices come again
         copied = 0;
     }
     // after the last slice: the values of 255 and more.  false: more of them than the list holds -- the caller copies LCP at full width
@@ -399,12 +446,15 @@ inline void release_host_cache_locked(HostPathCache& c)
     c.device = -1;
 }
 
+// BWT (build_bwt): null, or n bytes of the caller's that receive the BWT slice by slice with the rest of the result (HostCopySink);
+// *primary then the rank of the suffix 0.
 template <typename idx_t>
 int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, idx_t* SA, idx_t* LCP, int device,
-               caps_sa_stats* stats)
+               caps_sa_stats* stats, uint8_t* BWT = nullptr, uint64_t* primary = nullptr)
 {
     if (int rc = check_common<idx_t>(T, n, max_context)) return rc;
     if (n && (!SA || !LCP)) return fail(CAPS_SA_EINVAL, "null output");
+    const bool want_bwt = BWT != nullptr && n != 0;
     DeviceScope restore_device_;
     if (int rc = set_device(device)) return rc;
     return guarded([&]() -> int {
@@ -444,7 +494,9 @@ int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, 
         const uint64_t exc_cap = narrow || narrow_later ? std::max<uint64_t>(1024, n / 32) : 0;
         const size_t narrow_dev = narrow || narrow_later ? up(n) + up((exc_cap + 1) * sizeof(uint64_t)) + 512 : 0;
         const size_t ws_room = need.bytes + 1024 + wave_scratch_bytes<idx_t>(wave_scratch_elems(n, waves));
-        const size_t total = off_ws + ws_room + narrow_dev;
+        // the BWT's bytes and its primary index, behind everything else (builds without a BWT ask for the block they always did)
+        const size_t off_bwt = off_ws + up(ws_room) + up(narrow_dev);
+        const size_t total = want_bwt ? off_bwt + up(n) + 512 : off_ws + ws_room + narrow_dev;
         if (hc.device != device || hc.bytes < total) {
             std::vector<char*> keep;
             keep.swap(hc.host_chunks);                       // (the staging chunks survive a larger device block)
@@ -538,6 +590,14 @@ int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, 
             be.memset(sink.dexc_count, 0, sizeof(uint64_t));
             be.sync();
         }
+        if (want_bwt) {
+            sink.n = n;
+            sink.dBWT = reinterpret_cast<uint8_t*>(base + off_bwt);
+            sink.dprimary = reinterpret_cast<uint64_t*>(base + off_bwt + up(n));
+            sink.BWT = BWT;
+            be.memset(sink.dprimary, 0xFF, sizeof(uint64_t));
+            be.sync();
+        }
         sink.start();
         struct StreamGuard { decltype(Backend::stream) s; ~StreamGuard() { Backend::destroy_stream(s); } } guard{sink.copy_stream};
         bool served = false;
@@ -552,6 +612,11 @@ int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, 
             sink.drain();
             be.d2h(SA, dSA, n * sizeof(idx_t));
             be.d2h(LCP, dLCP, n * sizeof(idx_t));
+            if (want_bwt) {                          // ... and no BWT either: one gather over the whole suffix array
+                be.memset(sink.dprimary, 0xFF, sizeof(uint64_t));
+                launch_bwt<idx_t>(be, dT, n, dSA, 0, n, sink.dBWT, sink.dprimary);
+                be.d2h(BWT, sink.dBWT, n);
+            }
             be.sync();
             local.result_waves = 1;
             lcp_as_bytes = false;
@@ -561,6 +626,11 @@ int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, 
             lcp_as_bytes = false;
         }
         sink.stop();
+        if (want_bwt) {                              // (the copy stream has finished: finish_lcp / the branch above synchronised)
+            Backend::sync_stream(sink.copy_stream);
+            be.d2h(primary, sink.dprimary, sizeof(uint64_t));
+            be.sync();
+        }
         local.lcp_bytes_on_link = lcp_as_bytes ? 1u : (uint32_t)sizeof(idx_t);
         local.ms_h2d = be.elapsed_ms(h0, h1);
         // build + result copies, overlapped: host wall clock from the launch of the build to the last byte on the host, minus the build
@@ -630,7 +700,7 @@ template <typename R, typename F> void for_each_rank(std::vector<std::unique_ptr
 
 template <typename idx_t>
 int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, idx_t* SA, idx_t* LCP, int device,
-               caps_sa_stats* stats);
+               caps_sa_stats* stats, uint8_t* BWT, uint64_t* primary);
 
 template <typename idx_t>
 int build_multi(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, idx_t* SA, idx_t* LCP, const int* devices,
@@ -862,6 +932,58 @@ int verify_device(const void* dT, uint64_t n, const void* dSA, const void* dLCP,
         CAPS_LAUNCH((verify_kernel<idx_t>), want < 16384 ? want : 16384, 256, be, static_cast<const int8_t*>(dT), n,
                     static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), cnt, head, seen, err);
         be.d2h(n_errors, err, sizeof(uint64_t));
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+
+// construct() plus the BWT (include/caps_sa_hip.h caps_sa_hip_build_bwt_*)
+template <typename idx_t>
+int build_bwt(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, idx_t* SA, idx_t* LCP, uint8_t* BWT, uint64_t* primary,
+              int device, caps_sa_stats* stats)
+{
+    if (!primary) return fail(CAPS_SA_EINVAL, "null primary");
+    *primary = ~0ull;
+    if (n && !BWT) return fail(CAPS_SA_EINVAL, "null BWT");
+    if (max_context != 0 && max_context < n)
+        return fail(CAPS_SA_EUNSUPPORTED, "a bounded-context order is not a suffix array: it has no BWT");
+    return build_host<idx_t>(T, n, p_arg, max_context, SA, LCP, device, stats, BWT, primary);
+}
+
+// The device word bwt_device's kernel writes primary to: one per thread and device, allocated by the first call and kept (a hipFree
+// per call would synchronise the whole device every time a slice is transformed).  A call uses it from its memset to its final
+// synchronisation, so one per thread suffices.
+inline uint64_t* primary_word(Backend& be)
+{
+#ifdef CAPS_EMUL
+    const int dev = 0;
+#else
+    int dev = 0;
+    CAPS_HIP(hipGetDevice(&dev));
+#endif
+    thread_local std::vector<uint64_t*> words;
+    if ((size_t)dev >= words.size()) words.resize((size_t)dev + 1, nullptr);
+    if (!words[dev]) words[dev] = static_cast<uint64_t*>(be.alloc(sizeof(uint64_t)));
+    return words[dev];
+}
+
+// BWT of a slice of a suffix array in HBM (include/caps_sa_hip.h caps_sa_hip_bwt_device_*)
+template <typename idx_t>
+int bwt_device(const void* dT, uint64_t n, const void* dSA, uint64_t first, uint64_t cnt, void* dBWT, void* stream, uint64_t* primary)
+{
+    if (!primary) return fail(CAPS_SA_EINVAL, "null primary");
+    *primary = ~0ull;
+    if (int rc = check_common<idx_t>(dT, n, 0)) return rc;
+    if (first > n || cnt > n - first) return fail(CAPS_SA_EINVAL, "first + cnt > n");
+    if (cnt == 0) return CAPS_SA_OK;
+    if (!dSA || !dBWT) return fail(CAPS_SA_EINVAL, "null pointer");
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        uint64_t* dprimary = primary_word(be);
+        be.memset(dprimary, 0xFF, sizeof(uint64_t));
+        launch_bwt<idx_t>(be, static_cast<const uint8_t*>(dT), n, static_cast<const idx_t*>(dSA), first, cnt, static_cast<uint8_t*>(dBWT),
+                          dprimary);
+        be.d2h(primary, dprimary, sizeof(uint64_t));
         be.sync();
         return CAPS_SA_OK;
     });
@@ -1236,6 +1358,12 @@ int CAPS_API(workspace_bytes)(uint64_t n, uint64_t subproblem_count, int idx_byt
     int CAPS_API(build_device_##SFX)(const void* dT, uint64_t n, uint64_t p, uint64_t ctx, void* dSA, void* dLCP,          \
                                      void* ws, uint64_t ws_bytes, void* stream, caps_sa_stats* st)                         \
     { return caps::build_device<IDX>(dT, n, p, ctx, dSA, dLCP, ws, ws_bytes, stream, st); }                                \
+    int CAPS_API(build_bwt_##SFX)(const char* T, uint64_t n, uint64_t p, uint64_t ctx, IDX* SA, IDX* LCP, uint8_t* BWT,       \
+                                  uint64_t* primary, int device, caps_sa_stats* st)                                        \
+    { return caps::build_bwt<IDX>(T, n, p, ctx, SA, LCP, BWT, primary, device, st); }                                      \
+    int CAPS_API(bwt_device_##SFX)(const void* dT, uint64_t n, const void* dSA, uint64_t first, uint64_t cnt, void* dBWT,   \
+                                   void* stream, uint64_t* primary)                                                        \
+    { return caps::bwt_device<IDX>(dT, n, dSA, first, cnt, dBWT, stream, primary); }                                       \
     int CAPS_API(verify_device_##SFX)(const void* dT, uint64_t n, const void* dSA, const void* dLCP, void* stream,          \
                                       uint64_t* n_errors)                                                                  \
     { return caps::verify_device<IDX>(dT, n, dSA, dLCP, stream, n_errors); }                                               \

@@ -1,9 +1,12 @@
 // caps-sa_amd/csrc/caps_sa_cli.cpp -- command-line driver with the reference CLI's contract
 // (reference src/main.cpp:43-93):
 //
-//     caps_sa <input_path> <output_path> [subproblem-count] [bounded-context] [--pretty-print] [--gpus N]
+//     caps_sa <input_path> <output_path> [subproblem-count] [bounded-context] [--pretty-print] [--gpus N] [--bwt PATH]
 //
 // * --gpus N (not in the reference): shard the build over HIP devices 0 .. N-1;
+// * --bwt PATH (not in the reference): also write the Burrows-Wheeler transform of the (remapped) text to PATH after the SA / LCP
+//   output: u64 n, u64 primary, n bytes, native endianness (include/caps_sa_hip.h has the definition).  One GPU, no bounded
+//   context: both are refused before any file is opened;
 // * bounded-context (main.cpp:57): 0 or >= the text length = the suffix array; a smaller bound takes the reference's own
 //   sequence of merges (csrc/bounded.h: its output depends on them; a compatibility mode, seconds instead of milliseconds);
 // * every input byte is remapped to {A,C,G,T} with lookup[(toupper(c) & 0x6) >> 1],
@@ -23,6 +26,8 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include <sys/stat.h>
 
 #include "Suffix_Array.hpp"
 
@@ -51,7 +56,8 @@ static bool parse_count(const std::string& s, size_t& out)
 }
 
 template <typename idx_t>
-static int run(const std::string& text, const std::string& out_path, size_t p, size_t ctx, bool pretty, const std::vector<int>& devices)
+static int run(const std::string& text, const std::string& out_path, size_t p, size_t ctx, bool pretty, const std::vector<int>& devices,
+               const std::string& bwt_path)
 {
     if (p > std::numeric_limits<idx_t>::max()) { std::cerr << "subproblem-count does not fit the index type\n"; return EXIT_FAILURE; }
     // the bounded-context mode replays the reference's merge history, one GPU thread per merge node -- the top levels
@@ -62,7 +68,8 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
                   << " seconds for " << (text.size() >> 20) << " Mi chars; the unbounded construction takes milliseconds.\n";
     CaPS_SA::Suffix_Array<idx_t> suf_arr(text.c_str(), static_cast<idx_t>(text.size()), static_cast<idx_t>(p),
                                          static_cast<idx_t>(ctx >= text.size() ? 0 : ctx), devices);
-    suf_arr.construct();
+    if (bwt_path.empty()) suf_arr.construct();
+    else suf_arr.construct_bwt();
     const caps_sa_stats& st = suf_arr.stats();
     std::cerr << "Constructed the suffix array. Device time: " << st.ms_total / 1e3 << " seconds (h2d "
               << st.ms_h2d / 1e3 << ", d2h " << st.ms_d2h / 1e3 << "); subproblems " << st.p_eff << ", "
@@ -75,28 +82,53 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
         for (size_t i = 0; i < n; ++i) output << suf_arr.LCP()[i] << " \n"[i == n - 1];
     } else
         suf_arr.dump(output);
-    return output ? 0 : EXIT_FAILURE;
+    if (!output) return EXIT_FAILURE;
+    if (!bwt_path.empty()) {
+        std::ofstream bwt(bwt_path, std::ios::binary);
+        if (!bwt) { std::cerr << bwt_path << " : cannot open for writing\n"; return EXIT_FAILURE; }
+        const uint64_t n = suf_arr.n(), primary = suf_arr.primary();
+        bwt.write(reinterpret_cast<const char*>(&n), sizeof n);
+        bwt.write(reinterpret_cast<const char*>(&primary), sizeof primary);
+        bwt.write(reinterpret_cast<const char*>(suf_arr.BWT()), static_cast<std::streamsize>(n));
+        if (!bwt) return EXIT_FAILURE;
+    }
+    return 0;
 }
 
 int main(int argc, char* argv[])
 {
     std::vector<std::string> pos;
-    bool pretty = false;
+    bool pretty = false, bwt = false;
     size_t gpus = 1;
+    std::string bwt_path;
     for (int i = 1; i < argc; ++i) {
         if (std::strcmp(argv[i], "--pretty-print") == 0) pretty = true;
+        else if (std::strcmp(argv[i], "--bwt") == 0) {
+            bwt = true;
+            if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) bwt_path = argv[++i];
+        }
         else if (std::strcmp(argv[i], "--gpus") == 0 && i + 1 < argc) {
             if (!parse_count(argv[++i], gpus) || gpus < 1 || gpus > 64) { std::cerr << "--gpus: a device count, please\n"; return EXIT_FAILURE; }
         } else pos.push_back(argv[i]);
     }
     if (pos.size() < 2) {
         std::cerr << "Usage: caps_sa <input_path> <output_path> <(optional)-subproblem-count> "
-                     "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N>\n";
+                     "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH>\n";
         return EXIT_FAILURE;
     }
     size_t p = 0, ctx = 0;
     if (pos.size() >= 3 && !parse_count(pos[2], p)) { std::cerr << "subproblem-count: not a number: " << pos[2] << "\n"; return EXIT_FAILURE; }
     if (pos.size() >= 4 && !parse_count(pos[3], ctx)) { std::cerr << "bounded-context: not a number: " << pos[3] << "\n"; return EXIT_FAILURE; }
+    // --bwt: refused before any file is opened (the input's size comes from stat())
+    if (bwt) {
+        if (bwt_path.empty()) { std::cerr << "--bwt: missing output path (--bwt PATH)\n"; return EXIT_FAILURE; }
+        if (gpus > 1) { std::cerr << "--bwt: the BWT is built on one GPU; --gpus " << gpus << " has no BWT output\n"; return EXIT_FAILURE; }
+        struct stat sb;                                       // (an input that cannot be stat'ed is reported by read_input below)
+        if (ctx != 0 && stat(pos[0].c_str(), &sb) == 0 && ctx < static_cast<size_t>(sb.st_size)) {
+            std::cerr << "--bwt: a bounded-context order (bounded-context " << ctx << ") is not a suffix array and has no BWT\n";
+            return EXIT_FAILURE;
+        }
+    }
 
     std::string text;
     if (!read_input(pos[0], text)) return EXIT_FAILURE;
@@ -119,8 +151,8 @@ int main(int argc, char* argv[])
 
     std::cerr << "Text length: " << text.size() << ".\n";
     try {
-        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices);
-        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices);
+        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path);
+        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path);
     } catch (const std::exception& e) {
         std::cerr << e.what() << "\n";
         return EXIT_FAILURE;

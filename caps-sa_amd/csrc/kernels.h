@@ -4748,4 +4748,91 @@ GLOBAL_FN LAUNCH_BOUNDS(256) lcp_narrow_kernel(KCTX const uint32_t* __restrict__
     }
 }
 
+// ---- Burrows-Wheeler transform of a slice of the suffix array (capi_impl.h bwt_device, HostCopySink) ---------------------------
+// out[k] = T[(SA[k] + n - 1) mod n] for k < cnt, SA pointing at rank `first`; the one thread that meets SA[k] == 0 stores first + k
+// to *primary (a plain store: no other thread writes it; the caller set it to UINT64_MAX).  A pure gather, bound by the number of
+// text loads in flight (the text is 3 GB at C3, far beyond the caches): every lane takes BWT_PER consecutive entries, reads them as
+// one run of the SA (vector loads), issues all BWT_PER text loads before it uses any, and writes the bytes packed into words.
+constexpr uint32_t BWT_PER = 16;               // entries per lane: 64 (u32) / 128 (u64) bytes of SA in, one 16-byte store out
+// out + i0 has any alignment (a slice starts at any rank; a caller's pointer may be odd): the packed words are written through a
+// type of alignment 1, which is defined for any address.  gfx950 still gets one global_store_dwordx4 per lane from it: global memory
+// runs in the unaligned access mode under ROCm (the same holds for the LCP bytes of lcp_narrow_kernel at any slice base).
+typedef uint32_t u32_any_align __attribute__((aligned(1)));
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(256) bwt_kernel(KCTX const uint8_t* __restrict__ T, uint64_t n, const idx_t* __restrict__ SA, uint64_t first,
+                                        uint64_t cnt, uint8_t* __restrict__ out, uint64_t* __restrict__ primary)
+{
+    const uint64_t per_round = (uint64_t)K_BLOCK_DIM * BWT_PER, stride = (uint64_t)K_GRID_DIM * per_round;
+    for (uint64_t r0 = (uint64_t)K_BLOCK_IDX * per_round; r0 < cnt; r0 += stride) {              // block-uniform
+        PAR(tid) {
+            const uint64_t i0 = r0 + (uint64_t)tid * BWT_PER;
+            if (i0 + BWT_PER <= cnt) {
+                uint64_t s[BWT_PER];
+                uint32_t c[BWT_PER];
+                UNROLL
+                for (uint32_t k = 0; k < BWT_PER; ++k) s[k] = (uint64_t)STREAM_LOAD(&SA[i0 + k]);
+                UNROLL
+                for (uint32_t k = 0; k < BWT_PER; ++k) c[k] = T[s[k] ? s[k] - 1 : n - 1];     // all loads before any use
+                UNROLL
+                for (uint32_t k = 0; k < BWT_PER; ++k)
+                    if (s[k] == 0) *primary = first + i0 + k;
+                UNROLL
+                for (uint32_t w = 0; w < BWT_PER / 4; ++w)
+                    STREAM_STORE(reinterpret_cast<u32_any_align*>(out + i0) + w,
+                                 c[4 * w] | (c[4 * w + 1] << 8) | (c[4 * w + 2] << 16) | (c[4 * w + 3] << 24));
+            } else {
+                for (uint64_t i = i0; i < cnt; ++i) {                                          // the ragged end of the slice
+                    const uint64_t s = (uint64_t)SA[i];
+                    out[i] = T[s ? s - 1 : n - 1];
+                    if (s == 0) *primary = first + i;
+                }
+            }
+        }
+    }
+}
+
+// The same gather from the build's PACKED text (BITS-bit codes, most significant first in 32-bit words: 750 MB at C3 against the raw
+// text's 3 GB) through a code -> byte table: code2byte holds the 4 bytes of a 2-bit alphabet (byte k = the letter of code k); 8-bit
+// codes are the byte ^ 0x80 (pipeline.h build_lut).  What the host path's slices use (HostCopySink): measured at C3 on that path,
+// build_bwt() - build() = +110 ms with it against +114 ms from the raw text (docs/HISTORY.md); bwt_device has only the raw text.
+template <typename idx_t, int BITS>
+GLOBAL_FN LAUNCH_BOUNDS(256) bwt_packed_kernel(KCTX const uint32_t* __restrict__ P, uint64_t n, const idx_t* __restrict__ SA, uint64_t first,
+                                               uint64_t cnt, uint8_t* __restrict__ out, uint64_t* __restrict__ primary, uint32_t code2byte)
+{
+    constexpr uint32_t CPW = 32 / BITS;
+    const uint64_t per_round = (uint64_t)K_BLOCK_DIM * BWT_PER, stride = (uint64_t)K_GRID_DIM * per_round;
+    auto byte_of = [&](uint64_t pos, uint32_t word) -> uint32_t {
+        const uint32_t code = (word >> (32u - BITS - (uint32_t)(pos % CPW) * BITS)) & ((1u << BITS) - 1u);
+        return BITS == 2 ? (code2byte >> (8u * code)) & 0xFFu : code ^ 0x80u;
+    };
+    for (uint64_t r0 = (uint64_t)K_BLOCK_IDX * per_round; r0 < cnt; r0 += stride) {
+        PAR(tid) {
+            const uint64_t i0 = r0 + (uint64_t)tid * BWT_PER;
+            if (i0 + BWT_PER <= cnt) {
+                uint64_t s[BWT_PER];
+                uint32_t c[BWT_PER];
+                UNROLL
+                for (uint32_t k = 0; k < BWT_PER; ++k) { const uint64_t v = (uint64_t)STREAM_LOAD(&SA[i0 + k]); s[k] = v ? v - 1 : n - 1; }
+                UNROLL
+                for (uint32_t k = 0; k < BWT_PER; ++k) c[k] = P[s[k] / CPW];
+                UNROLL
+                for (uint32_t k = 0; k < BWT_PER; ++k) {
+                    c[k] = byte_of(s[k], c[k]);
+                    if (s[k] == n - 1) *primary = first + i0 + k;        // (only SA == 0 maps to n - 1)
+                }
+                UNROLL
+                for (uint32_t w = 0; w < BWT_PER / 4; ++w)
+                    STREAM_STORE(reinterpret_cast<u32_any_align*>(out + i0) + w,
+                                 c[4 * w] | (c[4 * w + 1] << 8) | (c[4 * w + 2] << 16) | (c[4 * w + 3] << 24));
+            } else {
+                for (uint64_t i = i0; i < cnt; ++i) {
+                    const uint64_t v = (uint64_t)SA[i], q = v ? v - 1 : n - 1;
+                    out[i] = (uint8_t)byte_of(q, P[q / CPW]);
+                    if (v == 0) *primary = first + i;
+                }
+            }
+        }
+    }
+}
+
 }  // namespace caps

@@ -1320,6 +1320,8 @@ struct WaveSink {
     // the build starts over (a slot overflowed under 32-bit keys, the deferred ties did not fit): what was handed over so far is
     // void -- the sink finishes reading the arrays the new attempt is about to rewrite and forgets it
     virtual void reset(Backend& be) = 0;
+    // the packed text of the build and its byte -> code table (device), before the build starts (HostCopySink: the BWT's source)
+    virtual void text(const uint32_t* P, const uint8_t* lut) {}
     virtual ~WaveSink() {}
 };
 

@@ -220,6 +220,37 @@ int caps_sa_hip_verify_slice_device_u32(const void* dT, uint64_t n, const void* 
 int caps_sa_hip_verify_slice_device_u64(const void* dT, uint64_t n, const void* dSA, const void* dLCP, uint64_t cnt,
                                         int is_head, void* hip_stream, uint64_t* n_errors);
 
+/* ---- Burrows-Wheeler transform, a third result beside SA and LCP ----------------------
+ *
+ * Let SA be the suffix array the library already builds, in the reference's order. That order includes signed-char bytes and
+ * puts a proper prefix before the longer suffix, so it is the order of T·$ with $ below every byte. Then:
+ *
+ *   BWT[k] = T[(SA[k] + n - 1) mod n] for k in [0, n): n bytes, the text's own bytes as given to the build;
+ *   primary = the k with SA[k] == 0.
+ *
+ * This is the BWT of T·$ with the $ row taken out: L = BWT[primary], BWT[0 .. primary), '$', BWT[primary + 1 .. n) is the last
+ * column of the n + 1 sorted rotations of T·$. Nothing else is needed to invert it.
+ *
+ * For a slice of the SA that does not hold the entry equal to 0, primary comes back as UINT64_MAX (n = 0 included).
+ * A bounded-context order (0 < max_context < n) is not a suffix array and has no BWT: CAPS_SA_EUNSUPPORTED.
+ */
+
+/* BWT of a slice of a suffix array already in HBM: dBWT[k] = dT[(dSA[k] + n - 1) mod n], k < cnt, where dSA points at rank
+ * `first`; *primary = first + k for the k with dSA[k] == 0, else UINT64_MAX.  dT (n bytes), dSA (cnt entries) and dBWT (cnt
+ * bytes) are device pointers on the current device; hip_stream as in caps_sa_hip_build_device_*.  first + cnt > n or a null
+ * pointer: CAPS_SA_EINVAL.  Returns after the stream work has completed. */
+int caps_sa_hip_bwt_device_u32(const void* dT, uint64_t n, const void* dSA, uint64_t first, uint64_t cnt,
+                               void* dBWT, void* hip_stream, uint64_t* primary);
+int caps_sa_hip_bwt_device_u64(const void* dT, uint64_t n, const void* dSA, uint64_t first, uint64_t cnt,
+                               void* dBWT, void* hip_stream, uint64_t* primary);
+/* construct() plus the BWT, host buffers: caps_sa_hip_build_* with BWT (n bytes, caller-owned) and *primary.  The BWT leaves the
+ * device slice by slice with SA and LCP (stats->result_waves slices; page-locked BWT memory copies at the link rate).  One
+ * device only: the sharded builds (caps_sa_hip_build_multi_*) have no BWT output. */
+int caps_sa_hip_build_bwt_u32(const char* T, uint64_t n, uint64_t subproblem_count, uint64_t max_context,
+                              uint32_t* SA, uint32_t* LCP, uint8_t* BWT, uint64_t* primary, int device, caps_sa_stats* stats);
+int caps_sa_hip_build_bwt_u64(const char* T, uint64_t n, uint64_t subproblem_count, uint64_t max_context,
+                              uint64_t* SA, uint64_t* LCP, uint8_t* BWT, uint64_t* primary, int device, caps_sa_stats* stats);
+
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
 /* merge_sort (src/Suffix_Array.cpp:112-129) of an arbitrary list of cnt distinct suffix
