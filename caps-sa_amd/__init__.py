@@ -44,6 +44,13 @@ def lib() -> CapsLib:
     return _lib
 
 
+def inverse_bwt(BWT, primary: int, device: int = 0) -> np.ndarray:
+    """The text back from its Burrows-Wheeler transform (include/caps_sa_hip.h caps_sa_hip_inverse_bwt_*): the inverse of
+    ``SuffixArray(T, bwt=True)``'s ``BWT()`` and ``primary()`` -> np.uint8 array.  The index width follows n.  An input that is
+    not the BWT of any text raises CapsSaError (code -1)."""
+    return lib().inverse_bwt(BWT, primary, device=device)
+
+
 class SuffixArray:
     """Python mirror of ``CaPS_SA::Suffix_Array<T_idx_>`` (include/Suffix_Array.hpp:22-181).
 

@@ -120,11 +120,12 @@ SHARD_EXPORTS = ["shard_create", "shard_destroy", "shard_info", "shard_phase1", 
                  "shard_phase2", "shard_last_sa", "shard_fix_first_lcp", "shard_scatter", "shard_plan", "shard_sort",
                  "shard_phase1_arrays", "shard_set_key_bits"]
 
-EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_bytes", "workspace_bytes", "workspace_bytes_ex", "release_cache", "host_alloc", "host_free", "gen_rand_seq"] + SHARD_EXPORTS + [
+EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_bytes", "workspace_bytes", "workspace_bytes_ex", "release_cache", "host_alloc", "host_free", "gen_rand_seq",
+           "inverse_bwt_workspace_bytes"] + SHARD_EXPORTS + [
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
     for name in ("build", "build_multi", "build_device", "verify_device", "verify_slice_device", "sort_suffixes", "sort_segments", "merge",
-                 "upper_bound", "lcp", "build_bwt", "bwt_device")
+                 "upper_bound", "lcp", "build_bwt", "bwt_device", "inverse_bwt", "inverse_bwt_device")
 ]
 
 
@@ -168,6 +169,8 @@ class CapsLib:
         f("host_free").argtypes = [_vp]
         f("gen_rand_seq").restype = _ci
         f("gen_rand_seq").argtypes = [ctypes.c_uint32, _u64, _vp]
+        f("inverse_bwt_workspace_bytes").restype = _ci
+        f("inverse_bwt_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
         for sfx in ("u32", "u64"):
             f(f"build_{sfx}").restype = _ci
             f(f"build_{sfx}").argtypes = [_vp, _u64, _u64, _u64, _vp, _vp, _ci, ctypes.POINTER(Stats)]
@@ -179,6 +182,10 @@ class CapsLib:
             f(f"build_bwt_{sfx}").argtypes = [_vp, _u64, _u64, _u64, _vp, _vp, _vp, ctypes.POINTER(_u64), _ci, ctypes.POINTER(Stats)]
             f(f"bwt_device_{sfx}").restype = _ci
             f(f"bwt_device_{sfx}").argtypes = [_vp, _u64, _vp, _u64, _u64, _vp, _vp, ctypes.POINTER(_u64)]
+            f(f"inverse_bwt_{sfx}").restype = _ci
+            f(f"inverse_bwt_{sfx}").argtypes = [_vp, _u64, _u64, _vp, _ci]
+            f(f"inverse_bwt_device_{sfx}").restype = _ci
+            f(f"inverse_bwt_device_{sfx}").argtypes = [_vp, _u64, _u64, _vp, _vp, _u64, _vp]
             f(f"verify_device_{sfx}").restype = _ci
             f(f"verify_device_{sfx}").argtypes = [_vp, _u64, _vp, _vp, _vp, ctypes.POINTER(_u64)]
             f(f"verify_slice_device_{sfx}").restype = _ci
@@ -357,6 +364,29 @@ class CapsLib:
         self._check(self._f(f"bwt_device_{sfx}")(dT_ptr or None, n, dSA_ptr or None, first, cnt, dBWT_ptr or None, stream or None,
                                                  ctypes.byref(primary)))
         return primary.value
+
+    def inverse_bwt(self, BWT, primary: int, idx_bits: int | None = None, device: int = 0) -> np.ndarray:
+        """T back from (BWT, primary) (include/caps_sa_hip.h caps_sa_hip_inverse_bwt_*) -> np.uint8 array of n bytes.  The index
+        width follows n unless idx_bits is given.  Not the BWT of any text: CapsSaError with code -1."""
+        B = self._text(BWT)
+        n = int(B.size)
+        sfx, _ = _sfx(idx_bits or (32 if n <= 0xFFFFFFFF else 64))
+        T = np.empty(n, dtype=np.uint8)
+        self._check(self._f(f"inverse_bwt_{sfx}")(B.ctypes.data if n else None, n, int(primary), T.ctypes.data if n else None, device))
+        return T
+
+    def inverse_bwt_workspace_bytes(self, n: int, idx_bits: int = 32) -> int:
+        out = _u64(0)
+        self._check(self._f("inverse_bwt_workspace_bytes")(n, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    def inverse_bwt_device(self, dBWT_ptr: int, n: int, primary: int, dT_ptr: int, dWS_ptr: int, ws_bytes: int, idx_bits: int = 32,
+                           stream: int = 0) -> None:
+        """T back from (BWT, primary) in device memory: dBWT_ptr (n bytes) -> dT_ptr (n bytes), workspace dWS_ptr of ws_bytes
+        (inverse_bwt_workspace_bytes)."""
+        sfx, _ = _sfx(idx_bits)
+        self._check(self._f(f"inverse_bwt_device_{sfx}")(dBWT_ptr or None, n, int(primary), dT_ptr or None, dWS_ptr or None, ws_bytes,
+                                                         stream or None))
 
     # ------------------------------------------------------------------ kernel-level entry points
     def sort_suffixes(self, T, idx, idx_bits: int = 32, device: int = 0):

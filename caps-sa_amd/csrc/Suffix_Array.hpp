@@ -18,6 +18,7 @@
 //  * an optional list of devices: construct() then shards the build over them (caps_sa_hip_build_multi_*);
 //  * construct_bwt() (not in the reference): construct() plus the Burrows-Wheeler transform (include/caps_sa_hip.h), one device;
 //    its n-byte buffer is allocated by the first construct_bwt(), so construct() callers pay nothing for it.
+//  * the free function inverse_bwt() (not in the reference): the text back from (BWT, primary).
 #ifndef CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 #define CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 
@@ -152,6 +153,18 @@ private:
     const std::vector<int> devices_;
     caps_sa_stats stats_;
 };
+
+// The text back from its BWT (include/caps_sa_hip.h caps_sa_hip_inverse_bwt_*; not in the reference): BWT and primary as
+// construct_bwt() returns them, T receives n bytes.  32-bit indices for n <= UINT32_MAX, else 64-bit; throws std::runtime_error
+// on any error, an input that is not the BWT of a text included.
+inline void inverse_bwt(const uint8_t* BWT, uint64_t n, uint64_t primary, char* T, int device = 0)
+{
+    const int rc = n <= UINT32_MAX ? caps_sa_hip_inverse_bwt_u32(BWT, n, primary, T, device)
+                                   : caps_sa_hip_inverse_bwt_u64(BWT, n, primary, T, device);
+    if (rc != CAPS_SA_OK)
+        throw std::runtime_error(std::string(n <= UINT32_MAX ? "caps_sa_hip_inverse_bwt_u32: " : "caps_sa_hip_inverse_bwt_u64: ") +
+                                 caps_sa_hip_last_error());
+}
 
 }  // namespace CaPS_SA
 

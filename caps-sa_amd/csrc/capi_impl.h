@@ -989,6 +989,158 @@ int bwt_device(const void* dT, uint64_t n, const void* dSA, uint64_t first, uint
     });
 }
 
+// ---- inverse BWT (include/caps_sa_hip.h caps_sa_hip_inverse_bwt_*; kernels.h ibwt_*) ----------------------------------------------
+// The workspace: the LF table ((n + 1) entries), the per-tile key counts, C and the range table, then per level of the splitter
+// lists succ / len / off (level 0: one node per IBWT_S0 rows; level k + 1: one per IBWT_S1 nodes of level k, until a level has at
+// most IBWT_TOP nodes), and the result words of the top walk.
+struct InvPlan {
+    uint64_t n_tiles = 0;
+    uint32_t levels = 0;
+    uint64_t M[16] = {};
+    size_t off_cnt = 0, off_total = 0, off_C = 0, off_sym = 0, off_res = 0;
+    size_t off_succ[16] = {}, off_len[16] = {}, off_off[16] = {};
+    size_t bytes = 0;
+};
+template <typename idx_t> InvPlan inv_plan(uint64_t n)
+{
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    InvPlan p;
+    p.n_tiles = (n + 1 + IBWT_TILE - 1) / IBWT_TILE;
+    size_t o = up((n + 1) * sizeof(idx_t));
+    p.off_cnt = o;   o += up(p.n_tiles * IBWT_KEYS * sizeof(idx_t));
+    p.off_total = o; o += up(IBWT_KEYS * sizeof(uint64_t));
+    p.off_C = o;     o += up((IBWT_KEYS + 1) * sizeof(uint64_t));
+    p.off_sym = o;   o += up((IBWT_KEYS + 1) * sizeof(uint64_t));
+    p.off_res = o;   o += 256;
+    uint64_t m = n / IBWT_S0 + 1;
+    for (;;) {
+        p.M[p.levels] = m;
+        p.off_succ[p.levels] = o; o += up(m * sizeof(idx_t));
+        p.off_len[p.levels] = o;  o += up(m * sizeof(uint64_t));
+        p.off_off[p.levels] = o;  o += up(m * sizeof(uint64_t));
+        ++p.levels;
+        if (m <= IBWT_TOP) break;
+        m = (m - 1) / IBWT_S1 + 1;
+    }
+    p.bytes = o + 256;                               // (room to align the caller's base)
+    return p;
+}
+
+inline int inverse_bwt_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
+{
+    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    *bytes = idx_bytes == 4 ? inv_plan<uint32_t>(n).bytes : inv_plan<uint64_t>(n).bytes;
+    return CAPS_SA_OK;
+}
+
+// the kernels on be's stream; the single-cycle check is read back (synchronises): false = not the BWT of any text
+template <typename idx_t>
+bool run_inverse_bwt(Backend& be, const uint8_t* dB, uint64_t n, uint64_t primary, uint8_t* dT, char* base, const InvPlan& p)
+{
+    idx_t* LF = reinterpret_cast<idx_t*>(base);
+    idx_t* cnt = reinterpret_cast<idx_t*>(base + p.off_cnt);
+    uint64_t* total = reinterpret_cast<uint64_t*>(base + p.off_total);
+    uint64_t* C = reinterpret_cast<uint64_t*>(base + p.off_C);
+    uint64_t* sym = reinterpret_cast<uint64_t*>(base + p.off_sym);
+    uint64_t* res = reinterpret_cast<uint64_t*>(base + p.off_res);
+    auto succ = [&](uint32_t k) { return reinterpret_cast<idx_t*>(base + p.off_succ[k]); };
+    auto len = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.off_len[k]); };
+    auto off = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.off_off[k]); };
+    auto walk_grid = [](uint64_t walks) { return capped_grid(std::min<uint64_t>((walks + IBWT_Q - 1) / IBWT_Q, 8192), IBWT_NT); };
+    const uint32_t tg = capped_grid(std::min<uint64_t>(p.n_tiles, 8192), IBWT_NT);
+    CAPS_LAUNCH((ibwt_count_kernel<idx_t>), tg, IBWT_NT, be, dB, n, primary, p.n_tiles, cnt);
+    CAPS_LAUNCH((ibwt_scan_kernel<idx_t>), IBWT_KEYS, IBWT_NT, be, cnt, p.n_tiles, total);
+    CAPS_LAUNCH(ibwt_c_kernel, 1, 64, be, total, C, sym);
+    CAPS_LAUNCH((ibwt_lf_kernel<idx_t>), tg, IBWT_NT, be, dB, n, primary, p.n_tiles, cnt, C, LF);
+    const uint32_t top = p.levels - 1;
+    CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_LINK0>), walk_grid(p.M[0]), IBWT_NT, be, LF, n, p.M[0], (uint64_t)0,
+                (const idx_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr, succ(0), len(0), (const uint64_t*)nullptr,
+                (const uint64_t*)nullptr, (uint8_t*)nullptr);
+    for (uint32_t k = 1; k <= top; ++k)
+        CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_LINK>), walk_grid(p.M[k]), IBWT_NT, be, LF, n, p.M[k], p.M[k - 1],
+                    (const idx_t*)succ(k - 1), (const uint64_t*)len(k - 1), (uint64_t*)nullptr, succ(k), len(k),
+                    (const uint64_t*)nullptr, (const uint64_t*)nullptr, (uint8_t*)nullptr);
+    CAPS_LAUNCH((ibwt_top_kernel<idx_t>), 1, IBWT_NT, be, (const idx_t*)succ(top), (const uint64_t*)len(top), p.M[top], n, off(top), res);
+    uint64_t h[3] = {0, 0, 0};
+    be.d2h(h, res, sizeof h);
+    be.sync();
+    if (h[0] != 1) return false;
+    for (uint32_t k = top; k >= 1; --k)
+        CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_PROP>), walk_grid(p.M[k]), IBWT_NT, be, LF, n, p.M[k], p.M[k - 1],
+                    (const idx_t*)succ(k - 1), (const uint64_t*)len(k - 1), off(k - 1), (idx_t*)nullptr, (uint64_t*)nullptr,
+                    (const uint64_t*)off(k), (const uint64_t*)nullptr, (uint8_t*)nullptr);
+    CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_WRITE>), walk_grid(p.M[0]), IBWT_NT, be, LF, n, p.M[0], (uint64_t)0,
+                (const idx_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr, (idx_t*)nullptr, len(0),
+                (const uint64_t*)off(0), (const uint64_t*)sym, dT);
+    be.sync();
+    return true;
+}
+
+inline const char* not_a_bwt_msg() { return "(BWT, primary) is not the BWT of any text: its LF mapping is not one cycle of n + 1 rows"; }
+
+template <typename idx_t> int check_inverse(const void* B, uint64_t n, uint64_t primary, const void* T)
+{
+    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
+    if (!B || !T) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (primary >= n) return fail(CAPS_SA_EINVAL, "primary >= n");
+    return CAPS_SA_OK;
+}
+
+// T back from (BWT, primary), device buffers (include/caps_sa_hip.h caps_sa_hip_inverse_bwt_device_*)
+template <typename idx_t>
+int inverse_bwt_device(const void* dB, uint64_t n, uint64_t primary, void* dT, void* workspace, uint64_t workspace_bytes, void* stream)
+{
+    if (n == 0) return CAPS_SA_OK;
+    if (int rc = check_inverse<idx_t>(dB, n, primary, dT)) return rc;
+    if (!workspace) return fail(CAPS_SA_EINVAL, "null workspace");
+    const InvPlan p = inv_plan<idx_t>(n);
+    if (workspace_bytes < p.bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_inverse_bwt_workspace_bytes)");
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+        if (!run_inverse_bwt<idx_t>(be, static_cast<const uint8_t*>(dB), n, primary, static_cast<uint8_t*>(dT), base, p))
+            return fail(CAPS_SA_EINVAL, not_a_bwt_msg());
+        return CAPS_SA_OK;
+    });
+}
+
+// host buffers: the BWT up, the inverse on the host-path block (HostPathCache), T down
+template <typename idx_t>
+int inverse_bwt_host(const uint8_t* B, uint64_t n, uint64_t primary, char* T, int device)
+{
+    if (n == 0) return CAPS_SA_OK;
+    if (int rc = check_inverse<idx_t>(B, n, primary, T)) return rc;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const InvPlan p = inv_plan<idx_t>(n);
+        const size_t off_T = up(n), off_ws = off_T + up(n), total = off_ws + p.bytes;
+        if (hc.device != device || hc.bytes < total) {
+            std::vector<char*> keep;
+            keep.swap(hc.host_chunks);                       // (the staging chunks of the builds survive a larger device block)
+            const size_t keep_bytes = hc.host_chunk_bytes;
+            release_host_cache_locked(hc);
+            hc.host_chunks.swap(keep);
+            hc.host_chunk_bytes = keep_bytes;
+            hc.base = static_cast<char*>(be.alloc(total));
+            hc.bytes = total;
+            hc.device = device;
+        }
+        uint8_t* dB = reinterpret_cast<uint8_t*>(hc.base);
+        uint8_t* dT = reinterpret_cast<uint8_t*>(hc.base + off_T);
+        be.h2d(dB, B, n);
+        if (!run_inverse_bwt<idx_t>(be, dB, n, primary, dT, hc.base + off_ws, p)) return fail(CAPS_SA_EINVAL, not_a_bwt_msg());
+        be.d2h(T, dT, n);
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+
 // Text on the device for the kernel-level entry points.
 struct DevText {
     uint8_t* raw = nullptr;
@@ -1386,6 +1538,16 @@ int CAPS_API(workspace_bytes)(uint64_t n, uint64_t subproblem_count, int idx_byt
 
 CAPS_DEFINE_WIDTH(u32, uint32_t)
 CAPS_DEFINE_WIDTH(u64, uint64_t)
+
+int CAPS_API(inverse_bwt_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::inverse_bwt_workspace_bytes(n, idx_bytes, bytes); }
+#define CAPS_DEFINE_INVERSE(SFX, IDX)                                                                                      \
+    int CAPS_API(inverse_bwt_device_##SFX)(const void* dBWT, uint64_t n, uint64_t primary, void* dT, void* ws,             \
+                                           uint64_t ws_bytes, void* stream)                                                \
+    { return caps::inverse_bwt_device<IDX>(dBWT, n, primary, dT, ws, ws_bytes, stream); }                                  \
+    int CAPS_API(inverse_bwt_##SFX)(const uint8_t* BWT, uint64_t n, uint64_t primary, char* T, int device)                 \
+    { return caps::inverse_bwt_host<IDX>(BWT, n, primary, T, device); }
+CAPS_DEFINE_INVERSE(u32, uint32_t)
+CAPS_DEFINE_INVERSE(u64, uint64_t)
 
 
 struct caps_sa_shard { std::unique_ptr<caps::ShardBase> impl; };

@@ -2,7 +2,11 @@
 // (reference src/main.cpp:43-93):
 //
 //     caps_sa <input_path> <output_path> [subproblem-count] [bounded-context] [--pretty-print] [--gpus N] [--bwt PATH]
+//     caps_sa --inverse-bwt IN.bwt OUT
 //
+// * --inverse-bwt IN.bwt OUT (not in the reference): the text back from a file that --bwt wrote (u64 n, u64 primary, n bytes):
+//   its n bytes to OUT, written only after the inverse has succeeded.  An unreadable IN, a size other than 16 + n, primary >= n
+//   and any other argument are refused before OUT is opened;
 // * --gpus N (not in the reference): shard the build over HIP devices 0 .. N-1;
 // * --bwt PATH (not in the reference): also write the Burrows-Wheeler transform of the (remapped) text to PATH after the SA / LCP
 //   output: u64 n, u64 primary, n bytes, native endianness (include/caps_sa_hip.h has the definition).  One GPU, no bounded
@@ -95,8 +99,54 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
     return 0;
 }
 
+// caps_sa --inverse-bwt IN OUT: args = everything after the program name
+static int inverse_bwt_main(const std::vector<std::string>& args)
+{
+    if (args.size() != 3 || args[0] != "--inverse-bwt") {
+        std::cerr << "--inverse-bwt: usage: caps_sa --inverse-bwt IN.bwt OUT (no other option or argument)\n";
+        return EXIT_FAILURE;
+    }
+    const std::string& in_path = args[1];
+    const std::string& out_path = args[2];
+    std::string data;
+    {
+        std::ifstream in(in_path, std::ios::binary | std::ios::ate);
+        if (!in) { std::cerr << "--inverse-bwt: " << in_path << " : cannot open\n"; return EXIT_FAILURE; }
+        const std::streamsize size = in.tellg();
+        if (size < 0) { std::cerr << "--inverse-bwt: " << in_path << " : cannot read\n"; return EXIT_FAILURE; }
+        in.seekg(0);
+        data.resize(static_cast<size_t>(size));
+        if (size && !in.read(&data[0], size)) { std::cerr << "--inverse-bwt: " << in_path << " : cannot read\n"; return EXIT_FAILURE; }
+    }
+    if (data.size() < 16) {
+        std::cerr << "--inverse-bwt: " << in_path << " is " << data.size() << " bytes, shorter than its 16-byte header (u64 n, u64 primary)\n";
+        return EXIT_FAILURE;
+    }
+    uint64_t n = 0, primary = 0;
+    std::memcpy(&n, data.data(), 8);
+    std::memcpy(&primary, data.data() + 8, 8);
+    if (data.size() - 16 != n) {
+        std::cerr << "--inverse-bwt: " << in_path << " holds " << data.size() - 16 << " bytes after its header, its n says " << n << "\n";
+        return EXIT_FAILURE;
+    }
+    if (n && primary >= n) { std::cerr << "--inverse-bwt: primary " << primary << " >= n " << n << "\n"; return EXIT_FAILURE; }
+    std::string text(static_cast<size_t>(n), '\0');
+    try {
+        CaPS_SA::inverse_bwt(reinterpret_cast<const uint8_t*>(data.data() + 16), n, primary, n ? &text[0] : nullptr);
+    } catch (const std::exception& e) {
+        std::cerr << e.what() << "\n";
+        return EXIT_FAILURE;
+    }
+    std::ofstream out(out_path, std::ios::binary);
+    if (!out) { std::cerr << out_path << " : cannot open for writing\n"; return EXIT_FAILURE; }
+    out.write(text.data(), static_cast<std::streamsize>(n));
+    return out ? 0 : EXIT_FAILURE;
+}
+
 int main(int argc, char* argv[])
 {
+    for (int i = 1; i < argc; ++i)
+        if (std::strcmp(argv[i], "--inverse-bwt") == 0) return inverse_bwt_main(std::vector<std::string>(argv + 1, argv + argc));
     std::vector<std::string> pos;
     bool pretty = false, bwt = false;
     size_t gpus = 1;
@@ -113,7 +163,8 @@ int main(int argc, char* argv[])
     }
     if (pos.size() < 2) {
         std::cerr << "Usage: caps_sa <input_path> <output_path> <(optional)-subproblem-count> "
-                     "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH>\n";
+                     "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH>\n"
+                     "       caps_sa --inverse-bwt IN.bwt OUT\n";
         return EXIT_FAILURE;
     }
     size_t p = 0, ctx = 0;

@@ -4835,4 +4835,273 @@ GLOBAL_FN LAUNCH_BOUNDS(256) bwt_packed_kernel(KCTX const uint32_t* __restrict__
     }
 }
 
+// ---- inverse Burrows-Wheeler transform (capi_impl.h inverse_bwt_device) --------------------------------------------------------
+// Rows r = 0 .. n of the sorted rotations of T·$: L[0] = BWT[primary], L[r] = BWT[r - 1] for 1 <= r <= primary, L[primary + 1] = '$',
+// L[r] = BWT[r - 1] after that.  Symbols as keys: '$' = 0, a byte b = (b ^ 0x80) + 1 (signed-char order), IBWT_KEYS of them.
+// LF[r] = C[key(L[r])] + |{r' < r : L[r'] = L[r]}|, and T[n - 1 - t] = L[LF^t(0)] = F[LF^(t+1)(0)]: a step of the walk is ONE load
+// (F is the key whose row range [C[k], C[k + 1]) holds LF[r], no L is read).  The walk is cut at splitter rows (every IBWT_S0-th),
+// the list of splitters ranked by walks over it (every IBWT_S1-th node, level by level, until a list fits one workgroup), and every
+// segment walked again, writing its stretch of T from its offset.  Every loop is bounded by n + 1 steps (or by its list's length),
+// whatever the input: LF is a permutation by construction, so a walk from a splitter meets a splitter again.
+constexpr uint32_t IBWT_KEYS = 257;
+constexpr uint32_t IBWT_NT = 256;              // threads of every inverse-BWT kernel (the rank masks below have IBWT_NT bits)
+constexpr uint32_t IBWT_ROUNDS = 64;           // rows of a tile of the LF table: IBWT_NT * IBWT_ROUNDS
+constexpr uint64_t IBWT_TILE = (uint64_t)IBWT_NT * IBWT_ROUNDS;
+constexpr uint32_t IBWT_S0_LOG = 6, IBWT_S1_LOG = 6;                 // splitter spacing: rows of the LF walk, nodes of a list
+constexpr uint64_t IBWT_S0 = 1ull << IBWT_S0_LOG, IBWT_S1 = 1ull << IBWT_S1_LOG;
+constexpr uint32_t IBWT_TOP = 256;             // a list of at most this many nodes is ranked by one workgroup in LDS
+constexpr uint32_t IBWT_Q = 4096;              // walks per workgroup range (the lanes take them one by one from an LDS counter)
+
+HD uint32_t ibwt_key_of_row(const uint8_t* __restrict__ B, uint64_t r, uint64_t primary)
+{
+    if (r == primary + 1) return 0;
+    return (uint32_t)(B[r ? r - 1 : primary] ^ 0x80u) + 1u;
+}
+
+// per tile of IBWT_TILE rows: how many rows hold each key -> cnt[key * n_tiles + tile] (key-major, for the scan below)
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(IBWT_NT) ibwt_count_kernel(KCTX const uint8_t* __restrict__ B, uint64_t n, uint64_t primary, uint64_t n_tiles,
+                                                    idx_t* __restrict__ cnt)
+{
+    SHARED_ARRAY(uint32_t, h, IBWT_KEYS);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        PAR(tid) { for (uint32_t k = tid; k < IBWT_KEYS; k += IBWT_NT) h[k] = 0; }
+        SYNC();
+        PAR(tid) {
+            const uint64_t r0 = tile * IBWT_TILE;
+            for (uint32_t j = 0; j < IBWT_ROUNDS; ++j) {
+                const uint64_t r = r0 + (uint64_t)j * IBWT_NT + tid;
+                if (r <= n) FETCH_ADD_U32(&h[ibwt_key_of_row(B, r, primary)], 1u);
+            }
+        }
+        SYNC();
+        PAR(tid) { for (uint32_t k = tid; k < IBWT_KEYS; k += IBWT_NT) cnt[(uint64_t)k * n_tiles + tile] = (idx_t)h[k]; }
+        SYNC();
+    }
+}
+
+// one workgroup per key: cnt[key][tile] -> the exclusive prefix over the tiles, in place; total[key] = the key's rows
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(IBWT_NT) ibwt_scan_kernel(KCTX idx_t* __restrict__ cnt, uint64_t n_tiles, uint64_t* __restrict__ total)
+{
+    SHARED_ARRAY(uint64_t, part, IBWT_NT);
+    const uint64_t per = (n_tiles + IBWT_NT - 1) / IBWT_NT;
+    for (uint32_t key = K_BLOCK_IDX; key < IBWT_KEYS; key += K_GRID_DIM) {          // block-uniform
+        idx_t* col = cnt + (uint64_t)key * n_tiles;
+        PAR(tid) {
+            const uint64_t a = std::min<uint64_t>(n_tiles, tid * per), b = std::min<uint64_t>(n_tiles, a + per);
+            uint64_t s = 0;
+            for (uint64_t k = a; k < b; ++k) s += (uint64_t)col[k];
+            part[tid] = s;
+        }
+        SYNC();
+        PAR(tid) {
+            if (tid == 0) {
+                uint64_t s = 0;
+                for (uint32_t k = 0; k < IBWT_NT; ++k) { const uint64_t v = part[k]; part[k] = s; s += v; }
+                total[key] = s;
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            const uint64_t a = std::min<uint64_t>(n_tiles, tid * per), b = std::min<uint64_t>(n_tiles, a + per);
+            uint64_t s = part[tid];
+            for (uint64_t k = a; k < b; ++k) { const uint64_t v = (uint64_t)col[k]; col[k] = (idx_t)s; s += v; }
+        }
+        SYNC();
+    }
+}
+
+// one thread: C[key] (first row of the key in F, C[IBWT_KEYS] = n + 1) and the keys present, as the walk's range table:
+// sym[0] = their number, then sym[1 + i] = the first row of the i-th present key | its byte << 56 ('$' first, row 0)
+GLOBAL_FN LAUNCH_BOUNDS(64) ibwt_c_kernel(KCTX const uint64_t* __restrict__ total, uint64_t* __restrict__ C, uint64_t* __restrict__ sym)
+{
+    PAR(tid) {
+        if (tid == 0) {
+            uint64_t s = 0, m = 0;
+            for (uint32_t k = 0; k < IBWT_KEYS; ++k) {
+                C[k] = s;
+                if (total[k]) sym[1 + m++] = s | ((uint64_t)(k ? ((k - 1) ^ 0x80u) : 0u) << 56);
+                s += total[k];
+            }
+            C[IBWT_KEYS] = s;
+            sym[0] = m;
+        }
+    }
+}
+
+// LF[r] for the rows of every tile: C[key] + the key's rows in earlier tiles (pre) + its rows before r in this tile.  The tile goes
+// in rounds of IBWT_NT rows, one per thread; a thread's rank among the round's rows of its key is the number of lower bits in the
+// key's IBWT_NT-bit mask (set by LDS atomics), and the round's last row of a key carries the key's count on and clears its mask.
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(IBWT_NT) ibwt_lf_kernel(KCTX const uint8_t* __restrict__ B, uint64_t n, uint64_t primary, uint64_t n_tiles,
+                                                 const idx_t* __restrict__ pre, const uint64_t* __restrict__ C, idx_t* __restrict__ LF)
+{
+    constexpr uint32_t MW = IBWT_NT / 32;         // mask words per key
+    SHARED_ARRAY(uint32_t, mask, IBWT_KEYS * MW);
+    SHARED_ARRAY(uint64_t, base, IBWT_KEYS);
+    TL_DECL(uint32_t, st, 2);                     // the row's key (IBWT_KEYS: no row); the key's rows in the round if last, else 0
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        PAR(tid) {
+            for (uint32_t k = tid; k < IBWT_KEYS; k += IBWT_NT) base[k] = C[k] + (uint64_t)pre[(uint64_t)k * n_tiles + tile];
+            for (uint32_t w = tid; w < IBWT_KEYS * MW; w += IBWT_NT) mask[w] = 0;
+        }
+        SYNC();
+        for (uint32_t j = 0; j < IBWT_ROUNDS; ++j) {
+            const uint64_t r0 = tile * IBWT_TILE + (uint64_t)j * IBWT_NT;
+            if (r0 > n) break;                                                      // block-uniform
+            PAR(tid) {
+                const uint64_t r = r0 + tid;
+                const uint32_t key = r <= n ? ibwt_key_of_row(B, r, primary) : IBWT_KEYS;
+                TL(st, tid, 0) = key;
+                if (key < IBWT_KEYS) ATOMIC_OR_U32(&mask[key * MW + tid / 32], 1u << (tid % 32));
+            }
+            SYNC();
+            PAR(tid) {
+                const uint32_t key = TL(st, tid, 0);
+                TL(st, tid, 1) = 0;
+                if (key < IBWT_KEYS) {
+                    const uint32_t* mk = mask + key * MW;
+                    const uint32_t w = tid / 32, bit = tid % 32;
+                    uint32_t below = 0, above = 0;
+                    for (uint32_t i = 0; i < MW; ++i) {
+                        const uint32_t v = mk[i];
+                        if (i < w) below += (uint32_t)__builtin_popcount(v);
+                        else if (i > w) above += (uint32_t)__builtin_popcount(v);
+                        else {
+                            below += (uint32_t)__builtin_popcount(v & ((1u << bit) - 1u));
+                            above += (uint32_t)__builtin_popcount(v >> bit) - 1u;
+                        }
+                    }
+                    const uint64_t r = r0 + tid;
+                    LF[r] = (idx_t)(base[key] + below);
+                    if (above == 0) TL(st, tid, 1) = below + 1;
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                const uint32_t key = TL(st, tid, 0), c = TL(st, tid, 1);
+                if (key < IBWT_KEYS && c) {
+                    base[key] += c;
+                    for (uint32_t i = 0; i < MW; ++i) mask[key * MW + i] = 0;
+                }
+            }
+            SYNC();
+        }
+    }
+}
+
+// The walks, one kind per MODE, over ranges of IBWT_Q walks per workgroup (a lane takes the next walk of the range from an LDS
+// counter when its last one ends: walk lengths vary, roughly geometric on natural text).
+//   IBWT_LINK0  from splitter row j * S0 along LF to the next splitter: succ[j], len[j] (rows; len[j] <= n + 1)
+//   IBWT_LINK   the same over a list (lsucc, llen) of M nodes with splitters at every S1-th node: succ[J], len[J] = the summed weight
+//   IBWT_PROP   the offsets of a list's nodes from the offsets of its splitters: loff[node] = off[J] + the weight before it
+//   IBWT_WRITE  from splitter row j * S0 at offset off[j] for len[j] steps: T[n - 1 - t] = F[LF[row]] for t = off[j] .. (t < n)
+enum { IBWT_LINK0 = 0, IBWT_LINK = 1, IBWT_PROP = 2, IBWT_WRITE = 3 };
+template <typename idx_t, int MODE>
+GLOBAL_FN LAUNCH_BOUNDS(IBWT_NT) ibwt_walk_kernel(KCTX const idx_t* __restrict__ LF, uint64_t n, uint64_t walks, uint64_t M,
+                                                   const idx_t* __restrict__ lsucc, const uint64_t* __restrict__ llen, uint64_t* __restrict__ loff,
+                                                   idx_t* __restrict__ succ, uint64_t* __restrict__ len, const uint64_t* __restrict__ off,
+                                                   const uint64_t* __restrict__ sym, uint8_t* __restrict__ T)
+{
+    SHARED_ARRAY(uint32_t, q, 1);
+    SHARED_ARRAY(uint64_t, bnd, IBWT_KEYS);       // IBWT_WRITE: the first rows of the present keys (sym), and their bytes
+    SHARED_ARRAY(uint8_t, byt, IBWT_KEYS);
+    uint32_t nsym = 0;
+    if (MODE == IBWT_WRITE) {
+        PAR(tid) {
+            for (uint32_t k = tid; k < IBWT_KEYS; k += IBWT_NT) {
+                const uint64_t v = k < sym[0] ? sym[1 + k] : ~0ull;
+                bnd[k] = v & ((1ull << 56) - 1);
+                byt[k] = (uint8_t)(v >> 56);
+            }
+        }
+        SYNC();
+        nsym = (uint32_t)sym[0];
+    }
+    const uint64_t ranges = (walks + IBWT_Q - 1) / IBWT_Q;
+    const uint32_t salign = (uint32_t)((uintptr_t)T & 3u);
+    for (uint64_t rg = K_BLOCK_IDX; rg < ranges; rg += K_GRID_DIM) {               // block-uniform
+        PAR(tid) { if (tid == 0) q[0] = 0; }
+        SYNC();
+        PAR(tid) {
+            const uint64_t lo = rg * IBWT_Q, cnt = std::min<uint64_t>(IBWT_Q, walks - lo);
+            for (;;) {
+                const uint32_t i = FETCH_ADD_U32(&q[0], 1u);
+                if (i >= cnt) break;
+                const uint64_t j = lo + i;
+                if (MODE == IBWT_LINK0) {
+                    uint64_t cur = j << IBWT_S0_LOG, steps = 0;
+                    do { cur = (uint64_t)LF[cur]; ++steps; } while ((cur & (IBWT_S0 - 1)) != 0 && steps <= n);
+                    succ[j] = (idx_t)(cur >> IBWT_S0_LOG);
+                    len[j] = steps;
+                } else if (MODE == IBWT_LINK) {
+                    uint64_t cur = j << IBWT_S1_LOG, steps = 0, w = 0;
+                    do { w += llen[cur]; cur = (uint64_t)lsucc[cur]; ++steps; } while ((cur & (IBWT_S1 - 1)) != 0 && steps < M);
+                    succ[j] = (idx_t)(cur >> IBWT_S1_LOG);
+                    len[j] = w;
+                } else if (MODE == IBWT_PROP) {
+                    uint64_t cur = j << IBWT_S1_LOG, steps = 0, o = off[j];
+                    do { loff[cur] = o; o += llen[cur]; cur = (uint64_t)lsucc[cur]; ++steps; } while ((cur & (IBWT_S1 - 1)) != 0 && steps < M);
+                } else {
+                    // positions hi = n - 1 - off down to lo: a word store for a 4-byte word of T that lies inside them, byte stores at
+                    // the edges (a neighbouring segment owns the rest of an edge word)
+                    const uint64_t o = off[j], steps = std::min<uint64_t>(len[j], n + 1);
+                    if (o > n) continue;                                            // (never, after the single-cycle check)
+                    const int64_t hi = (int64_t)n - 1 - (int64_t)o, lo = std::max<int64_t>(0, hi - (int64_t)steps + 1);
+                    uint64_t cur = j << IBWT_S0_LOG;
+                    uint32_t word = 0;
+                    for (uint64_t k = 0; k < steps; ++k) {
+                        cur = (uint64_t)LF[cur];
+                        const int64_t p = hi - (int64_t)k;
+                        if (p < 0) break;                                           // the '$' step (t = n)
+                        uint32_t a = 0, m = nsym;                                   // the last present key whose first row <= cur
+                        while (m > 1) { const uint32_t h = m / 2; if (bnd[a + h] <= cur) { a += h; m -= h; } else m = h; }
+                        const uint32_t c = byt[a];
+                        const uint32_t qb = (uint32_t)((salign + (uint64_t)p) & 3u);
+                        const int64_t ws = p - (int64_t)qb;
+                        if (ws >= lo && ws + 3 <= hi) {
+                            word |= c << (8 * qb);
+                            if (qb == 0) { *reinterpret_cast<uint32_t*>(T + ws) = word; word = 0; }
+                        } else T[p] = (uint8_t)c;
+                    }
+                }
+            }
+        }
+        SYNC();
+    }
+}
+
+// The top list (M <= IBWT_TOP nodes) in LDS, walked by one thread from node 0: off[node] = the rows before it on the cycle of row 0.
+// res[0] = 1 when that cycle holds every row (it comes back to node 0 with n + 1 rows: LF is one cycle, the input a BWT), else 0;
+// res[1] = the rows counted, res[2] = the nodes visited.
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(IBWT_NT) ibwt_top_kernel(KCTX const idx_t* __restrict__ succ, const uint64_t* __restrict__ len, uint64_t M,
+                                                  uint64_t n, uint64_t* __restrict__ off, uint64_t* __restrict__ res)
+{
+    SHARED_ARRAY(uint32_t, s, IBWT_TOP);
+    SHARED_ARRAY(uint64_t, w, IBWT_TOP);
+    SHARED_ARRAY(uint64_t, o, IBWT_TOP);
+    PAR(tid) {
+        for (uint32_t k = tid; k < IBWT_TOP; k += IBWT_NT) {
+            s[k] = k < M ? (uint32_t)succ[k] : 0u;
+            w[k] = k < M ? len[k] : 0;
+            o[k] = 0;
+        }
+    }
+    SYNC();
+    PAR(tid) {
+        if (tid == 0) {
+            uint64_t acc = 0, steps = 0;
+            uint32_t cur = 0;
+            do { o[cur] = acc; acc += w[cur]; cur = s[cur]; ++steps; } while (cur != 0 && steps < M);
+            res[0] = cur == 0 && acc == n + 1 ? 1 : 0;
+            res[1] = acc;
+            res[2] = steps;
+        }
+    }
+    SYNC();
+    PAR(tid) { for (uint32_t k = tid; k < M; k += IBWT_NT) off[k] = o[k]; }
+}
+
 }  // namespace caps

@@ -251,6 +251,37 @@ int caps_sa_hip_build_bwt_u32(const char* T, uint64_t n, uint64_t subproblem_cou
 int caps_sa_hip_build_bwt_u64(const char* T, uint64_t n, uint64_t subproblem_count, uint64_t max_context,
                               uint64_t* SA, uint64_t* LCP, uint8_t* BWT, uint64_t* primary, int device, caps_sa_stats* stats);
 
+/* ---- inverse Burrows-Wheeler transform: the text back from (BWT, primary) --------------
+ *
+ * The inverse of the block above, over a whole suffix array's (BWT, primary): n bytes and primary < n. Take
+ * L = BWT[primary], BWT[0 .. primary), '$', BWT[primary + 1 .. n): rows 0 .. n, bytes in signed-char order, '$' below every
+ * byte. F is L sorted, C[c] the symbols of L below c, LF[r] = C[L[r]] + |{r' < r : L[r'] = L[r]}|. Then
+ *
+ *   T[n - 1 - t] = F[LF^(t+1)(0)] for t in [0, n).
+ *
+ * LF is a permutation of the n + 1 rows for any input; the input is the BWT of a text exactly when LF is ONE cycle. Any other
+ * input is refused with CAPS_SA_EINVAL and a message that says so (T is then unspecified): every input either inverts or gets
+ * this error, and every loop of the kernels is bounded by n + 1 steps whatever the input. n = 0: CAPS_SA_OK, nothing read or
+ * written (primary not looked at). n >= 1 with primary >= n, a null pointer, n > UINT32_MAX for _u32 (checked before any
+ * allocation), a workspace smaller than caps_sa_hip_inverse_bwt_workspace_bytes says: CAPS_SA_EINVAL.
+ *
+ * The index width sizes the LF table, (n + 1) x 4 bytes for _u32 and x 8 for _u64, plus O(n / 64) for the splitter lists.
+ */
+
+/* Workspace of caps_sa_hip_inverse_bwt_device_* for n symbols, idx_bytes = 4 (_u32) or 8 (_u64). */
+int caps_sa_hip_inverse_bwt_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes);
+/* dBWT (n bytes), dT (n bytes, written) and workspace are device pointers on the current device; the work runs on hip_stream
+ * (as in caps_sa_hip_build_device_*). Returns after the stream work has completed: the single-cycle check is read back. */
+int caps_sa_hip_inverse_bwt_device_u32(const void* dBWT, uint64_t n, uint64_t primary, void* dT,
+                                       void* workspace, uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_inverse_bwt_device_u64(const void* dBWT, uint64_t n, uint64_t primary, void* dT,
+                                       void* workspace, uint64_t workspace_bytes, void* hip_stream);
+/* Host buffers (any host memory; page-locked T copies at the link rate): uploads the BWT, inverts it on `device` and downloads T.
+ * Runs on the device block of the host-buffer builds (freed by caps_sa_hip_release_cache(); calls are serialised on it) and
+ * restores the caller's current device. */
+int caps_sa_hip_inverse_bwt_u32(const uint8_t* BWT, uint64_t n, uint64_t primary, char* T, int device);
+int caps_sa_hip_inverse_bwt_u64(const uint8_t* BWT, uint64_t n, uint64_t primary, char* T, int device);
+
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
 /* merge_sort (src/Suffix_Array.cpp:112-129) of an arbitrary list of cnt distinct suffix
