@@ -126,3 +126,65 @@ class SuffixArray:
             f.write(np.uint64(self._n).tobytes())
             f.write(self.SA().tobytes())
             f.write(self.LCP().tobytes())
+
+
+class FMIndex:
+    """FM-index over (BWT, primary) (include/caps_sa_hip.h "FM-index"): batched ``count`` and ``locate`` on the GPU for texts of at
+    most 4 distinct bytes.  The index is one blob (``blob``, np.uint8; ``nbytes``); ``save`` / ``load`` write and read exactly it."""
+
+    def __init__(self, blob: np.ndarray, device: int = 0, _lib: CapsLib | None = None):
+        self.blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        self._device = device
+        self._lib = _lib
+        if self.blob.size < 256 or bytes(self.blob[:8]) != b"CAPSFMI1":
+            raise ValueError("not an FM-index blob")
+        hdr = self.blob[:256].view(np.uint64)
+        self._n, self._sample = int(hdr[2]), int(hdr[12])
+
+    def _l(self) -> CapsLib:
+        return self._lib or lib()
+
+    @classmethod
+    def from_bwt(cls, BWT, primary: int, SA=None, sa_sample: int = 32, idx_bits: int | None = None, device: int = 0,
+                 _lib: CapsLib | None = None) -> "FMIndex":
+        """SA = None: an index that counts; with the suffix array it also locates (every sa_sample-th text position is kept)."""
+        return cls((_lib or lib()).fm_build(BWT, primary, SA, sa_sample, idx_bits, device), device, _lib)
+
+    @classmethod
+    def from_suffix_array(cls, sa_obj: "SuffixArray", sa_sample: int = 32) -> "FMIndex":
+        """From a constructed ``SuffixArray(..., bwt=True)``."""
+        return cls.from_bwt(sa_obj.BWT(), sa_obj.primary(), sa_obj.SA(), sa_sample, sa_obj._bits, sa_obj._device)
+
+    @property
+    def n(self) -> int:
+        return self._n
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.blob.size)
+
+    @property
+    def sa_sample(self) -> int:
+        """0: built without an SA (count only)."""
+        return self._sample
+
+    def count(self, patterns):
+        """(first, count), np.uint64 arrays: pattern j occurs at SA[first[j] : first[j] + count[j]] (count 0: first 0)."""
+        return self._l().fm_count(self.blob, patterns, self._device)
+
+    def locate(self, patterns, max_hits: int | None = None) -> list:
+        """Per pattern its text positions in SA order (np.uint64), at most max_hits of them."""
+        first, count = self.count(patterns)
+        take = count if max_hits is None else np.minimum(count, np.uint64(max_hits))
+        off = np.zeros(take.size + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(take, dtype=np.uint64)
+        pos, _ = self._l().fm_locate(self.blob, first, count, off, self._device)
+        return [pos[int(off[j]):int(off[j + 1])] for j in range(take.size)]
+
+    def save(self, path: str) -> None:
+        with open(path, "wb") as f:
+            f.write(self.blob.tobytes())
+
+    @classmethod
+    def load(cls, path: str, device: int = 0, _lib: CapsLib | None = None) -> "FMIndex":
+        return cls(np.fromfile(path, dtype=np.uint8), device, _lib)

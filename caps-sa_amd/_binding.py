@@ -121,11 +121,11 @@ SHARD_EXPORTS = ["shard_create", "shard_destroy", "shard_info", "shard_phase1", 
                  "shard_phase1_arrays", "shard_set_key_bits"]
 
 EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_bytes", "workspace_bytes", "workspace_bytes_ex", "release_cache", "host_alloc", "host_free", "gen_rand_seq",
-           "inverse_bwt_workspace_bytes"] + SHARD_EXPORTS + [
+           "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device"] + SHARD_EXPORTS + [
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
     for name in ("build", "build_multi", "build_device", "verify_device", "verify_slice_device", "sort_suffixes", "sort_segments", "merge",
-                 "upper_bound", "lcp", "build_bwt", "bwt_device", "inverse_bwt", "inverse_bwt_device")
+                 "upper_bound", "lcp", "build_bwt", "bwt_device", "inverse_bwt", "inverse_bwt_device", "fm_build", "fm_build_device")
 ]
 
 
@@ -171,7 +171,21 @@ class CapsLib:
         f("gen_rand_seq").argtypes = [ctypes.c_uint32, _u64, _vp]
         f("inverse_bwt_workspace_bytes").restype = _ci
         f("inverse_bwt_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
+        f("fm_index_bytes").restype = _ci
+        f("fm_index_bytes").argtypes = [_u64, ctypes.c_uint32, _ci, ctypes.POINTER(_u64)]
+        f("fm_count").restype = _ci
+        f("fm_count").argtypes = [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _ci]
+        f("fm_locate").restype = _ci
+        f("fm_locate").argtypes = [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _ci]
+        f("fm_count_device").restype = _ci
+        f("fm_count_device").argtypes = [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]
+        f("fm_locate_device").restype = _ci
+        f("fm_locate_device").argtypes = [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp]
         for sfx in ("u32", "u64"):
+            f(f"fm_build_{sfx}").restype = _ci
+            f(f"fm_build_{sfx}").argtypes = [_vp, _u64, _u64, _vp, ctypes.c_uint32, _vp, _u64, _ci]
+            f(f"fm_build_device_{sfx}").restype = _ci
+            f(f"fm_build_device_{sfx}").argtypes = [_vp, _u64, _u64, _vp, ctypes.c_uint32, _vp, _u64, _vp]
             f(f"build_{sfx}").restype = _ci
             f(f"build_{sfx}").argtypes = [_vp, _u64, _u64, _u64, _vp, _vp, _ci, ctypes.POINTER(Stats)]
             f(f"build_multi_{sfx}").restype = _ci
@@ -387,6 +401,86 @@ class CapsLib:
         sfx, _ = _sfx(idx_bits)
         self._check(self._f(f"inverse_bwt_device_{sfx}")(dBWT_ptr or None, n, int(primary), dT_ptr or None, dWS_ptr or None, ws_bytes,
                                                          stream or None))
+
+    # ------------------------------------------------------------------ FM-index (include/caps_sa_hip.h "FM-index")
+    def fm_index_bytes(self, n: int, sa_sample: int = 32, idx_bits: int = 32) -> int:
+        """Bytes of the index of n symbols; sa_sample = 0: without SA samples (count only)."""
+        out = _u64(0)
+        self._check(self._f("fm_index_bytes")(n, sa_sample, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    def fm_build(self, BWT, primary: int, SA=None, sa_sample: int = 32, idx_bits: int | None = None, device: int = 0) -> np.ndarray:
+        """The index of (BWT, primary) as one np.uint8 blob; SA (the whole suffix array) adds the samples locate needs.  The index
+        width follows SA's dtype, else n, unless idx_bits is given.  More than 4 distinct bytes: CapsSaError with code -6."""
+        B = self._text(BWT)
+        n = int(B.size)
+        if idx_bits is None:
+            idx_bits = 64 if (SA is not None and np.asarray(SA).dtype.itemsize == 8) or n > 0xFFFFFFFF else 32
+        sfx, dt = _sfx(idx_bits)
+        if SA is not None:
+            SA = np.ascontiguousarray(SA, dtype=dt)
+            if SA.size != n:
+                raise ValueError("SA must be the whole suffix array: n entries")
+        blob = np.zeros(self.fm_index_bytes(n, sa_sample if SA is not None else 0, idx_bits), dtype=np.uint8)
+        self._check(self._f(f"fm_build_{sfx}")(B.ctypes.data if n else None, n, int(primary) if n else 0,
+                                               SA.ctypes.data if SA is not None else None, sa_sample, blob.ctypes.data, blob.size, device))
+        return blob
+
+    def fm_build_device(self, dBWT_ptr: int, n: int, primary: int, dSA_ptr: int, sa_sample: int, dIndex_ptr: int, index_bytes: int,
+                        idx_bits: int = 32, stream: int = 0) -> None:
+        """The index in device memory: dBWT_ptr (n bytes), dSA_ptr (0: no samples) -> dIndex_ptr (index_bytes >= fm_index_bytes)."""
+        sfx, _ = _sfx(idx_bits)
+        self._check(self._f(f"fm_build_device_{sfx}")(dBWT_ptr or None, n, int(primary), dSA_ptr or None, sa_sample, dIndex_ptr or None,
+                                                      index_bytes, stream or None))
+
+    @staticmethod
+    def _patterns(patterns):
+        """A list of bytes / np.uint8 arrays -> (concatenated bytes, u64 offsets[q + 1])."""
+        arrs = [np.frombuffer(bytes(p), dtype=np.uint8) if isinstance(p, (bytes, bytearray)) else np.ascontiguousarray(p, dtype=np.uint8)
+                for p in patterns]
+        off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+        if arrs:
+            off[1:] = np.cumsum([a.size for a in arrs], dtype=np.uint64)
+        cat = np.concatenate(arrs) if arrs and int(off[-1]) else np.zeros(0, dtype=np.uint8)
+        return cat, off
+
+    def fm_count(self, index: np.ndarray, patterns, device: int = 0):
+        """(first, count) as np.uint64 arrays for a list of patterns (bytes / np.uint8 arrays), or for (bytes, offsets) given as a
+        tuple: occurrences of pattern j = SA[first[j] : first[j] + count[j]]."""
+        cat, off = patterns if isinstance(patterns, tuple) else self._patterns(patterns)
+        cat = np.ascontiguousarray(cat, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        q = off.size - 1
+        first = np.zeros(q, dtype=np.uint64)
+        count = np.zeros(q, dtype=np.uint64)
+        self._check(self._f("fm_count")(index.ctypes.data, index.size, cat.ctypes.data if cat.size else None, off.ctypes.data, q,
+                                        first.ctypes.data, count.ctypes.data, device))
+        return first, count
+
+    def fm_locate(self, index: np.ndarray, first, count, out_off=None, device: int = 0):
+        """Positions of the ranks first[j] + t, t < min(count[j], out_off[j + 1] - out_off[j]) -> (pos u64[out_off[q]], out_off);
+        out_off = None: every hit of every query."""
+        first = np.ascontiguousarray(first, dtype=np.uint64)
+        count = np.ascontiguousarray(count, dtype=np.uint64)
+        q = first.size
+        if out_off is None:
+            out_off = np.zeros(q + 1, dtype=np.uint64)
+            out_off[1:] = np.cumsum(count, dtype=np.uint64)
+        out_off = np.ascontiguousarray(out_off, dtype=np.uint64)
+        pos = np.full(int(out_off[-1]) if q else 0, 2**64 - 1, dtype=np.uint64)
+        self._check(self._f("fm_locate")(index.ctypes.data, index.size, first.ctypes.data, count.ctypes.data, out_off.ctypes.data, q,
+                                         pos.ctypes.data if pos.size else None, device))
+        return pos, out_off
+
+    def fm_count_device(self, dIndex_ptr: int, index_bytes: int, dPat_ptr: int, dPatOff_ptr: int, q: int, dFirst_ptr: int, dCount_ptr: int,
+                        stream: int = 0) -> None:
+        self._check(self._f("fm_count_device")(dIndex_ptr or None, index_bytes, dPat_ptr or None, dPatOff_ptr or None, q, dFirst_ptr or None,
+                                               dCount_ptr or None, stream or None))
+
+    def fm_locate_device(self, dIndex_ptr: int, index_bytes: int, dFirst_ptr: int, dCount_ptr: int, dOutOff_ptr: int, q: int, dPos_ptr: int,
+                         stream: int = 0) -> None:
+        self._check(self._f("fm_locate_device")(dIndex_ptr or None, index_bytes, dFirst_ptr or None, dCount_ptr or None, dOutOff_ptr or None, q,
+                                                dPos_ptr or None, stream or None))
 
     # ------------------------------------------------------------------ kernel-level entry points
     def sort_suffixes(self, T, idx, idx_bits: int = 32, device: int = 0):

@@ -19,6 +19,7 @@
 //  * construct_bwt() (not in the reference): construct() plus the Burrows-Wheeler transform (include/caps_sa_hip.h), one device;
 //    its n-byte buffer is allocated by the first construct_bwt(), so construct() callers pay nothing for it.
 //  * the free function inverse_bwt() (not in the reference): the text back from (BWT, primary).
+//  * the class FM_Index (not in the reference either): count and locate over (BWT, primary) and a sample of the SA.
 #ifndef CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 #define CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 
@@ -165,6 +166,87 @@ inline void inverse_bwt(const uint8_t* BWT, uint64_t n, uint64_t primary, char* 
         throw std::runtime_error(std::string(n <= UINT32_MAX ? "caps_sa_hip_inverse_bwt_u32: " : "caps_sa_hip_inverse_bwt_u64: ") +
                                  caps_sa_hip_last_error());
 }
+
+// FM-index over (BWT, primary) (include/caps_sa_hip.h "FM-index"; not in the reference): count and locate for batches of patterns
+// over texts of at most 4 distinct bytes.  The index is one blob (data(), size()); save / load write and read exactly it.  Every
+// error of the C ABI is thrown as std::runtime_error with its message.
+class FM_Index
+{
+public:
+    FM_Index() : device_(0) {}
+
+    // SA: null (an index that counts), or the whole suffix array, idx_t = uint32_t / uint64_t (it also locates)
+    template <typename idx_t>
+    static FM_Index build(const uint8_t* BWT, uint64_t n, uint64_t primary, const idx_t* SA, uint32_t sa_sample = 32, int device = 0)
+    {
+        static_assert(std::is_same<idx_t, uint32_t>::value || std::is_same<idx_t, uint64_t>::value, "uint32_t or uint64_t");
+        FM_Index fm;
+        fm.device_ = device;
+        uint64_t bytes = 0;
+        check(caps_sa_hip_fm_index_bytes(n, SA ? sa_sample : 0, (int)sizeof(idx_t), &bytes), "caps_sa_hip_fm_index_bytes");
+        fm.blob_.resize(static_cast<std::size_t>(bytes));
+        if (sizeof(idx_t) == 4)
+            check(caps_sa_hip_fm_build_u32(BWT, n, primary, reinterpret_cast<const uint32_t*>(SA), sa_sample, fm.blob_.data(), bytes, device),
+                  "caps_sa_hip_fm_build_u32");
+        else
+            check(caps_sa_hip_fm_build_u64(BWT, n, primary, reinterpret_cast<const uint64_t*>(SA), sa_sample, fm.blob_.data(), bytes, device),
+                  "caps_sa_hip_fm_build_u64");
+        return fm;
+    }
+
+    const uint8_t* data() const { return blob_.data(); }
+    std::size_t size() const { return blob_.size(); }
+
+    // patterns: the concatenated bytes, off[j] .. off[j + 1] the j-th of them (off.size() = q + 1) -> first / count, q entries each
+    void count(const std::string& patterns, const std::vector<uint64_t>& off, std::vector<uint64_t>& first, std::vector<uint64_t>& cnt) const
+    {
+        const uint64_t q = off.empty() ? 0 : off.size() - 1;
+        first.assign(q, 0);
+        cnt.assign(q, 0);
+        check(caps_sa_hip_fm_count(blob_.data(), blob_.size(), reinterpret_cast<const uint8_t*>(patterns.data()), off.data(), q,
+                                   first.data(), cnt.data(), device_), "caps_sa_hip_fm_count");
+    }
+
+    // at most max_hits positions per query, in SA order: pos[out_off[j] .. out_off[j + 1])
+    void locate(const std::vector<uint64_t>& first, const std::vector<uint64_t>& cnt, uint64_t max_hits, std::vector<uint64_t>& out_off,
+                std::vector<uint64_t>& pos) const
+    {
+        const uint64_t q = first.size();
+        out_off.assign(q + 1, 0);
+        for (uint64_t j = 0; j < q; ++j) out_off[j + 1] = out_off[j] + (cnt[j] < max_hits ? cnt[j] : max_hits);
+        pos.assign(static_cast<std::size_t>(out_off[q]), 0);
+        check(caps_sa_hip_fm_locate(blob_.data(), blob_.size(), first.data(), cnt.data(), out_off.data(), q, pos.data(), device_),
+              "caps_sa_hip_fm_locate");
+    }
+
+    void save(const std::string& path) const
+    {
+        std::ofstream out(path, std::ios::binary);
+        if (out) out.write(reinterpret_cast<const char*>(blob_.data()), static_cast<std::streamsize>(blob_.size()));
+        if (!out) throw std::runtime_error(path + " : cannot write");
+    }
+
+    static FM_Index load(const std::string& path, int device = 0)
+    {
+        std::ifstream in(path, std::ios::binary | std::ios::ate);
+        if (!in) throw std::runtime_error(path + " : cannot open");
+        const std::streamsize size = in.tellg();
+        FM_Index fm;
+        fm.device_ = device;
+        fm.blob_.resize(size > 0 ? static_cast<std::size_t>(size) : 0);
+        in.seekg(0);
+        if (size > 0 && !in.read(reinterpret_cast<char*>(fm.blob_.data()), size)) throw std::runtime_error(path + " : cannot read");
+        return fm;
+    }
+
+private:
+    static void check(int rc, const char* what)
+    {
+        if (rc != CAPS_SA_OK) throw std::runtime_error(std::string(what) + ": " + caps_sa_hip_last_error());
+    }
+    std::vector<uint8_t> blob_;
+    int device_;
+};
 
 }  // namespace CaPS_SA
 

@@ -425,6 +425,11 @@ struct HostPathCache {
     std::vector<char*> host_chunks;    // page-locked staging of the LCP bytes (HostCopySink), host_chunk_bytes each
     size_t host_chunk_bytes = 0;
     uint64_t calls = 0;                // host-buffer builds of this process so far
+    // the FM-index at the head of the block (fm_count_host / fm_locate_host): the host blob it was uploaded from, its size, its
+    // header and a sum over a stride of its body; null when anything else has used the block since
+    const void* fm_host = nullptr;
+    uint64_t fm_bytes = 0, fm_sum = 0;
+    uint64_t fm_hdr[32] = {};
 };
 inline HostPathCache& host_cache()
 {
@@ -444,6 +449,7 @@ inline void release_host_cache_locked(HostPathCache& c)
     c.base = nullptr;
     c.bytes = 0;
     c.device = -1;
+    c.fm_host = nullptr;
 }
 
 // BWT (build_bwt): null, or n bytes of the caller's that receive the BWT slice by slice with the rest of the result (HostCopySink);
@@ -461,6 +467,7 @@ int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, 
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
+        hc.fm_host = nullptr;                                // (the block is this build's now)
         auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
         // the text arena is sized for 2-bit codes when the first MiB of the text shows at most 4 distinct bytes (a text that
         // turns out to have more is built again below with the arena of 8-bit codes)
@@ -1117,6 +1124,7 @@ int inverse_bwt_host(const uint8_t* B, uint64_t n, uint64_t primary, char* T, in
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
+        hc.fm_host = nullptr;
         auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
         const InvPlan p = inv_plan<idx_t>(n);
         const size_t off_T = up(n), off_ws = off_T + up(n), total = off_ws + p.bytes;
@@ -1136,6 +1144,429 @@ int inverse_bwt_host(const uint8_t* B, uint64_t n, uint64_t primary, char* T, in
         be.h2d(dB, B, n);
         if (!run_inverse_bwt<idx_t>(be, dB, n, primary, dT, hc.base + off_ws, p)) return fail(CAPS_SA_EINVAL, not_a_bwt_msg());
         be.d2h(T, dT, n);
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+
+// ---- FM-index (include/caps_sa_hip.h caps_sa_hip_fm_*; kernels.h fm_*) ------------------------------------------------------------
+// The blob: a header of FM_HDR_WORDS 64-bit words, the Occ blocks, then (with samples) the per-block mark ranks and the samples.
+constexpr uint64_t FM_MAGIC = 0x31494D4653504143ull;      // "CAPSFMI1"
+constexpr uint64_t FM_VERSION = 1;
+constexpr uint32_t FM_HDR_WORDS = 32;
+enum { FMH_MAGIC = 0, FMH_VERSION, FMH_N, FMH_PRIMARY, FMH_IDX_BYTES, FMH_SIGMA, FMH_SYMS, FMH_C0, FMH_S = FMH_C0 + 5, FMH_NSAMPLES,
+       FMH_NBLOCKS, FMH_OFF_OCC, FMH_OFF_MRANK, FMH_OFF_SAMPLES, FMH_TOTAL };
+
+struct FmLayout {
+    uint64_t n_blocks = 0, n_samples = 0, off_occ = 0, off_mrank = 0, off_samples = 0, total = 0;
+};
+inline FmLayout fm_layout(uint64_t n, uint32_t s, int idx_bytes)
+{
+    auto up = [](uint64_t b) { return (b + 63) & ~uint64_t(63); };
+    const uint64_t rows = idx_bytes == 4 ? 128 : 256, block_bytes = rows / 2;
+    FmLayout l;
+    l.n_blocks = (n + 1) / rows + 1;
+    l.n_samples = s && n ? (n - 1) / s + 1 : 0;
+    l.off_occ = FM_HDR_WORDS * sizeof(uint64_t);
+    l.off_mrank = l.off_occ + l.n_blocks * block_bytes;
+    l.off_samples = l.off_mrank + (s ? up(l.n_blocks * (uint64_t)idx_bytes) : 0);
+    l.total = l.off_samples + (s ? up(l.n_samples * (uint64_t)idx_bytes) : 0);
+    return l;
+}
+inline bool fm_sample_ok(uint64_t s) { return s >= 1 && s <= FM_MAX_SAMPLE && (s & (s - 1)) == 0; }
+
+inline int fm_index_bytes(uint64_t n, uint32_t s, int idx_bytes, uint64_t* bytes)
+{
+    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (s && !fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be 0 (no samples) or a power of two in 1 .. 1024");
+    *bytes = fm_layout(n, s, idx_bytes).total;
+    return CAPS_SA_OK;
+}
+
+// a few device words of the FM calls (flags, totals), one set per thread and device, kept (primary_word's reasons)
+inline uint64_t* fm_words(Backend& be)
+{
+#ifdef CAPS_EMUL
+    const int dev = 0;
+#else
+    int dev = 0;
+    CAPS_HIP(hipGetDevice(&dev));
+#endif
+    thread_local std::vector<uint64_t*> words;
+    if ((size_t)dev >= words.size()) words.resize((size_t)dev + 1, nullptr);
+    if (!words[dev]) words[dev] = static_cast<uint64_t*>(be.alloc(16 * sizeof(uint64_t)));
+    return words[dev];
+}
+
+// the header, checked on the host before any kernel reads the body; fills the kernels' view of the blob at dIndex
+inline int fm_check_header(const uint64_t* h, uint64_t index_bytes, const void* dIndex, FmView& v)
+{
+    if (h[FMH_MAGIC] != FM_MAGIC) return fail(CAPS_SA_EINVAL, "not an FM-index of this library (wrong magic)");
+    if (h[FMH_VERSION] != FM_VERSION) return fail(CAPS_SA_EINVAL, "FM-index of another format version");
+    const uint64_t ib = h[FMH_IDX_BYTES], n = h[FMH_N], s = h[FMH_S];
+    if (ib != 4 && ib != 8) return fail(CAPS_SA_EINVAL, "FM-index header: bad index width");
+    if (ib == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "FM-index header: n does not fit its index width");
+    if (n >= 1 && h[FMH_PRIMARY] >= n) return fail(CAPS_SA_EINVAL, "FM-index header: primary >= n");
+    if (s && !fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "FM-index header: bad sample distance");
+    if (h[FMH_SIGMA] > 4 || (n >= 1 && h[FMH_SIGMA] == 0)) return fail(CAPS_SA_EINVAL, "FM-index header: bad alphabet size");
+    const FmLayout l = fm_layout(n, (uint32_t)s, (int)ib);
+    if (h[FMH_NBLOCKS] != l.n_blocks || h[FMH_OFF_OCC] != l.off_occ || h[FMH_OFF_MRANK] != l.off_mrank ||
+        h[FMH_OFF_SAMPLES] != l.off_samples || h[FMH_TOTAL] != l.total || h[FMH_NSAMPLES] != l.n_samples)
+        return fail(CAPS_SA_EINVAL, "FM-index header: section offsets do not fit n, the index width and the sample distance");
+    if (l.total > index_bytes) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than the FM-index (truncated blob)");
+    if (h[FMH_C0] != 1 || h[FMH_C0 + 4] != n + 1) return fail(CAPS_SA_EINVAL, "FM-index header: bad C[]");
+    for (int c = 0; c < 4; ++c)
+        if (h[FMH_C0 + c] > h[FMH_C0 + c + 1]) return fail(CAPS_SA_EINVAL, "FM-index header: bad C[]");
+    v.n = n;
+    v.primary = h[FMH_PRIMARY];
+    for (int c = 0; c < 5; ++c) v.C[c] = h[FMH_C0 + c];
+    v.n_blocks = l.n_blocks;
+    v.n_samples = l.n_samples;
+    const char* base = static_cast<const char*>(dIndex);
+    v.occ = reinterpret_cast<const uint32_t*>(base + l.off_occ);
+    v.mrank = base + l.off_mrank;
+    v.samples = base + l.off_samples;
+    v.sigma = (uint32_t)h[FMH_SIGMA];
+    v.syms = (uint32_t)h[FMH_SYMS];
+    v.s = (uint32_t)s;
+    return CAPS_SA_OK;
+}
+
+template <typename idx_t>
+int fm_check_build(const void* B, uint64_t n, uint64_t primary, const void* SA, uint64_t s, const void* index, uint64_t index_bytes, uint64_t* need)
+{
+    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
+    if (SA && !fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be a power of two in 1 .. 1024");
+    if (!index) return fail(CAPS_SA_EINVAL, "null index");
+    if (n && !B) return fail(CAPS_SA_EINVAL, "null BWT");
+    if (n && primary >= n) return fail(CAPS_SA_EINVAL, "primary >= n");
+    *need = fm_layout(n, SA ? (uint32_t)s : 0u, (int)sizeof(idx_t)).total;
+    if (index_bytes < *need) return fail(CAPS_SA_EINVAL, "index_bytes too small (caps_sa_hip_fm_index_bytes)");
+    return CAPS_SA_OK;
+}
+
+// the build on be's stream; synchronises (the alphabet and the totals are read back).  hdr_out: the header as written.
+template <typename idx_t>
+int run_fm_build(Backend& be, const uint8_t* dB, uint64_t n, uint64_t primary, const idx_t* dSA, uint32_t s, char* dIndex, uint64_t* hdr_out)
+{
+    using G = FmGeom<idx_t>;
+    if (!dSA) s = 0;
+    const FmLayout l = fm_layout(n, s, (int)sizeof(idx_t));
+    uint64_t h[FM_HDR_WORDS] = {};
+    h[FMH_MAGIC] = FM_MAGIC; h[FMH_VERSION] = FM_VERSION; h[FMH_N] = n; h[FMH_PRIMARY] = n ? primary : 0; h[FMH_IDX_BYTES] = sizeof(idx_t);
+    h[FMH_S] = s; h[FMH_NSAMPLES] = l.n_samples; h[FMH_NBLOCKS] = l.n_blocks; h[FMH_OFF_OCC] = l.off_occ; h[FMH_OFF_MRANK] = l.off_mrank;
+    h[FMH_OFF_SAMPLES] = l.off_samples; h[FMH_TOTAL] = l.total;
+    h[FMH_C0] = 1;
+    for (int c = 1; c < 5; ++c) h[FMH_C0 + c] = n + 1;
+    if (n == 0) {
+        be.memset(dIndex + l.off_occ, 0, l.total - l.off_occ);
+    } else {
+        DevAllocs da(be);
+        const uint64_t n_tiles = (l.n_blocks * G::ROWS + FM_TILE - 1) / FM_TILE;
+        uint32_t* present = da.get<uint32_t>(8);
+        uint64_t* cnt = da.get<uint64_t>(FM_KEYS * n_tiles);
+        uint64_t* total = da.get<uint64_t>(FM_KEYS);
+        be.memset(present, 0, 8 * sizeof(uint32_t));
+        CAPS_LAUNCH(fm_probe_kernel, capped_grid(std::min<uint64_t>((n + 16ull * FM_NT - 1) / (16ull * FM_NT), 4096), FM_NT), FM_NT, be, dB, n, present);
+        uint32_t pm[8];
+        be.d2h(pm, present, sizeof pm);
+        be.sync();
+        uint32_t sigma = 0, syms = 0;
+        for (uint32_t k = 0; k < 256; ++k) {                 // signed-char order: 0x80 .. 0xFF, then 0x00 .. 0x7F
+            const uint32_t b = k ^ 0x80u;
+            if (!((pm[b / 32] >> (b % 32)) & 1u)) continue;
+            if (sigma < 4) syms |= b << (8 * sigma);
+            ++sigma;
+        }
+        if (sigma > 4) return fail(CAPS_SA_EALPHABET, "the BWT has more than 4 distinct bytes: the FM-index packs 2-bit codes");
+        h[FMH_SIGMA] = sigma;
+        h[FMH_SYMS] = syms;
+        const uint32_t tg = capped_grid(std::min<uint64_t>(n_tiles, 16384), FM_NT);
+        CAPS_LAUNCH(fm_tile_count_kernel, tg, FM_NT, be, dB, n, primary, n_tiles, syms, sigma, cnt);
+        CAPS_LAUNCH(fm_scan_kernel, 4, FM_NT, be, cnt, n_tiles, 0u, 4u, total);
+        uint32_t* occ = reinterpret_cast<uint32_t*>(dIndex + l.off_occ);
+        CAPS_LAUNCH((fm_pack_kernel<idx_t>), tg, FM_NT, be, dB, n, primary, n_tiles, l.n_blocks, syms, sigma, (const uint64_t*)cnt, occ);
+        uint64_t tot[FM_KEYS] = {};
+        be.d2h(tot, total, 4 * sizeof(uint64_t));
+        if (s) {
+            idx_t* mrank = reinterpret_cast<idx_t*>(dIndex + l.off_mrank);
+            idx_t* samples = reinterpret_cast<idx_t*>(dIndex + l.off_samples);
+            // (the padding behind the two sections: the blob is the same bytes whatever the memory held)
+            const uint64_t mrank_end = l.off_mrank + l.n_blocks * sizeof(idx_t), samples_end = l.off_samples + l.n_samples * sizeof(idx_t);
+            if (l.off_samples > mrank_end) be.memset(dIndex + mrank_end, 0, l.off_samples - mrank_end);
+            if (l.total > samples_end) be.memset(dIndex + samples_end, 0, l.total - samples_end);
+            CAPS_LAUNCH((fm_mark_kernel<idx_t>), tg, FM_NT, be, dSA, n, n_tiles, l.n_blocks, s, occ, mrank, cnt);
+            CAPS_LAUNCH(fm_scan_kernel, 1, FM_NT, be, cnt, n_tiles, 4u, 1u, total);
+            CAPS_LAUNCH((fm_sample_kernel<idx_t>), tg, FM_NT, be, dSA, n, n_tiles, l.n_blocks, s, (const uint32_t*)occ, mrank,
+                        (const uint64_t*)cnt, samples, l.n_samples);
+            be.d2h(tot + 4, total + 4, sizeof(uint64_t));
+        }
+        be.sync();
+        // code 0 also counted the '$' row and the rows behind n
+        const uint64_t pad = n_tiles * FM_TILE - (n + 1);
+        if (tot[0] < pad + 1 || tot[0] - pad - 1 + tot[1] + tot[2] + tot[3] != n) throw HipError("fm build: the symbol counts do not add up to n");
+        tot[0] -= pad + 1;
+        for (int c = 0; c < 4; ++c) h[FMH_C0 + c + 1] = h[FMH_C0 + c] + tot[c];
+        if (s && tot[4] != l.n_samples)
+            return fail(CAPS_SA_EINVAL, ("SA is not the suffix array of a text of n symbols: it holds " + std::to_string(tot[4]) + " multiples of sa_sample, a suffix array " +
+                                         std::to_string(l.n_samples)).c_str());
+    }
+    be.h2d(dIndex, h, sizeof h);
+    be.sync();
+    if (hdr_out) std::memcpy(hdr_out, h, sizeof h);
+    return CAPS_SA_OK;
+}
+
+template <typename idx_t>
+int fm_build_device(const void* dB, uint64_t n, uint64_t primary, const void* dSA, uint64_t s, void* dIndex, uint64_t index_bytes, void* stream)
+{
+    uint64_t need = 0;
+    if (int rc = fm_check_build<idx_t>(dB, n, primary, dSA, s, dIndex, index_bytes, &need)) return rc;
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        return run_fm_build<idx_t>(be, static_cast<const uint8_t*>(dB), n, primary, static_cast<const idx_t*>(dSA), (uint32_t)s,
+                                   static_cast<char*>(dIndex), nullptr);
+    });
+}
+
+// the host-path block with room for `total` bytes (what build_host and inverse_bwt_host do)
+inline void fm_host_block(HostPathCache& hc, Backend& be, int device, size_t total)
+{
+    if (hc.device == device && hc.bytes >= total) return;
+    std::vector<char*> keep;
+    keep.swap(hc.host_chunks);
+    const size_t keep_bytes = hc.host_chunk_bytes;
+    release_host_cache_locked(hc);
+    hc.host_chunks.swap(keep);
+    hc.host_chunk_bytes = keep_bytes;
+    hc.base = static_cast<char*>(be.alloc(total));
+    hc.bytes = total;
+    hc.device = device;
+}
+// what identifies an uploaded blob beside its address and size: its header and a sum over at most 4096 words of its body
+inline uint64_t fm_body_sum(const void* index, uint64_t bytes)
+{
+    const uint64_t words = bytes / 8, step = std::max<uint64_t>(1, words / 4096);
+    uint64_t s = 0, w = 0;
+    for (uint64_t k = FM_HDR_WORDS; k < words; k += step) { std::memcpy(&w, static_cast<const char*>(index) + k * 8, 8); s = s * 0x9E3779B97F4A7C15ull + w; }
+    return s;
+}
+inline void fm_mark_resident(HostPathCache& hc, const void* index, uint64_t bytes)
+{
+    hc.fm_host = index;
+    hc.fm_bytes = bytes;
+    std::memcpy(hc.fm_hdr, index, sizeof hc.fm_hdr);
+    hc.fm_sum = fm_body_sum(index, bytes);
+}
+
+template <typename idx_t>
+int fm_build_host(const uint8_t* B, uint64_t n, uint64_t primary, const idx_t* SA, uint64_t s, void* index, uint64_t index_bytes, int device)
+{
+    uint64_t need = 0;
+    if (int rc = fm_check_build<idx_t>(B, n, primary, SA, s, index, index_bytes, &need)) return rc;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        hc.fm_host = nullptr;
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const size_t off_B = up(need), off_SA = off_B + up(n ? n : 1), total = off_SA + (SA ? up(n * sizeof(idx_t)) : 0) + 256;
+        fm_host_block(hc, be, device, total);
+        uint8_t* dB = reinterpret_cast<uint8_t*>(hc.base + off_B);
+        idx_t* dSA = SA ? reinterpret_cast<idx_t*>(hc.base + off_SA) : nullptr;
+        be.h2d(dB, B, n);
+        if (SA) be.h2d(dSA, SA, n * sizeof(idx_t));
+        if (int rc = run_fm_build<idx_t>(be, dB, n, primary, dSA, (uint32_t)s, hc.base, nullptr)) return rc;
+        be.d2h(index, hc.base, need);
+        be.sync();
+        fm_mark_resident(hc, index, need);
+        return CAPS_SA_OK;
+    });
+}
+
+// count on device arrays; `hdr`: the header when the caller has read it already (the host forms), else it is read back here
+inline int run_fm_count(Backend& be, const void* dIndex, uint64_t index_bytes, const uint64_t* hdr, const void* dPat, const void* dPatOff, uint64_t q,
+                        void* dFirst, void* dCount)
+{
+    uint64_t h[FM_HDR_WORDS];
+    if (hdr) std::memcpy(h, hdr, sizeof h);
+    else { be.d2h(h, dIndex, sizeof h); be.sync(); }
+    FmView v;
+    if (int rc = fm_check_header(h, index_bytes, dIndex, v)) return rc;
+    if (q == 0) return CAPS_SA_OK;
+    uint64_t* words = fm_words(be);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(words);
+    const uint32_t g = capped_grid(std::min<uint64_t>((q + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+    be.memset(words, 0, sizeof(uint64_t));
+    CAPS_LAUNCH(fm_check_kernel, g, FM_NT, be, static_cast<const uint64_t*>(dPatOff), q, (const uint64_t*)nullptr, (const uint64_t*)nullptr, v.n, flags);
+    uint32_t f = 0;
+    be.d2h(&f, flags, sizeof f);
+    be.sync();
+    if (f & 1u) return fail(CAPS_SA_EINVAL, "pattern offsets are not monotone");
+    if (v.n == 0) {
+        be.memset(dFirst, 0, q * sizeof(uint64_t));
+        be.memset(dCount, 0, q * sizeof(uint64_t));
+    } else if (h[FMH_IDX_BYTES] == 4) {
+        CAPS_LAUNCH((fm_count_kernel<uint32_t>), g, FM_NT, be, v, static_cast<const uint8_t*>(dPat), static_cast<const uint64_t*>(dPatOff), q,
+                    static_cast<uint64_t*>(dFirst), static_cast<uint64_t*>(dCount));
+    } else {
+        CAPS_LAUNCH((fm_count_kernel<uint64_t>), g, FM_NT, be, v, static_cast<const uint8_t*>(dPat), static_cast<const uint64_t*>(dPatOff), q,
+                    static_cast<uint64_t*>(dFirst), static_cast<uint64_t*>(dCount));
+    }
+    be.sync();
+    return CAPS_SA_OK;
+}
+
+inline int fm_count_device(const void* dIndex, uint64_t index_bytes, const void* dPat, const void* dPatOff, uint64_t q, void* dFirst, void* dCount,
+                           void* stream)
+{
+    if (!dIndex) return fail(CAPS_SA_EINVAL, "null index");
+    if (index_bytes < FM_HDR_WORDS * sizeof(uint64_t)) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than an FM-index header");
+    if (q && (!dPatOff || !dFirst || !dCount)) return fail(CAPS_SA_EINVAL, "null pointer");
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        return run_fm_count(be, dIndex, index_bytes, nullptr, dPat, dPatOff, q, dFirst, dCount);
+    });
+}
+
+inline int run_fm_locate(Backend& be, const void* dIndex, uint64_t index_bytes, const uint64_t* hdr, const void* dFirst, const void* dCount,
+                         const void* dOutOff, uint64_t q, void* dPos)
+{
+    uint64_t h[FM_HDR_WORDS];
+    if (hdr) std::memcpy(h, hdr, sizeof h);
+    else { be.d2h(h, dIndex, sizeof h); be.sync(); }
+    FmView v;
+    if (int rc = fm_check_header(h, index_bytes, dIndex, v)) return rc;
+    if (v.s == 0 && v.n) return fail(CAPS_SA_EUNSUPPORTED, "this FM-index was built without SA samples: it can count, not locate");
+    if (q == 0) return CAPS_SA_OK;
+    uint64_t* words = fm_words(be);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(words);
+    const uint32_t g = capped_grid(std::min<uint64_t>((q + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+    be.memset(words, 0, sizeof(uint64_t));
+    CAPS_LAUNCH(fm_check_kernel, g, FM_NT, be, static_cast<const uint64_t*>(dOutOff), q, static_cast<const uint64_t*>(dFirst),
+                static_cast<const uint64_t*>(dCount), v.n, flags);
+    uint32_t f = 0;
+    uint64_t o_begin = 0, o_end = 0;
+    be.d2h(&f, flags, sizeof f);
+    be.d2h(&o_begin, dOutOff, sizeof(uint64_t));
+    be.d2h(&o_end, static_cast<const uint64_t*>(dOutOff) + q, sizeof(uint64_t));
+    be.sync();
+    if (f & 1u) return fail(CAPS_SA_EINVAL, "output offsets are not monotone");
+    if (f & 2u) return fail(CAPS_SA_EINVAL, "first + count > n");
+    if (o_end == o_begin || v.n == 0) return CAPS_SA_OK;
+    if (!dPos) return fail(CAPS_SA_EINVAL, "null pointer");
+    const uint32_t lg = capped_grid(std::min<uint64_t>((o_end - o_begin + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+    if (h[FMH_IDX_BYTES] == 4)
+        CAPS_LAUNCH((fm_locate_kernel<uint32_t>), lg, FM_NT, be, v, static_cast<const uint64_t*>(dFirst), static_cast<const uint64_t*>(dCount),
+                    static_cast<const uint64_t*>(dOutOff), q, o_begin, o_end, static_cast<uint64_t*>(dPos), flags);
+    else
+        CAPS_LAUNCH((fm_locate_kernel<uint64_t>), lg, FM_NT, be, v, static_cast<const uint64_t*>(dFirst), static_cast<const uint64_t*>(dCount),
+                    static_cast<const uint64_t*>(dOutOff), q, o_begin, o_end, static_cast<uint64_t*>(dPos), flags);
+    be.d2h(&f, flags, sizeof f);
+    be.sync();
+    if (f & 4u)
+        return fail(CAPS_SA_EINVAL, "a locate walk did not reach a sampled row within sa_sample steps: the blob is not an index this library built");
+    return CAPS_SA_OK;
+}
+
+inline int fm_locate_device(const void* dIndex, uint64_t index_bytes, const void* dFirst, const void* dCount, const void* dOutOff, uint64_t q,
+                            void* dPos, void* stream)
+{
+    if (!dIndex) return fail(CAPS_SA_EINVAL, "null index");
+    if (index_bytes < FM_HDR_WORDS * sizeof(uint64_t)) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than an FM-index header");
+    if (q && (!dOutOff || !dFirst || !dCount)) return fail(CAPS_SA_EINVAL, "null pointer");
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        return run_fm_locate(be, dIndex, index_bytes, nullptr, dFirst, dCount, dOutOff, q, dPos);
+    });
+}
+
+// the host forms: the blob at the head of the host-path block (uploaded unless it is the one there already), the query arrays behind it
+inline void fm_upload(HostPathCache& hc, Backend& be, int device, const void* index, uint64_t blob, size_t total)
+{
+    const bool resident = hc.fm_host == index && hc.fm_bytes == blob && hc.device == device && hc.bytes >= total && hc.base &&
+                          std::memcmp(hc.fm_hdr, index, sizeof hc.fm_hdr) == 0 && hc.fm_sum == fm_body_sum(index, blob);
+    if (resident) return;
+    hc.fm_host = nullptr;
+    fm_host_block(hc, be, device, total);
+    be.h2d(hc.base, index, blob);
+    be.sync();
+    fm_mark_resident(hc, index, blob);
+}
+inline int fm_host_header(const void* index, uint64_t index_bytes, uint64_t* h, FmView& v)
+{
+    if (!index) return fail(CAPS_SA_EINVAL, "null index");
+    if (index_bytes < FM_HDR_WORDS * sizeof(uint64_t)) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than an FM-index header");
+    std::memcpy(h, index, FM_HDR_WORDS * sizeof(uint64_t));
+    return fm_check_header(h, index_bytes, index, v);
+}
+
+inline int fm_count_host(const void* index, uint64_t index_bytes, const uint8_t* pat, const uint64_t* patoff, uint64_t q, uint64_t* first,
+                         uint64_t* count, int device)
+{
+    uint64_t h[FM_HDR_WORDS];
+    FmView v;
+    if (int rc = fm_host_header(index, index_bytes, h, v)) return rc;
+    if (q == 0) return CAPS_SA_OK;
+    if (!patoff || !first || !count) return fail(CAPS_SA_EINVAL, "null pointer");
+    for (uint64_t j = 0; j < q; ++j)
+        if (patoff[j + 1] < patoff[j]) return fail(CAPS_SA_EINVAL, "pattern offsets are not monotone");
+    const uint64_t pbytes = patoff[q];
+    if (pbytes && !pat) return fail(CAPS_SA_EINVAL, "null pointer");
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const uint64_t blob = h[FMH_TOTAL];
+        const size_t off_pat = up(blob), off_off = off_pat + up(pbytes + 1), off_first = off_off + up((q + 1) * 8), off_count = off_first + up(q * 8);
+        fm_upload(hc, be, device, index, blob, off_count + up(q * 8));
+        be.h2d(hc.base + off_pat, pat, pbytes);
+        be.h2d(hc.base + off_off, patoff, (q + 1) * 8);
+        if (int rc = run_fm_count(be, hc.base, blob, h, hc.base + off_pat, hc.base + off_off, q, hc.base + off_first, hc.base + off_count)) return rc;
+        be.d2h(first, hc.base + off_first, q * 8);
+        be.d2h(count, hc.base + off_count, q * 8);
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+
+inline int fm_locate_host(const void* index, uint64_t index_bytes, const uint64_t* first, const uint64_t* count, const uint64_t* outoff, uint64_t q,
+                          uint64_t* pos, int device)
+{
+    uint64_t h[FM_HDR_WORDS];
+    FmView v;
+    if (int rc = fm_host_header(index, index_bytes, h, v)) return rc;
+    if (v.s == 0 && v.n) return fail(CAPS_SA_EUNSUPPORTED, "this FM-index was built without SA samples: it can count, not locate");
+    if (q == 0) return CAPS_SA_OK;
+    if (!outoff || !first || !count) return fail(CAPS_SA_EINVAL, "null pointer");
+    for (uint64_t j = 0; j < q; ++j) {
+        if (outoff[j + 1] < outoff[j]) return fail(CAPS_SA_EINVAL, "output offsets are not monotone");
+        if (first[j] > v.n || count[j] > v.n - first[j]) return fail(CAPS_SA_EINVAL, "first + count > n");
+    }
+    const uint64_t o_end = outoff[q];
+    if (o_end > outoff[0] && !pos) return fail(CAPS_SA_EINVAL, "null pointer");
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const uint64_t blob = h[FMH_TOTAL];
+        const size_t off_first = up(blob), off_count = off_first + up(q * 8), off_off = off_count + up(q * 8), off_pos = off_off + up((q + 1) * 8);
+        fm_upload(hc, be, device, index, blob, off_pos + up(o_end * 8 + 8));
+        be.h2d(hc.base + off_first, first, q * 8);
+        be.h2d(hc.base + off_count, count, q * 8);
+        be.h2d(hc.base + off_off, outoff, (q + 1) * 8);
+        be.memset(hc.base + off_pos, 0xFF, o_end * 8 + 8);   // (slots beyond a query's hits come back as UINT64_MAX)
+        if (int rc = run_fm_locate(be, hc.base, blob, h, hc.base + off_first, hc.base + off_count, hc.base + off_off, q, hc.base + off_pos)) return rc;
+        be.d2h(pos + outoff[0], hc.base + off_pos + outoff[0] * 8, (o_end - outoff[0]) * 8);
         be.sync();
         return CAPS_SA_OK;
     });
@@ -1548,6 +1979,29 @@ int CAPS_API(inverse_bwt_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* b
     { return caps::inverse_bwt_host<IDX>(BWT, n, primary, T, device); }
 CAPS_DEFINE_INVERSE(u32, uint32_t)
 CAPS_DEFINE_INVERSE(u64, uint64_t)
+
+int CAPS_API(fm_index_bytes)(uint64_t n, uint32_t sa_sample, int idx_bytes, uint64_t* bytes) { return caps::fm_index_bytes(n, sa_sample, idx_bytes, bytes); }
+#define CAPS_DEFINE_FM(SFX, IDX)                                                                                           \
+    int CAPS_API(fm_build_device_##SFX)(const void* dBWT, uint64_t n, uint64_t primary, const void* dSA, uint32_t sa_sample, \
+                                        void* dIndex, uint64_t index_bytes, void* stream)                                  \
+    { return caps::fm_build_device<IDX>(dBWT, n, primary, dSA, sa_sample, dIndex, index_bytes, stream); }                  \
+    int CAPS_API(fm_build_##SFX)(const uint8_t* BWT, uint64_t n, uint64_t primary, const IDX* SA, uint32_t sa_sample,      \
+                                 void* index, uint64_t index_bytes, int device)                                            \
+    { return caps::fm_build_host<IDX>(BWT, n, primary, SA, sa_sample, index, index_bytes, device); }
+CAPS_DEFINE_FM(u32, uint32_t)
+CAPS_DEFINE_FM(u64, uint64_t)
+int CAPS_API(fm_count_device)(const void* dIndex, uint64_t index_bytes, const void* dPatterns, const void* dPatOff, uint64_t q,
+                              void* dFirst, void* dCount, void* stream)
+{ return caps::fm_count_device(dIndex, index_bytes, dPatterns, dPatOff, q, dFirst, dCount, stream); }
+int CAPS_API(fm_locate_device)(const void* dIndex, uint64_t index_bytes, const void* dFirst, const void* dCount, const void* dOutOff,
+                               uint64_t q, void* dPos, void* stream)
+{ return caps::fm_locate_device(dIndex, index_bytes, dFirst, dCount, dOutOff, q, dPos, stream); }
+int CAPS_API(fm_count)(const void* index, uint64_t index_bytes, const uint8_t* patterns, const uint64_t* pat_off, uint64_t q,
+                       uint64_t* first, uint64_t* count, int device)
+{ return caps::fm_count_host(index, index_bytes, patterns, pat_off, q, first, count, device); }
+int CAPS_API(fm_locate)(const void* index, uint64_t index_bytes, const uint64_t* first, const uint64_t* count, const uint64_t* out_off,
+                        uint64_t q, uint64_t* pos, int device)
+{ return caps::fm_locate_host(index, index_bytes, first, count, out_off, q, pos, device); }
 
 
 struct caps_sa_shard { std::unique_ptr<caps::ShardBase> impl; };

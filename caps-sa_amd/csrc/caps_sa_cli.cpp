@@ -3,7 +3,14 @@
 //
 //     caps_sa <input_path> <output_path> [subproblem-count] [bounded-context] [--pretty-print] [--gpus N] [--bwt PATH]
 //     caps_sa --inverse-bwt IN.bwt OUT
+//     caps_sa <input_path> <output_path> [subproblem-count] --fm-index PATH [--fm-sample S]
+//     caps_sa --fm-search INDEX PATTERNS [--locate K]
 //
+// * --fm-index PATH [--fm-sample S] (not in the reference): also write the FM-index of the (remapped) text to PATH (the blob of
+//   include/caps_sa_hip.h "FM-index", SA samples every S = 32 text positions; S a power of two, 1 .. 1024).  One GPU, no bounded
+//   context, like --bwt: refused before any file is opened;
+// * --fm-search INDEX PATTERNS [--locate K] (not in the reference): one pattern per line of PATTERNS, remapped like the text;
+//   per line the count, and with --locate K up to K positions in suffix-array order.  Any other argument is refused;
 // * --inverse-bwt IN.bwt OUT (not in the reference): the text back from a file that --bwt wrote (u64 n, u64 primary, n bytes):
 //   its n bytes to OUT, written only after the inverse has succeeded.  An unreadable IN, a size other than 16 + n, primary >= n
 //   and any other argument are refused before OUT is opened;
@@ -61,7 +68,7 @@ static bool parse_count(const std::string& s, size_t& out)
 
 template <typename idx_t>
 static int run(const std::string& text, const std::string& out_path, size_t p, size_t ctx, bool pretty, const std::vector<int>& devices,
-               const std::string& bwt_path)
+               const std::string& bwt_path, const std::string& fm_path = std::string(), uint32_t fm_sample = 32)
 {
     if (p > std::numeric_limits<idx_t>::max()) { std::cerr << "subproblem-count does not fit the index type\n"; return EXIT_FAILURE; }
     // the bounded-context mode replays the reference's merge history, one GPU thread per merge node -- the top levels
@@ -72,7 +79,7 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
                   << " seconds for " << (text.size() >> 20) << " Mi chars; the unbounded construction takes milliseconds.\n";
     CaPS_SA::Suffix_Array<idx_t> suf_arr(text.c_str(), static_cast<idx_t>(text.size()), static_cast<idx_t>(p),
                                          static_cast<idx_t>(ctx >= text.size() ? 0 : ctx), devices);
-    if (bwt_path.empty()) suf_arr.construct();
+    if (bwt_path.empty() && fm_path.empty()) suf_arr.construct();
     else suf_arr.construct_bwt();
     const caps_sa_stats& st = suf_arr.stats();
     std::cerr << "Constructed the suffix array. Device time: " << st.ms_total / 1e3 << " seconds (h2d "
@@ -95,6 +102,52 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
         bwt.write(reinterpret_cast<const char*>(&primary), sizeof primary);
         bwt.write(reinterpret_cast<const char*>(suf_arr.BWT()), static_cast<std::streamsize>(n));
         if (!bwt) return EXIT_FAILURE;
+    }
+    if (!fm_path.empty()) {
+        const CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::build<idx_t>(suf_arr.BWT(), suf_arr.n(), suf_arr.primary(), suf_arr.SA(), fm_sample);
+        fm.save(fm_path);
+        std::cerr << "FM-index: " << fm.size() << " bytes, SA samples every " << fm_sample << " positions.\n";
+    }
+    return 0;
+}
+
+// caps_sa --fm-search INDEX PATTERNS [--locate K]: args = everything after the program name
+static int fm_search_main(const std::vector<std::string>& args)
+{
+    const char* usage = "--fm-search: usage: caps_sa --fm-search INDEX PATTERNS [--locate K] (no other option or argument)\n";
+    if (args.size() < 3 || args[0] != "--fm-search" || (args.size() != 3 && args.size() != 5)) { std::cerr << usage; return EXIT_FAILURE; }
+    size_t k = 0;
+    const bool locate = args.size() == 5;
+    if (locate && (args[3] != "--locate" || !parse_count(args[4], k) || k < 1)) { std::cerr << usage; return EXIT_FAILURE; }
+    if (args[1].compare(0, 2, "--") == 0 || args[2].compare(0, 2, "--") == 0) { std::cerr << usage; return EXIT_FAILURE; }
+    std::string lines;
+    if (!read_input(args[2], lines)) return EXIT_FAILURE;
+    try {
+        const CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::load(args[1]);
+        static const char lookup[4] = {'A', 'C', 'T', 'G'};
+        std::string pats;
+        std::vector<uint64_t> off(1, 0);
+        for (size_t a = 0; a < lines.size();) {
+            size_t b = lines.find('\n', a);
+            if (b == std::string::npos) b = lines.size();
+            size_t e = b;
+            if (e > a && lines[e - 1] == '\r') --e;
+            for (size_t j = a; j < e; ++j) pats.push_back(lookup[(std::toupper(static_cast<unsigned char>(lines[j])) & 0x6) >> 1]);
+            off.push_back(pats.size());
+            a = b + 1;
+        }
+        std::vector<uint64_t> first, cnt, out_off, pos;
+        fm.count(pats, off, first, cnt);
+        if (locate) fm.locate(first, cnt, k, out_off, pos);
+        for (size_t j = 0; j + 1 < off.size(); ++j) {
+            std::cout << cnt[j];
+            if (locate)
+                for (uint64_t t = out_off[j]; t < out_off[j + 1]; ++t) std::cout << ' ' << pos[t];
+            std::cout << '\n';
+        }
+    } catch (const std::exception& e) {
+        std::cerr << e.what() << "\n";
+        return EXIT_FAILURE;
     }
     return 0;
 }
@@ -147,24 +200,40 @@ int main(int argc, char* argv[])
 {
     for (int i = 1; i < argc; ++i)
         if (std::strcmp(argv[i], "--inverse-bwt") == 0) return inverse_bwt_main(std::vector<std::string>(argv + 1, argv + argc));
+    for (int i = 1; i < argc; ++i)
+        if (std::strcmp(argv[i], "--fm-search") == 0) return fm_search_main(std::vector<std::string>(argv + 1, argv + argc));
     std::vector<std::string> pos;
-    bool pretty = false, bwt = false;
-    size_t gpus = 1;
-    std::string bwt_path;
+    bool pretty = false, bwt = false, fm = false, fm_sample_given = false;
+    size_t gpus = 1, fm_sample = 32;
+    std::string bwt_path, fm_path;
     for (int i = 1; i < argc; ++i) {
         if (std::strcmp(argv[i], "--pretty-print") == 0) pretty = true;
         else if (std::strcmp(argv[i], "--bwt") == 0) {
             bwt = true;
             if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) bwt_path = argv[++i];
         }
+        else if (std::strcmp(argv[i], "--fm-index") == 0) {
+            fm = true;
+            if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) fm_path = argv[++i];
+        }
+        else if (std::strcmp(argv[i], "--fm-sample") == 0) {
+            fm_sample_given = true;
+            if (i + 1 >= argc || !parse_count(argv[++i], fm_sample) || fm_sample < 1 || fm_sample > 1024 || (fm_sample & (fm_sample - 1))) {
+                std::cerr << "--fm-sample: a power of two in 1 .. 1024, please\n";
+                return EXIT_FAILURE;
+            }
+        }
+        else if (std::strcmp(argv[i], "--locate") == 0) { std::cerr << "--locate: only with --fm-search\n"; return EXIT_FAILURE; }
         else if (std::strcmp(argv[i], "--gpus") == 0 && i + 1 < argc) {
             if (!parse_count(argv[++i], gpus) || gpus < 1 || gpus > 64) { std::cerr << "--gpus: a device count, please\n"; return EXIT_FAILURE; }
         } else pos.push_back(argv[i]);
     }
     if (pos.size() < 2) {
         std::cerr << "Usage: caps_sa <input_path> <output_path> <(optional)-subproblem-count> "
-                     "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH>\n"
-                     "       caps_sa --inverse-bwt IN.bwt OUT\n";
+                     "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH> "
+                     "<(optional)--fm-index PATH [--fm-sample S]>\n"
+                     "       caps_sa --inverse-bwt IN.bwt OUT\n"
+                     "       caps_sa --fm-search INDEX PATTERNS [--locate K]\n";
         return EXIT_FAILURE;
     }
     size_t p = 0, ctx = 0;
@@ -177,6 +246,17 @@ int main(int argc, char* argv[])
         struct stat sb;                                       // (an input that cannot be stat'ed is reported by read_input below)
         if (ctx != 0 && stat(pos[0].c_str(), &sb) == 0 && ctx < static_cast<size_t>(sb.st_size)) {
             std::cerr << "--bwt: a bounded-context order (bounded-context " << ctx << ") is not a suffix array and has no BWT\n";
+            return EXIT_FAILURE;
+        }
+    }
+    // --fm-index: the same manners
+    if (fm_sample_given && !fm) { std::cerr << "--fm-sample: only with --fm-index PATH\n"; return EXIT_FAILURE; }
+    if (fm) {
+        if (fm_path.empty()) { std::cerr << "--fm-index: missing output path (--fm-index PATH)\n"; return EXIT_FAILURE; }
+        if (gpus > 1) { std::cerr << "--fm-index: the index is built on one GPU; --gpus " << gpus << " has no BWT to build it from\n"; return EXIT_FAILURE; }
+        struct stat sb;
+        if (ctx != 0 && stat(pos[0].c_str(), &sb) == 0 && ctx < static_cast<size_t>(sb.st_size)) {
+            std::cerr << "--fm-index: a bounded-context order (bounded-context " << ctx << ") is not a suffix array and has no FM-index\n";
             return EXIT_FAILURE;
         }
     }
@@ -202,8 +282,8 @@ int main(int argc, char* argv[])
 
     std::cerr << "Text length: " << text.size() << ".\n";
     try {
-        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path);
-        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path);
+        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample);
+        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample);
     } catch (const std::exception& e) {
         std::cerr << e.what() << "\n";
         return EXIT_FAILURE;

@@ -5104,4 +5104,475 @@ GLOBAL_FN LAUNCH_BOUNDS(IBWT_NT) ibwt_top_kernel(KCTX const idx_t* __restrict__ 
     PAR(tid) { for (uint32_t k = tid; k < M; k += IBWT_NT) off[k] = o[k]; }
 }
 
+// ---- FM-index over (BWT, primary) (capi_impl.h fm_*; include/caps_sa_hip.h "FM-index") ------------------------------------------
+// Rows and L as in the inverse BWT above.  The alphabet has at most 4 bytes, coded 0 .. sigma - 1 in signed-char order; the '$' row
+// stores code 0 and Occ(0, r) gives one back for r > primary + 1.  The Occ section is an array of blocks of ROWS rows, one aligned
+// block = the 4 absolute counts (idx_t: symbols of each code in the rows before the block), the rows' 2-bit codes (row j of a
+// word at bits 2j) and one "this row's SA value is sampled" bit per row:
+//   _u32   64 B per 128 rows: counts 16 B | codes 32 B | marks 16 B        _u64  128 B per 256 rows: 32 B | 64 B | 32 B
+// so Occ(c, r), the code of row r and its mark are ONE block: a step of a query is one line.  C[c] = the first row whose rotation
+// starts with code c (C[0] = 1: row 0 starts with '$'), C[4] = n + 1.  Samples: the SA values that are multiples of s, in row
+// order; the sample of a marked row = samples[mrank[block] + marks below the row in its block].
+// The query kernels take the header's fields by value (FmView: validated on the host) and compare every row, block and sample
+// index with its section's size before it becomes an address: whatever the body holds, they read inside the blob and end.
+constexpr uint32_t FM_NT = 256;                // threads of every FM kernel
+constexpr uint32_t FM_WROWS = 16;              // rows of a code word
+constexpr uint32_t FM_ROUNDS = 4;              // code words per thread and tile
+constexpr uint64_t FM_TILE = (uint64_t)FM_NT * FM_WROWS * FM_ROUNDS;      // rows of a tile: 16,384 (a whole number of blocks)
+constexpr uint32_t FM_MROWS = 32, FM_MROUNDS = 2;                         // mark pass: rows per thread (one mark word), rounds per tile
+constexpr uint32_t FM_KEYS = 5;                // columns of the tile counts: the 4 codes, the marks
+constexpr uint32_t FM_MAX_SAMPLE = 1024;
+template <typename idx_t> struct FmGeom {
+    static constexpr uint32_t ROWS = sizeof(idx_t) == 4 ? 128u : 256u;    // rows of a block
+    static constexpr uint32_t BW = ROWS / 8;                              // 32-bit words of a block (16 / 32)
+    static constexpr uint32_t CW0 = sizeof(idx_t);                        // first code word (behind 4 counts of idx_t)
+    static constexpr uint32_t CWN = ROWS / 16;                            // code words
+    static constexpr uint32_t MW0 = CW0 + CWN;                            // first mark word
+    static constexpr uint32_t MWN = ROWS / 32;                            // mark words
+};
+struct FmView {
+    uint64_t n, primary;
+    uint64_t C[5];
+    uint64_t n_blocks, n_samples;
+    const uint32_t* occ;
+    const void* mrank;                         // idx_t[n_blocks]
+    const void* samples;                       // idx_t[n_samples]
+    uint32_t sigma, syms, s;                   // syms: byte k = the letter of code k
+};
+
+// the code of byte b under the alphabet (syms, sigma): the number of letters below it in signed-char order (b need not be a letter)
+HD uint32_t fm_code_of(uint32_t syms, uint32_t sigma, uint32_t b)
+{
+    const uint32_t kb = b ^ 0x80u;
+    uint32_t c = 0;
+    UNROLL
+    for (uint32_t k = 1; k < 4; ++k) c += (k < sigma && kb >= (((syms >> (8u * k)) & 0xFFu) ^ 0x80u)) ? 1u : 0u;
+    return c;
+}
+HD bool fm_is_letter(uint32_t syms, uint32_t sigma, uint32_t b, uint32_t c) { return c < sigma && ((syms >> (8u * c)) & 0xFFu) == b; }
+
+// the code word of rows r0 .. r0 + 15 (r0 a multiple of 16)
+HD uint32_t fm_code_word(const uint8_t* __restrict__ B, uint64_t n, uint64_t primary, uint64_t r0, uint32_t syms, uint32_t sigma)
+{
+    uint32_t w = 0;
+    if (r0 >= FM_WROWS && r0 + FM_WROWS <= n && !(primary + 1 >= r0 && primary + 1 < r0 + FM_WROWS)) {
+        // rows r0 .. r0 + 15 = bytes r0 - 1 .. r0 + 14: the 16 bytes at r0 (any alignment) and the one before them
+        uint32_t x[4];
+        UNROLL
+        for (uint32_t k = 0; k < 4; ++k) x[k] = STREAM_LOAD(reinterpret_cast<const u32_any_align*>(B + r0) + k);
+        uint32_t prev = B[r0 - 1];
+        UNROLL
+        for (uint32_t j = 0; j < FM_WROWS; ++j) {
+            w |= fm_code_of(syms, sigma, prev) << (2u * j);
+            prev = (x[j / 4] >> (8u * (j % 4))) & 0xFFu;
+        }
+    } else {
+        for (uint32_t j = 0; j < FM_WROWS; ++j) {
+            const uint64_t r = r0 + j;
+            if (r > n || r == primary + 1) continue;
+            w |= fm_code_of(syms, sigma, B[r ? r - 1 : primary]) << (2u * j);
+        }
+    }
+    return w;
+}
+// rows of code c among the first `rows` (0 .. 16) rows of a code word
+HD uint32_t fm_word_rank(uint32_t w, uint32_t c, uint32_t rows)
+{
+    const uint32_t x = w ^ (c * 0x55555555u);
+    uint32_t m = ~(x | (x >> 1)) & 0x55555555u;
+    if (rows < FM_WROWS) m &= (1u << (2u * rows)) - 1u;
+    return (uint32_t)__builtin_popcount(m);
+}
+
+// alphabet probe: the set of byte values in B as 256 bits, OR-ed into present[8].  Every lane keeps the set in four 64-bit
+// registers (no LDS traffic per byte: with 4 letters every LDS atomic of a wave would hit one of 4 words).
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_probe_kernel(KCTX const uint8_t* __restrict__ B, uint64_t n, uint32_t* __restrict__ present)
+{
+    SHARED_ARRAY(uint32_t, pm, 8);
+    PAR(tid) { if (tid < 8) pm[tid] = 0; }
+    SYNC();
+    PAR(tid) {
+        uint64_t m[4] = {0, 0, 0, 0};
+        auto add = [&](uint32_t b) {
+            const uint64_t bit = 1ull << (b & 63u);
+            const uint32_t h = b >> 6;
+            m[0] |= h == 0 ? bit : 0; m[1] |= h == 1 ? bit : 0; m[2] |= h == 2 ? bit : 0; m[3] |= h == 3 ? bit : 0;
+        };
+        const uint64_t chunks = (n + 15) / 16, stride = (uint64_t)K_GRID_DIM * FM_NT;
+        for (uint64_t ch = (uint64_t)K_BLOCK_IDX * FM_NT + tid; ch < chunks; ch += stride) {
+            const uint64_t i0 = ch * 16;
+            if (i0 + 16 <= n) {
+                uint32_t x[4];
+                UNROLL
+                for (uint32_t k = 0; k < 4; ++k) x[k] = STREAM_LOAD(reinterpret_cast<const u32_any_align*>(B + i0) + k);
+                UNROLL
+                for (uint32_t j = 0; j < 16; ++j) add((x[j / 4] >> (8u * (j % 4))) & 0xFFu);
+            } else {
+                for (uint64_t i = i0; i < n; ++i) add(B[i]);
+            }
+        }
+        for (uint32_t k = 0; k < 4; ++k) {
+            if ((uint32_t)m[k]) ATOMIC_OR_U32(&pm[2 * k], (uint32_t)m[k]);
+            if ((uint32_t)(m[k] >> 32)) ATOMIC_OR_U32(&pm[2 * k + 1], (uint32_t)(m[k] >> 32));
+        }
+    }
+    SYNC();
+    PAR(tid) { if (tid < 8 && pm[tid]) ATOMIC_OR_U32(&present[tid], pm[tid]); }
+}
+
+// per tile of FM_TILE rows: the rows of each code -> cnt[code * n_tiles + tile] (the '$' row and the rows behind n count as code 0:
+// they are stored so)
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_tile_count_kernel(KCTX const uint8_t* __restrict__ B, uint64_t n, uint64_t primary, uint64_t n_tiles,
+                                                     uint32_t syms, uint32_t sigma, uint64_t* __restrict__ cnt)
+{
+    SHARED_ARRAY(uint32_t, h, 4);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        PAR(tid) { if (tid < 4) h[tid] = 0; }
+        SYNC();
+        PAR(tid) {
+            uint32_t c[4] = {0, 0, 0, 0};
+            for (uint32_t j = 0; j < FM_ROUNDS; ++j) {
+                const uint64_t r0 = tile * FM_TILE + ((uint64_t)j * FM_NT + tid) * FM_WROWS;
+                const uint32_t w = fm_code_word(B, n, primary, r0, syms, sigma);
+                UNROLL
+                for (uint32_t k = 0; k < 4; ++k) c[k] += fm_word_rank(w, k, FM_WROWS);
+            }
+            for (uint32_t k = 0; k < 4; ++k) if (c[k]) FETCH_ADD_U32(&h[k], c[k]);
+        }
+        SYNC();
+        PAR(tid) { if (tid < 4) cnt[(uint64_t)tid * n_tiles + tile] = h[tid]; }
+        SYNC();
+    }
+}
+
+// one workgroup per column: cnt[key][tile] -> the exclusive prefix over the tiles, in place; total[key] (ibwt_scan_kernel's pattern)
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_scan_kernel(KCTX uint64_t* __restrict__ cnt, uint64_t n_tiles, uint32_t key0, uint32_t keys,
+                                               uint64_t* __restrict__ total)
+{
+    SHARED_ARRAY(uint64_t, part, FM_NT);
+    const uint64_t per = (n_tiles + FM_NT - 1) / FM_NT;
+    for (uint32_t key = key0 + K_BLOCK_IDX; key < key0 + keys; key += K_GRID_DIM) { // block-uniform
+        uint64_t* col = cnt + (uint64_t)key * n_tiles;
+        PAR(tid) {
+            const uint64_t a = std::min<uint64_t>(n_tiles, tid * per), b = std::min<uint64_t>(n_tiles, a + per);
+            uint64_t s = 0;
+            for (uint64_t k = a; k < b; ++k) s += col[k];
+            part[tid] = s;
+        }
+        SYNC();
+        PAR(tid) {
+            if (tid == 0) {
+                uint64_t s = 0;
+                for (uint32_t k = 0; k < FM_NT; ++k) { const uint64_t v = part[k]; part[k] = s; s += v; }
+                total[key] = s;
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            const uint64_t a = std::min<uint64_t>(n_tiles, tid * per), b = std::min<uint64_t>(n_tiles, a + per);
+            uint64_t s = part[tid];
+            for (uint64_t k = a; k < b; ++k) { const uint64_t v = col[k]; col[k] = s; s += v; }
+        }
+        SYNC();
+    }
+}
+
+// the pack pass: the blocks of every tile.  A round is FM_NT code words = FM_NT / CWN blocks: every thread makes one word and its 4
+// counts, the first thread of a block sums its block's, four threads scan the blocks of the round (one code each), then the words
+// and the absolute counts go out; the mark words are zeroed here (fm_mark_kernel sets them when there is an SA).
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_pack_kernel(KCTX const uint8_t* __restrict__ B, uint64_t n, uint64_t primary, uint64_t n_tiles,
+                                               uint64_t n_blocks, uint32_t syms, uint32_t sigma, const uint64_t* __restrict__ pre,
+                                               uint32_t* __restrict__ occ)
+{
+    using G = FmGeom<idx_t>;
+    constexpr uint32_t BPR = FM_NT / G::CWN;      // blocks of a round
+    SHARED_ARRAY(uint32_t, tc, 4 * FM_NT);        // [code][thread]
+    SHARED_ARRAY(uint64_t, bc, 4 * BPR);          // [code][block of the round]: the sum, then the absolute count before the block
+    SHARED_ARRAY(uint64_t, run, 4);
+    TL_DECL(uint32_t, wd, 1);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        PAR(tid) { if (tid < 4) run[tid] = pre[(uint64_t)tid * n_tiles + tile]; }
+        SYNC();
+        for (uint32_t j = 0; j < FM_ROUNDS; ++j) {
+            const uint64_t w0 = (tile * FM_ROUNDS + j) * FM_NT;                     // first code word of the round
+            PAR(tid) {
+                const uint32_t w = fm_code_word(B, n, primary, (w0 + tid) * FM_WROWS, syms, sigma);
+                TL(wd, tid, 0) = w;
+                UNROLL
+                for (uint32_t k = 0; k < 4; ++k) tc[k * FM_NT + tid] = fm_word_rank(w, k, FM_WROWS);
+            }
+            SYNC();
+            PAR(tid) {
+                if (tid % G::CWN == 0) {
+                    for (uint32_t k = 0; k < 4; ++k) {
+                        uint32_t s = 0;
+                        for (uint32_t i = 0; i < G::CWN; ++i) s += tc[k * FM_NT + tid + i];
+                        bc[k * BPR + tid / G::CWN] = s;
+                    }
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                if (tid < 4) {
+                    uint64_t s = run[tid];
+                    for (uint32_t i = 0; i < BPR; ++i) { const uint64_t v = bc[tid * BPR + i]; bc[tid * BPR + i] = s; s += v; }
+                    run[tid] = s;
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                const uint64_t blk = (w0 + tid) / G::CWN;
+                if (blk < n_blocks) {
+                    uint32_t* p = occ + blk * G::BW;
+                    p[G::CW0 + tid % G::CWN] = TL(wd, tid, 0);
+                    if (tid % G::CWN == 0) {
+                        for (uint32_t k = 0; k < 4; ++k) reinterpret_cast<idx_t*>(p)[k] = (idx_t)bc[k * BPR + tid / G::CWN];
+                        for (uint32_t k = 0; k < G::MWN; ++k) p[G::MW0 + k] = 0;
+                    }
+                }
+            }
+            SYNC();
+        }
+    }
+}
+
+// the mark word of rows r0 .. r0 + 31 (row k + 1 is SA rank k): bit j = SA[r0 + j - 1] is a multiple of s
+template <typename idx_t>
+HD uint32_t fm_mark_word(const idx_t* __restrict__ SA, uint64_t n, uint64_t r0, uint32_t s)
+{
+    uint32_t m = 0;
+    if (r0 >= 1 && r0 + FM_MROWS <= n + 1) {
+        UNROLL
+        for (uint32_t j = 0; j < FM_MROWS; ++j) m |= (((uint64_t)STREAM_LOAD(&SA[r0 + j - 1]) & (s - 1u)) == 0 ? 1u : 0u) << j;
+    } else {
+        for (uint32_t j = 0; j < FM_MROWS; ++j) {
+            const uint64_t r = r0 + j;
+            if (r >= 1 && r <= n && ((uint64_t)SA[r - 1] & (s - 1u)) == 0) m |= 1u << j;
+        }
+    }
+    return m;
+}
+
+// the mark pass: the mark words of every block, mrank[block] = the marks before the block IN ITS TILE, cnt[4][tile] = the tile's marks
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_mark_kernel(KCTX const idx_t* __restrict__ SA, uint64_t n, uint64_t n_tiles, uint64_t n_blocks, uint32_t s,
+                                               uint32_t* __restrict__ occ, idx_t* __restrict__ mrank, uint64_t* __restrict__ cnt)
+{
+    using G = FmGeom<idx_t>;
+    constexpr uint32_t BPR = FM_NT / G::MWN;
+    SHARED_ARRAY(uint32_t, tc, FM_NT);
+    SHARED_ARRAY(uint32_t, bc, BPR);
+    SHARED_ARRAY(uint32_t, run, 1);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        PAR(tid) { if (tid == 0) run[0] = 0; }
+        SYNC();
+        for (uint32_t j = 0; j < FM_MROUNDS; ++j) {
+            const uint64_t w0 = (tile * FM_MROUNDS + j) * FM_NT;                    // first mark word of the round
+            PAR(tid) {
+                const uint32_t m = fm_mark_word<idx_t>(SA, n, (w0 + tid) * FM_MROWS, s);
+                const uint64_t blk = (w0 + tid) / G::MWN;
+                if (blk < n_blocks) occ[blk * G::BW + G::MW0 + tid % G::MWN] = m;
+                tc[tid] = (uint32_t)__builtin_popcount(m);
+            }
+            SYNC();
+            PAR(tid) {
+                if (tid == 0) {
+                    uint32_t sum = run[0];
+                    for (uint32_t b = 0; b < BPR; ++b) {
+                        bc[b] = sum;
+                        for (uint32_t i = 0; i < G::MWN; ++i) sum += tc[b * G::MWN + i];
+                    }
+                    run[0] = sum;
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                const uint64_t blk = (w0 + tid) / G::MWN;
+                if (tid % G::MWN == 0 && blk < n_blocks) mrank[blk] = (idx_t)bc[tid / G::MWN];
+            }
+            SYNC();
+        }
+        PAR(tid) { if (tid == 0) cnt[4 * n_tiles + tile] = run[0]; }
+        SYNC();
+    }
+}
+
+// sample compaction in row order: the marked rows' SA values to samples[pre[tile] + mrank[block] + marks below in the block], and
+// mrank[block] made absolute.  An index at or beyond cap (an SA that is no permutation marks too many rows) is not written.
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_sample_kernel(KCTX const idx_t* __restrict__ SA, uint64_t n, uint64_t n_tiles, uint64_t n_blocks, uint32_t s,
+                                                 const uint32_t* __restrict__ occ, idx_t* __restrict__ mrank, const uint64_t* __restrict__ pre,
+                                                 idx_t* __restrict__ samples, uint64_t cap)
+{
+    using G = FmGeom<idx_t>;
+    TL_DECL(uint64_t, at, 1);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t base = pre[4 * n_tiles + tile];
+        for (uint32_t j = 0; j < FM_MROUNDS; ++j) {
+            const uint64_t w0 = (tile * FM_MROUNDS + j) * FM_NT;
+            PAR(tid) {
+                const uint64_t blk = (w0 + tid) / G::MWN;
+                uint64_t a = ~0ull;
+                if (blk < n_blocks) {
+                    a = base + (uint64_t)mrank[blk];
+                    for (uint32_t i = 0; i < tid % G::MWN; ++i) a += (uint32_t)__builtin_popcount(occ[blk * G::BW + G::MW0 + i]);
+                }
+                TL(at, tid, 0) = a;
+            }
+            SYNC();
+            PAR(tid) {
+                const uint64_t blk = (w0 + tid) / G::MWN, r0 = (w0 + tid) * FM_MROWS;
+                if (blk < n_blocks) {
+                    uint64_t a = TL(at, tid, 0);
+                    uint32_t m = occ[blk * G::BW + G::MW0 + tid % G::MWN];
+                    while (m) {
+                        const uint32_t b = (uint32_t)__builtin_ctz(m);
+                        m &= m - 1;
+                        const uint64_t r = r0 + b;
+                        if (a < cap && r >= 1 && r <= n) samples[a] = SA[r - 1];
+                        ++a;
+                    }
+                    if (tid % G::MWN == 0) mrank[blk] = (idx_t)(base + (uint64_t)mrank[blk]);
+                }
+            }
+            SYNC();
+        }
+    }
+}
+
+// Occ(c, r) + the '$' correction from the block p of row r; k = r mod ROWS.  The count is read at its (dynamic) place, the code words
+// at fixed offsets: one line, no indexed register array.
+template <typename idx_t>
+HD uint64_t fm_block_occ(const uint32_t* __restrict__ p, uint32_t c, uint32_t k, bool past_dollar)
+{
+    using G = FmGeom<idx_t>;
+    uint64_t cnt = (uint64_t)reinterpret_cast<const idx_t*>(p)[c];
+    uint32_t w[G::CWN];
+    UNROLL
+    for (uint32_t i = 0; i < G::CWN; ++i) w[i] = p[G::CW0 + i];
+    UNROLL
+    for (uint32_t i = 0; i < G::CWN; ++i) {
+        const uint32_t rows = k > i * FM_WROWS ? (k - i * FM_WROWS < FM_WROWS ? k - i * FM_WROWS : FM_WROWS) : 0u;
+        cnt += fm_word_rank(w[i], c, rows);
+    }
+    if (c == 0 && past_dollar) --cnt;
+    return cnt;
+}
+// C[c] by selects (c differs from lane to lane: no indexed read of the kernel's arguments)
+HD uint64_t fm_c_of(const FmView& v, uint32_t c) { return c == 0 ? v.C[0] : c == 1 ? v.C[1] : c == 2 ? v.C[2] : v.C[3]; }
+// the block of row r, inside the Occ section whatever r is
+template <typename idx_t>
+HD const uint32_t* fm_block_of(const FmView& v, uint64_t r)
+{
+    using G = FmGeom<idx_t>;
+    uint64_t b = r / G::ROWS;
+    if (b >= v.n_blocks) b = v.n_blocks - 1;      // (never for r <= n + 1: n_blocks = (n + 1) / ROWS + 1)
+    return v.occ + b * G::BW;
+}
+// row r (<= n + 1) -> C[c] + Occ(c, r), kept inside 0 .. n + 1
+template <typename idx_t>
+HD uint64_t fm_lf(const FmView& v, uint32_t c, uint64_t r)
+{
+    using G = FmGeom<idx_t>;
+    const uint64_t x = fm_c_of(v, c) + fm_block_occ<idx_t>(fm_block_of<idx_t>(v, r), c, (uint32_t)(r % G::ROWS), r > v.primary + 1);
+    return x <= v.n + 1 ? x : v.n + 1;
+}
+
+// count: one lane per pattern, backward search from the last byte; first[j] = the SA rank of the first occurrence, count[j]
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_count_kernel(KCTX FmView v, const uint8_t* __restrict__ pat, const uint64_t* __restrict__ patoff, uint64_t q,
+                                                uint64_t* __restrict__ first, uint64_t* __restrict__ count)
+{
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t j0 = (uint64_t)K_BLOCK_IDX * FM_NT; j0 < q; j0 += stride) {       // block-uniform
+        PAR(tid) {
+            const uint64_t j = j0 + tid;
+            if (j < q) {
+                const uint64_t a = patoff[j], b = patoff[j + 1], m = b > a ? b - a : 0;
+                uint64_t lo = m ? 0 : 1, hi = v.n + 1;                             // every row; without the '$' row for the empty pattern
+                if (m > v.n) hi = lo;
+                for (uint64_t i = m; i > 0 && lo < hi; --i) {
+                    const uint32_t byte = pat[a + i - 1], c = fm_code_of(v.syms, v.sigma, byte);
+                    if (!fm_is_letter(v.syms, v.sigma, byte, c)) { hi = lo; break; }
+                    const uint64_t l2 = fm_lf<idx_t>(v, c, lo), h2 = fm_lf<idx_t>(v, c, hi);     // (independent: issued together)
+                    lo = l2;
+                    hi = h2;
+                }
+                first[j] = lo < hi ? lo - 1 : 0;
+                count[j] = lo < hi ? hi - lo : 0;
+            }
+        }
+    }
+}
+
+// entry checks of the query calls on the caller's device arrays: off[0 .. q] monotone (flag 1), first + count <= n (flag 2)
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_check_kernel(KCTX const uint64_t* __restrict__ off, uint64_t q, const uint64_t* __restrict__ first,
+                                                const uint64_t* __restrict__ count, uint64_t n, uint32_t* __restrict__ flags)
+{
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t j0 = (uint64_t)K_BLOCK_IDX * FM_NT; j0 < q; j0 += stride) {       // block-uniform
+        PAR(tid) {
+            const uint64_t j = j0 + tid;
+            if (j < q) {
+                uint32_t f = off[j + 1] < off[j] ? 1u : 0u;
+                if (first && (first[j] > n || count[j] > n - first[j])) f |= 2u;
+                if (f) ATOMIC_OR_U32(flags, f);
+            }
+        }
+    }
+}
+
+// locate: one lane per output position o in [off[0], off[q]): its query j by bisection over off, rank first[j] + t; LF steps to a
+// marked row or the '$' row, at most s of them.  flags: 4 = a walk did not end (or met a sample index outside the samples).
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_locate_kernel(KCTX FmView v, const uint64_t* __restrict__ first, const uint64_t* __restrict__ count,
+                                                 const uint64_t* __restrict__ off, uint64_t q, uint64_t o_begin, uint64_t o_end,
+                                                 uint64_t* __restrict__ pos, uint32_t* __restrict__ flags)
+{
+    using G = FmGeom<idx_t>;
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t o0 = o_begin + (uint64_t)K_BLOCK_IDX * FM_NT; o0 < o_end; o0 += stride) {     // block-uniform
+        PAR(tid) {
+            const uint64_t o = o0 + tid;
+            if (o < o_end) {
+                uint64_t a = 0, b = q;                                              // the last j with off[j] <= o
+                while (b - a > 1) { const uint64_t mid = a + (b - a) / 2; if (off[mid] <= o) a = mid; else b = mid; }
+                const uint64_t t = o - off[a];
+                if (off[a] <= o && t < count[a] && first[a] + t < v.n) {
+                    uint64_t r = first[a] + t + 1, res = ~0ull;
+                    bool done = false;
+                    for (uint32_t steps = 0; steps <= v.s; ++steps) {
+                        if (r == v.primary + 1) { res = steps; done = true; break; }
+                        const uint32_t* p = fm_block_of<idx_t>(v, r);
+                        const uint32_t k = (uint32_t)(r % G::ROWS);
+                        uint32_t mw[G::MWN];
+                        UNROLL
+                        for (uint32_t i = 0; i < G::MWN; ++i) mw[i] = p[G::MW0 + i];
+                        const uint32_t cw = p[G::CW0 + k / FM_WROWS];
+                        uint32_t below = 0, marked = 0;                             // marks below row k in the block; row k's own
+                        UNROLL
+                        for (uint32_t i = 0; i < G::MWN; ++i) {
+                            const uint32_t rows = k > 32 * i ? (k - 32 * i < 32 ? k - 32 * i : 32) : 0u;
+                            below += (uint32_t)__builtin_popcount(rows < 32 ? mw[i] & ((1u << rows) - 1u) : mw[i]);
+                            if (k / 32 == i) marked = (mw[i] >> (k % 32)) & 1u;
+                        }
+                        if (marked) {
+                            const uint64_t blk = r / G::ROWS;
+                            const uint64_t si = (uint64_t)static_cast<const idx_t*>(v.mrank)[blk < v.n_blocks ? blk : v.n_blocks - 1] + below;
+                            if (si < v.n_samples) { res = (uint64_t)static_cast<const idx_t*>(v.samples)[si] + steps; done = true; }
+                            break;
+                        }
+                        const uint32_t c = (cw >> (2u * (k % FM_WROWS))) & 3u;
+                        const uint64_t x = fm_c_of(v, c) + fm_block_occ<idx_t>(p, c, k, r > v.primary + 1);
+                        r = x <= v.n ? (x ? x : 1) : v.n;                            // (a row of the index: 1 .. n)
+                    }
+                    if (!done) { ATOMIC_OR_U32(flags, 4u); res = (uint64_t)(idx_t)~(idx_t)0; }
+                    pos[o] = res;
+                }
+            }
+        }
+    }
+}
+
 }  // namespace caps

@@ -33,7 +33,8 @@ extern "C" {
 #define CAPS_SA_EHIP (-3)         /* HIP runtime error; see caps_sa_hip_last_error() */
 #define CAPS_SA_ENOMEM (-4)       /* device or host allocation failed */
 #define CAPS_SA_ENODEVICE (-5)    /* no usable GPU */
-#define CAPS_SA_EALPHABET (-6)    /* the workspace was sized for a 2-bit text (caps_sa_hip_workspace_bytes_ex), the text has more than 4 bytes */
+#define CAPS_SA_EALPHABET (-6)    /* the workspace was sized for a 2-bit text (caps_sa_hip_workspace_bytes_ex), the text has more than 4 bytes;
+                                     caps_sa_hip_fm_build_*: the BWT has more than 4 distinct bytes */
 
 /* Per-build record; replaces the per-phase stderr lines of construct()
  * (src/Suffix_Array.cpp:469-493).  Times are HIP-event milliseconds on the build's stream. */
@@ -281,6 +282,73 @@ int caps_sa_hip_inverse_bwt_device_u64(const void* dBWT, uint64_t n, uint64_t pr
  * restores the caller's current device. */
 int caps_sa_hip_inverse_bwt_u32(const uint8_t* BWT, uint64_t n, uint64_t primary, char* T, int device);
 int caps_sa_hip_inverse_bwt_u64(const uint8_t* BWT, uint64_t n, uint64_t primary, char* T, int device);
+
+/* ---- FM-index over (BWT, primary): batched count and locate ---------------------------
+ *
+ * A self-index built from what the build emits, in the row convention of the inverse BWT above (rows 0 .. n of the sorted
+ * rotations of T.$, L[0] = BWT[primary], L[primary + 1] = '$', row r >= 1 is SA rank r - 1). It answers "how often does P occur
+ * in T" with neither the SA nor the text resident, and "where" from a sparse sample of the SA.
+ *
+ * Alphabet: at most 4 distinct byte values in the BWT (any bytes, >= 0x80 included), coded 0 .. sigma - 1 in signed-char order --
+ * the condition under which the build packs the text to 2 bits. More than 4: CAPS_SA_EALPHABET, decided on the device, nothing
+ * written. (A wider alphabet needs another rank structure -- a wavelet tree over the codes -- and is out of scope.)
+ *
+ * The index is ONE relocatable blob without pointers: copy it device <-> host or write it to a file as it is.
+ *   header    256 bytes: magic, format version, n, primary, index width, sigma and the byte values, C[0 .. 4], sa_sample, number of
+ *             samples, number of blocks, section offsets, total bytes
+ *   Occ       one aligned block per 128 rows (_u32: 64 bytes = 4 x u32 counts | 32 B of 2-bit codes | 16 B of mark bits) or per
+ *             256 rows (_u64: 128 bytes = 4 x u64 | 64 B | 32 B): Occ(c, r), the code of a row and its mark touch one block
+ *   samples   (only with an SA at build time) per block the number of marked rows before it, then the SA values that are
+ *             multiples of sa_sample (a power of two, 1 .. 1024) in row order: sampling by TEXT position bounds every locate
+ *             walk by sa_sample LF steps
+ * caps_sa_hip_fm_index_bytes(n, 32, 4) = 0.66 n, (n, 32, 8) = 0.78 n, (n, 0, 4) = 0.5 n bytes (+ the header).
+ *
+ * count: for pattern j = dPatterns[dPatOff[j] .. dPatOff[j + 1]) the occurrences of P in T are exactly SA[first .. first + count)
+ * of the library's SA. count == 0 => first == 0 (a byte outside the alphabet included). Empty pattern: first = 0, count = n. A
+ * pattern longer than n: 0.
+ * locate: for query j and t < min(dCount[j], dOutOff[j + 1] - dOutOff[j]): dPos[dOutOff[j] + t] = SA[dFirst[j] + t] -- SA order,
+ * comparable with the SA entry by entry; a caller that wants at most k hits per query sizes the offsets so. Other slots of dPos
+ * are not written by the device form and come back as UINT64_MAX from the host form. An index built without an SA counts, and
+ * answers locate with CAPS_SA_EUNSUPPORTED.
+ *
+ * Errors: the header is read back and checked on the HOST (magic, version, width, primary < n for n >= 1, C[], section offsets
+ * and total against index_bytes) before any kernel reads the body: anything wrong is CAPS_SA_EINVAL with a message in
+ * caps_sa_hip_last_error(). Non-monotone dPatOff / dOutOff, first + count > n, a null pointer with q > 0: CAPS_SA_EINVAL. n = 0:
+ * the build succeeds and every count is 0. n > UINT32_MAX with _u32: CAPS_SA_EINVAL before any allocation. The kernels compare
+ * every row, block and sample index with its section's size before it is used: for any body they read inside the blob and
+ * terminate (count: at most one step per pattern byte; locate: at most sa_sample steps). A locate walk that does not end within
+ * sa_sample steps means the blob is not an index this library built: CAPS_SA_EINVAL, the message says so, dPos unspecified.
+ */
+
+/* Size of the index of n symbols: sa_sample = 0 for an index without samples, idx_bytes = 4 (_u32) or 8 (_u64). */
+int caps_sa_hip_fm_index_bytes(uint64_t n, uint32_t sa_sample, int idx_bytes, uint64_t* bytes);
+/* dBWT (n bytes), dSA (NULL: no samples, sa_sample ignored; else the WHOLE suffix array, n entries of the index width) and dIndex
+ * (index_bytes >= caps_sa_hip_fm_index_bytes, written; 64-byte aligned) are device pointers on the current device; the work runs
+ * on hip_stream and has completed on return. An SA whose multiples of sa_sample are not (n - 1) / sa_sample + 1: CAPS_SA_EINVAL. */
+int caps_sa_hip_fm_build_device_u32(const void* dBWT, uint64_t n, uint64_t primary, const void* dSA, uint32_t sa_sample,
+                                    void* dIndex, uint64_t index_bytes, void* hip_stream);
+int caps_sa_hip_fm_build_device_u64(const void* dBWT, uint64_t n, uint64_t primary, const void* dSA, uint32_t sa_sample,
+                                    void* dIndex, uint64_t index_bytes, void* hip_stream);
+/* Host buffers: BWT and SA (or NULL) up, the index built on `device` and downloaded into `index`. Runs on the device block of the
+ * host-buffer builds (calls serialised on it, the caller's current device restored); the index stays there for the host queries. */
+int caps_sa_hip_fm_build_u32(const uint8_t* BWT, uint64_t n, uint64_t primary, const uint32_t* SA, uint32_t sa_sample,
+                             void* index, uint64_t index_bytes, int device);
+int caps_sa_hip_fm_build_u64(const uint8_t* BWT, uint64_t n, uint64_t primary, const uint64_t* SA, uint32_t sa_sample,
+                             void* index, uint64_t index_bytes, int device);
+/* dPatOff: u64[q + 1], dFirst / dCount: u64[q] (written), all on the current device; the index width comes from the header. */
+int caps_sa_hip_fm_count_device(const void* dIndex, uint64_t index_bytes, const void* dPatterns, const void* dPatOff, uint64_t q,
+                                void* dFirst, void* dCount, void* hip_stream);
+/* dFirst / dCount: u64[q] (e.g. what count wrote), dOutOff: u64[q + 1], dPos: u64[dOutOff[q]] (written). */
+int caps_sa_hip_fm_locate_device(const void* dIndex, uint64_t index_bytes, const void* dFirst, const void* dCount,
+                                 const void* dOutOff, uint64_t q, void* dPos, void* hip_stream);
+/* The same on host buffers, the index in host memory: it is uploaded to the device block of the host-buffer builds (calls
+ * serialised on it, the caller's current device restored), and an index already uploaded is not uploaded again. "Already
+ * uploaded" = same address, size, header and the same sum over a stride of the body: a caller that rewrites a blob in place
+ * calls caps_sa_hip_release_cache() before it queries again. */
+int caps_sa_hip_fm_count(const void* index, uint64_t index_bytes, const uint8_t* patterns, const uint64_t* pat_off, uint64_t q,
+                         uint64_t* first, uint64_t* count, int device);
+int caps_sa_hip_fm_locate(const void* index, uint64_t index_bytes, const uint64_t* first, const uint64_t* count,
+                          const uint64_t* out_off, uint64_t q, uint64_t* pos, int device);
 
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
