@@ -303,6 +303,39 @@ int caps_sa_hip_inverse_bwt_u64(const uint8_t* BWT, uint64_t n, uint64_t primary
  *             walk by sa_sample LF steps
  * caps_sa_hip_fm_index_bytes(n, 32, 4) = 0.66 n, (n, 32, 8) = 0.78 n, (n, 0, 4) = 0.5 n bytes (+ the header).
  *
+ * The blob, byte by byte (format version 1; every number little-endian). W = the index width in bytes (4 or 8), ROWS = 128 for
+ * W = 4 and 256 for W = 8. The header is 32 64-bit words:
+ *   word  0        magic: the 8 bytes "CAPSFMI1" (0x31494D4653504143)
+ *   word  1        format version = 1
+ *   word  2        n
+ *   word  3        primary (0 when n = 0)
+ *   word  4        W
+ *   word  5        sigma: the number of distinct bytes of the BWT (0 when n = 0)
+ *   word  6        the letters, one per byte in code order: bits 8c .. 8c + 7 = the byte of code c, c < sigma; other bytes 0
+ *   words 7 .. 11  C[0 .. 4]: C[0] = 1, C[c + 1] = C[c] + the number of bytes of the BWT with code c (codes >= sigma: none),
+ *                  so C[4] = n + 1
+ *   word  12       sa_sample (0: no samples)
+ *   word  13       number of samples = (n - 1) / sa_sample + 1, or 0 when sa_sample = 0 or n = 0
+ *   word  14       n_blocks = (n + 1) / ROWS + 1 (integer division): the block of row n + 1 exists
+ *   word  15       offset of the Occ section = 256
+ *   word  16       offset of the mark ranks = 256 + n_blocks * ROWS / 2
+ *   word  17       offset of the samples = word 16 + n_blocks * W rounded up to a multiple of 64 (= word 16 when sa_sample = 0)
+ *   word  18       total = word 17 + (number of samples) * W rounded up to a multiple of 64 (= word 17 when sa_sample = 0)
+ *   words 19 .. 31 zero
+ * Rows: row r of block b = r / ROWS stores a 2-bit code and a mark bit. The STORED code of row 0 is that of BWT[primary], of
+ * row r in 1 .. n that of BWT[r - 1], except that the '$' row primary + 1 and the rows behind n (up to n_blocks * ROWS - 1) store
+ * code 0. The mark of row r in 1 .. n is 1 iff SA[r - 1] is a multiple of sa_sample; row 0, the rows behind n and every row of
+ * an index without samples have mark 0 (the '$' row is SA rank primary, whose SA value 0 is a multiple: its mark is 1).
+ * Block b, ROWS / 2 bytes at offset 256 + b * ROWS / 2:
+ *   4 counts of W bytes: count[c] = the number of rows before the block (rows 0 .. b * ROWS - 1) whose STORED code is c -- the '$'
+ *     row counts as code 0 here; a reader takes it back out of Occ(0, r) for r > primary + 1
+ *   ROWS / 16 code words of 32 bits: word i holds rows b * ROWS + 16 i .. + 15, row j of the word at bits 2j, 2j + 1
+ *   ROWS / 32 mark words of 32 bits: word i holds rows b * ROWS + 32 i .. + 31, row j of the word at bit j
+ * Mark ranks (only with samples): n_blocks numbers of W bytes, mrank[b] = the ABSOLUTE number of marked rows before block b.
+ * Samples (only with samples): the SA values that are multiples of sa_sample, W bytes each, in row order (the order in which
+ * they stand in the SA). The padding that rounds each of these two sections up to 64 bytes is zero: equal inputs give equal
+ * blobs, whatever the memory held before.
+ *
  * count: for pattern j = dPatterns[dPatOff[j] .. dPatOff[j + 1]) the occurrences of P in T are exactly SA[first .. first + count)
  * of the library's SA. count == 0 => first == 0 (a byte outside the alphabet included). Empty pattern: first = 0, count = n. A
  * pattern longer than n: 0.

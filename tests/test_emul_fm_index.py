@@ -324,6 +324,53 @@ def test_other_builds_give_the_same_bytes():
                 assert got[1:] == ref[1:]
 
 
+@pytest.mark.slow
+def test_poison_and_race_builds_at_the_geometry_edges():
+    """FM build, count and locate, build_bwt and bwt_device through the poison-filled build (LDS and registers start as 0xA5,
+    scattered order) and the barrier-race detector, at sizes on a block edge (127, 128), a tile edge of the FM kernels (16,383,
+    16,384) and beyond two tiles (40,001), both widths, s = 1 and 32: the plain build's blobs and answers, and no race."""
+    import ctypes
+    from test_emul_inverse_bwt import _load
+    plain = emul()
+    poison, _ = _load("libcaps_sa_emul_small_poison.so")
+    race, raw = _load("libcaps_sa_emul_small_race.so")
+    raw.caps_sa_emul_races_found.restype = ctypes.c_ulonglong
+    raw.caps_sa_emul_races_reset()
+    rs = np.random.RandomState(29)
+    runs = 0
+    for n in (127, 128, 16_383, 16_384, 40_001):
+        T = rs.choice(DNA, size=n)
+        pats = make_patterns(T, rs)
+        ref = {}
+        for E in (plain, poison, race):
+            for bits in (32, 64):
+                SA, LCP, B, primary, _ = E.build_bwt(T, idx_bits=bits)
+                got = {"sa": SA.astype(np.uint64).tobytes(), "lcp": LCP.astype(np.uint64).tobytes(), "bwt": B.tobytes(), "primary": primary}
+                for first, cnt in ((0, n), (1, n - 1), (primary, 1), (max(primary - 1, 0), 2), (n // 2, 0)):
+                    out = np.full(cnt + 2, 0xA5, dtype=np.uint8)
+                    p = E.bwt_device(T.ctypes.data, n, SA[first:].ctypes.data, first, cnt, out[1:].ctypes.data, idx_bits=bits)
+                    assert out[0] == 0xA5 and out[-1] == 0xA5
+                    got["slice", first, cnt] = (out[1:-1].tobytes(), p)
+                for s in (1, 32):
+                    blob = E.fm_build(B, primary, SA, s, bits)
+                    first, count = E.fm_count(blob, pats)
+                    pos, _ = E.fm_locate(blob, first, count)
+                    got["fm", s] = (blob.tobytes(), first.tobytes(), count.tobytes(), pos.tobytes())
+                    if E is plain and bits == 32 and s == 1:
+                        check_answers(T, SA, pats, first, count)
+                        out_off = np.concatenate([[0], np.cumsum(count.astype(np.int64))])
+                        check_locate(SA, first, count, [pos[out_off[j]:out_off[j + 1]] for j in range(len(pats))])
+                    runs += 1
+                if E is plain:
+                    ref[bits] = got
+                    assert got["bwt"] == _bwt_of(T, SA)[0].tobytes() and primary == _bwt_of(T, SA)[1]
+                assert got.keys() == ref[bits].keys()
+                for key in got:
+                    assert got[key] == ref[bits][key], (n, bits, key)
+    assert runs == 5 * 3 * 2 * 2
+    assert int(raw.caps_sa_emul_races_found()) == 0
+
+
 ANY_BLOB_CHILD = r"""
 import sys
 import numpy as np
