@@ -919,11 +919,10 @@ int build_multi(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context,
 
 template <typename idx_t>
 int verify_device(const void* dT, uint64_t n, const void* dSA, const void* dLCP, void* stream, uint64_t* n_errors,
-                  uint64_t cnt = ~0ull, uint32_t head = 1)
+                  uint64_t cnt, uint32_t head)
 {
     if (!n_errors) return fail(CAPS_SA_EINVAL, "null n_errors");
     *n_errors = 0;
-    if (cnt == ~0ull) cnt = n;
     if (cnt > n) return fail(CAPS_SA_EINVAL, "more entries than suffixes");
     if (n == 0 || cnt == 0) return CAPS_SA_OK;
     if (!dT || !dSA || !dLCP) return fail(CAPS_SA_EINVAL, "null pointer");
@@ -1949,7 +1948,7 @@ int CAPS_API(workspace_bytes)(uint64_t n, uint64_t subproblem_count, int idx_byt
     { return caps::bwt_device<IDX>(dT, n, dSA, first, cnt, dBWT, stream, primary); }                                       \
     int CAPS_API(verify_device_##SFX)(const void* dT, uint64_t n, const void* dSA, const void* dLCP, void* stream,          \
                                       uint64_t* n_errors)                                                                  \
-    { return caps::verify_device<IDX>(dT, n, dSA, dLCP, stream, n_errors); }                                               \
+    { return caps::verify_device<IDX>(dT, n, dSA, dLCP, stream, n_errors, n, 1u); }                                        \
     int CAPS_API(verify_slice_device_##SFX)(const void* dT, uint64_t n, const void* dSA, const void* dLCP, uint64_t cnt,    \
                                             int is_head, void* stream, uint64_t* n_errors)                                 \
     { return caps::verify_device<IDX>(dT, n, dSA, dLCP, stream, n_errors, cnt, is_head ? 1u : 0u); }                       \

@@ -207,6 +207,19 @@ int caps_sa_hip_build_device_u64(const void* dT, uint64_t n, uint64_t subproblem
  * (src/Suffix_Array.cpp:512-536) plus a permutation check; byte loops on the raw text,
  * independent of the build kernels' packed text.  *n_errors = 0 iff (dSA, dLCP) is the
  * suffix array and LCP array of dT.
+ *
+ * What *n_errors counts (cnt = n and is_head = 1 here; the slice calls below pass their own).  Per entry i < cnt:
+ *   - SA[i] >= n counts 1, and nothing else is counted for that entry.
+ *   - Otherwise:
+ *       - a value already met in this call counts 1 (k copies of a value give k - 1);
+ *       - i == 0: counts 1 if is_head is set and LCP[0] != 0;
+ *       - i > 0 with SA[i-1] < n: counts 1 if LCP[i] is not the exact common prefix of the suffixes SA[i-1] and SA[i];
+ *       - i > 0 with SA[i-1] < n: counts 1 more if the pair is not in strictly increasing order.  The order is on signed
+ *         bytes, with a proper prefix first: the longer suffix before its own proper prefix is the violation (a value next
+ *         to itself is a repeat, not an order error).
+ *     A pair whose left entry SA[i-1] >= n is not looked at: that entry has been counted on its own.
+ * n == 0 or cnt == 0: CAPS_SA_OK with *n_errors = 0, whatever the pointers.  cnt > n, a null n_errors, or a null dT / dSA /
+ * dLCP with something to check: CAPS_SA_EINVAL.
  */
 int caps_sa_hip_verify_device_u32(const void* dT, uint64_t n, const void* dSA, const void* dLCP,
                                   void* hip_stream, uint64_t* n_errors);

@@ -84,3 +84,21 @@ def test_sharded_deferral_and_its_retry_over_gloo(small):
         first = [ln for ln in r.stdout.splitlines() if ln.startswith("case n=160000 ")]
         assert len(first) == 1 and "path=direct" in first[0] and "exch=0" in first[0], r.stdout
         assert ("ties=0 " in first[0]) == fail, first[0]
+
+
+def test_verify_sharded_across_slice_boundaries():
+    """caps_sa_dist.verify_sharded is what vouches for a build at world sizes above one (bench.py --gpus N, the check at the end of
+    every case above).  World 3, nothing built: every rank edits its slice of the naive arrays of a 1,500-character text
+    (tests/dist_verify_worker.py).  Accepted: an even split, an empty first, middle and last slice, a slice of one entry.  Rejected
+    with exactly 1: a slice head's LCP off by one either way, the pair across a boundary out of order, a value repeated across a
+    boundary, one suffix missing from slices that still join, every offset shifted; rejected: one offset shifted."""
+    from emul_util import emul
+    emul()
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=3", "--master-addr", "127.0.0.1",
+           "--master-port", "29561", os.path.join(ROOT, "tests", "dist_verify_worker.py")]
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("verify case ")]
+    assert len(lines) == 34 and all(ln.endswith(" OK") for ln in lines), r.stdout
+    assert sum("expect=0 " in ln for ln in lines) == 10 and sum("expect=1 " in ln for ln in lines) == 22, r.stdout

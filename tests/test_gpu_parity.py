@@ -213,6 +213,14 @@ def _device_build_and_verify(L, n, p, seed):
     # a corrupted result must be caught by the verifier
     SA[n // 2], SA[n // 2 + 1] = SA[n // 2 + 1].clone(), SA[n // 2].clone()
     assert L.verify_device(T.data_ptr(), n, SA.data_ptr(), LCP.data_ptr()) > 0
+    SA[n // 2], SA[n // 2 + 1] = SA[n // 2 + 1].clone(), SA[n // 2].clone()
+    # ... and at this size count what tests/test_gpu_verifier.py pins at small ones: one LCP off by one with the SA intact, in the
+    # last entry (the last trip of the kernel's grid-stride loop), and one entry out of range -- exactly 1 each
+    LCP[n - 1] += 1
+    assert L.verify_device(T.data_ptr(), n, SA.data_ptr(), LCP.data_ptr()) == 1
+    LCP[n - 1] -= 1
+    SA[n - 2] = n if n < 1 << 31 else n - (1 << 32)        # (the tensor is int32: the same 32 bits)
+    assert L.verify_device(T.data_ptr(), n, SA.data_ptr(), LCP.data_ptr()) == 1
     return st
 
 

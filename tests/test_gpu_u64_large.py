@@ -186,6 +186,22 @@ def test_c4_sharded_direct_path_for_the_last_rank(L, c4_text, monkeypatch):
         # a corrupted slice must be caught
         SA[cnt // 2], SA[cnt // 2 + 1] = SA[cnt // 2 + 1].clone(), SA[cnt // 2].clone()
         assert L.verify_slice_device(T.data_ptr(), n, bufs.SA.data_ptr(), bufs.LCP.data_ptr(), cnt, False, idx_bits=64) > 0
+        SA[cnt // 2], SA[cnt // 2 + 1] = SA[cnt // 2 + 1].clone(), SA[cnt // 2].clone()
+        # ... and a value beyond 2^32 twice (a word of the verifier's bit set beyond 2^27), next to itself with the LCPs of both pairs
+        # exact, so that only the repeat can count: exactly 1 (tests/verifier_cases.py repeat_at, at this size)
+        LCP = bufs.LCP[:cnt]
+        i = int(SA[1:cnt - 2].argmax().item()) + 2               # behind the slice's largest value: the repeated suffix is a few bytes
+        a, c = int(SA[i - 1].item()), int(SA[i + 1].item())      # long (one thread walks the whole of it, n - a steps)
+        assert a >= TWO32 and n - a < 1 << 20 and i + 1 < cnt
+        w = min(4096, n - a, n - c)
+        differ = (T[a:a + w] != T[c:c + w]).nonzero()
+        assert differ.numel() or w < 4096                        # random DNA: the suffixes part after a few dozen bases
+        saved = SA[i].clone(), LCP[i].clone(), LCP[i + 1].clone()
+        SA[i], LCP[i], LCP[i + 1] = a, n - a, int(differ[0].item()) if differ.numel() else w
+        errs = L.verify_slice_device(T.data_ptr(), n, bufs.SA.data_ptr(), bufs.LCP.data_ptr(), cnt, False, idx_bits=64)
+        SA[i], LCP[i], LCP[i + 1] = saved
+        assert errs == 1, errs
+        assert L.verify_slice_device(T.data_ptr(), n, bufs.SA.data_ptr(), bufs.LCP.data_ptr(), cnt, False, idx_bits=64) == 0
     finally:
         keep.close()
 
