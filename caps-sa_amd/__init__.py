@@ -151,6 +151,13 @@ class FMIndex:
         return cls((_lib or lib()).fm_build(BWT, primary, SA, sa_sample, idx_bits, device), device, _lib)
 
     @classmethod
+    def from_bwt_only(cls, BWT, primary: int, sa_sample: int = 32, idx_bits: int | None = None, device: int = 0,
+                      _lib: CapsLib | None = None) -> "FMIndex":
+        """An index that locates from (BWT, primary) ALONE: the SA samples come from an LF walk over the index itself, the blob is
+        the one ``from_bwt`` builds with the suffix array.  Not the BWT of any text: CapsSaError with code -1."""
+        return cls((_lib or lib()).fm_build_from_bwt(BWT, primary, sa_sample, idx_bits, device), device, _lib)
+
+    @classmethod
     def from_suffix_array(cls, sa_obj: "SuffixArray", sa_sample: int = 32) -> "FMIndex":
         """From a constructed ``SuffixArray(..., bwt=True)``."""
         return cls.from_bwt(sa_obj.BWT(), sa_obj.primary(), sa_obj.SA(), sa_sample, sa_obj._bits, sa_obj._device)

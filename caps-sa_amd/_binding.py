@@ -121,11 +121,12 @@ SHARD_EXPORTS = ["shard_create", "shard_destroy", "shard_info", "shard_phase1", 
                  "shard_phase1_arrays", "shard_set_key_bits"]
 
 EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_bytes", "workspace_bytes", "workspace_bytes_ex", "release_cache", "host_alloc", "host_free", "gen_rand_seq",
-           "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device"] + SHARD_EXPORTS + [
+           "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_from_bwt_workspace_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device"] + SHARD_EXPORTS + [
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
     for name in ("build", "build_multi", "build_device", "verify_device", "verify_slice_device", "sort_suffixes", "sort_segments", "merge",
-                 "upper_bound", "lcp", "build_bwt", "bwt_device", "inverse_bwt", "inverse_bwt_device", "fm_build", "fm_build_device")
+                 "upper_bound", "lcp", "build_bwt", "bwt_device", "inverse_bwt", "inverse_bwt_device", "fm_build", "fm_build_device",
+                 "fm_build_from_bwt", "fm_build_from_bwt_device")
 ]
 
 
@@ -181,7 +182,13 @@ class CapsLib:
         f("fm_count_device").argtypes = [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]
         f("fm_locate_device").restype = _ci
         f("fm_locate_device").argtypes = [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp]
+        f("fm_from_bwt_workspace_bytes").restype = _ci
+        f("fm_from_bwt_workspace_bytes").argtypes = [_u64, ctypes.c_uint32, _ci, ctypes.POINTER(_u64)]
         for sfx in ("u32", "u64"):
+            f(f"fm_build_from_bwt_{sfx}").restype = _ci
+            f(f"fm_build_from_bwt_{sfx}").argtypes = [_vp, _u64, _u64, ctypes.c_uint32, _vp, _u64, _ci]
+            f(f"fm_build_from_bwt_device_{sfx}").restype = _ci
+            f(f"fm_build_from_bwt_device_{sfx}").argtypes = [_vp, _u64, _u64, ctypes.c_uint32, _vp, _u64, _vp, _u64, _vp]
             f(f"fm_build_{sfx}").restype = _ci
             f(f"fm_build_{sfx}").argtypes = [_vp, _u64, _u64, _vp, ctypes.c_uint32, _vp, _u64, _ci]
             f(f"fm_build_device_{sfx}").restype = _ci
@@ -432,6 +439,33 @@ class CapsLib:
         sfx, _ = _sfx(idx_bits)
         self._check(self._f(f"fm_build_device_{sfx}")(dBWT_ptr or None, n, int(primary), dSA_ptr or None, sa_sample, dIndex_ptr or None,
                                                       index_bytes, stream or None))
+
+    def fm_from_bwt_workspace_bytes(self, n: int, sa_sample: int = 32, idx_bits: int = 32) -> int:
+        """Device workspace of fm_build_from_bwt_device: one entry per sample and O(n / 64) list nodes, no array of n entries."""
+        out = _u64(0)
+        self._check(self._f("fm_from_bwt_workspace_bytes")(n, sa_sample, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    def fm_build_from_bwt(self, BWT, primary: int, sa_sample: int = 32, idx_bits: int | None = None, device: int = 0) -> np.ndarray:
+        """The index WITH samples from (BWT, primary) alone: the same blob as fm_build with the suffix array of the text the BWT
+        inverts to.  The index width follows n unless idx_bits is given.  Not the BWT of any text: CapsSaError with code -1; more
+        than 4 distinct bytes: -6."""
+        B = self._text(BWT)
+        n = int(B.size)
+        idx_bits = idx_bits or (32 if n <= 0xFFFFFFFF else 64)
+        sfx, _ = _sfx(idx_bits)
+        blob = np.zeros(self.fm_index_bytes(n, sa_sample, idx_bits), dtype=np.uint8)
+        self._check(self._f(f"fm_build_from_bwt_{sfx}")(B.ctypes.data if n else None, n, int(primary) if n else 0, sa_sample,
+                                                        blob.ctypes.data, blob.size, device))
+        return blob
+
+    def fm_build_from_bwt_device(self, dBWT_ptr: int, n: int, primary: int, sa_sample: int, dIndex_ptr: int, index_bytes: int,
+                                 dWS_ptr: int = 0, ws_bytes: int = 0, idx_bits: int = 32, stream: int = 0) -> None:
+        """The same in device memory: dBWT_ptr (n bytes) -> dIndex_ptr (index_bytes >= fm_index_bytes(n, sa_sample)); workspace
+        dWS_ptr of ws_bytes (fm_from_bwt_workspace_bytes), or 0: allocated and freed by the call."""
+        sfx, _ = _sfx(idx_bits)
+        self._check(self._f(f"fm_build_from_bwt_device_{sfx}")(dBWT_ptr or None, n, int(primary), sa_sample, dIndex_ptr or None,
+                                                               index_bytes, dWS_ptr or None, ws_bytes, stream or None))
 
     @staticmethod
     def _patterns(patterns):

@@ -194,6 +194,23 @@ public:
         return fm;
     }
 
+    // The index WITH samples from (BWT, primary) alone (include/caps_sa_hip.h "FM-index from the BWT alone"): the same blob as
+    // build() with the suffix array of the text the BWT inverts to.  32-bit indices for n <= UINT32_MAX, else 64-bit.
+    static FM_Index build_from_bwt(const uint8_t* BWT, uint64_t n, uint64_t primary, uint32_t sa_sample = 32, int device = 0)
+    {
+        FM_Index fm;
+        fm.device_ = device;
+        const bool narrow = n <= UINT32_MAX;
+        uint64_t bytes = 0;
+        check(caps_sa_hip_fm_index_bytes(n, sa_sample, narrow ? 4 : 8, &bytes), "caps_sa_hip_fm_index_bytes");
+        fm.blob_.resize(static_cast<std::size_t>(bytes));
+        if (narrow)
+            check(caps_sa_hip_fm_build_from_bwt_u32(BWT, n, primary, sa_sample, fm.blob_.data(), bytes, device), "caps_sa_hip_fm_build_from_bwt_u32");
+        else
+            check(caps_sa_hip_fm_build_from_bwt_u64(BWT, n, primary, sa_sample, fm.blob_.data(), bytes, device), "caps_sa_hip_fm_build_from_bwt_u64");
+        return fm;
+    }
+
     const uint8_t* data() const { return blob_.data(); }
     std::size_t size() const { return blob_.size(); }
 

@@ -1245,68 +1245,101 @@ int fm_check_build(const void* B, uint64_t n, uint64_t primary, const void* SA, 
     return CAPS_SA_OK;
 }
 
-// the build on be's stream; synchronises (the alphabet and the totals are read back).  hdr_out: the header as written.
-template <typename idx_t>
-int run_fm_build(Backend& be, const uint8_t* dB, uint64_t n, uint64_t primary, const idx_t* dSA, uint32_t s, char* dIndex, uint64_t* hdr_out)
+// the header of (n, primary, s) before the alphabet and C[] are known
+template <typename idx_t> void fm_header_init(uint64_t* h, uint64_t n, uint64_t primary, uint32_t s, const FmLayout& l)
 {
-    using G = FmGeom<idx_t>;
-    if (!dSA) s = 0;
-    const FmLayout l = fm_layout(n, s, (int)sizeof(idx_t));
-    uint64_t h[FM_HDR_WORDS] = {};
+    std::memset(h, 0, FM_HDR_WORDS * sizeof(uint64_t));
     h[FMH_MAGIC] = FM_MAGIC; h[FMH_VERSION] = FM_VERSION; h[FMH_N] = n; h[FMH_PRIMARY] = n ? primary : 0; h[FMH_IDX_BYTES] = sizeof(idx_t);
     h[FMH_S] = s; h[FMH_NSAMPLES] = l.n_samples; h[FMH_NBLOCKS] = l.n_blocks; h[FMH_OFF_OCC] = l.off_occ; h[FMH_OFF_MRANK] = l.off_mrank;
     h[FMH_OFF_SAMPLES] = l.off_samples; h[FMH_TOTAL] = l.total;
     h[FMH_C0] = 1;
     for (int c = 1; c < 5; ++c) h[FMH_C0 + c] = n + 1;
+}
+template <typename idx_t> uint64_t fm_tiles(const FmLayout& l) { return (l.n_blocks * FmGeom<idx_t>::ROWS + FM_TILE - 1) / FM_TILE; }
+
+// the device words of a build: the alphabet probe's 8, the tile counts (FM_KEYS columns of n_tiles), the FM_KEYS totals
+struct FmScratch {
+    uint32_t* present;
+    uint64_t *cnt, *total;
+};
+// n >= 1: the alphabet (read back: synchronises; more than 4 letters is refused before anything is written to the index), then the
+// Occ section with zero mark words, and with samples the zero padding of the two sections behind it; the 4 symbol totals are on
+// their way to tot[] (the caller synchronises before it reads them)
+template <typename idx_t>
+int fm_build_occ(Backend& be, const uint8_t* dB, uint64_t n, uint64_t primary, uint32_t s, const FmLayout& l, char* dIndex, const FmScratch& sc,
+                 uint64_t* h, uint64_t* tot)
+{
+    const uint64_t n_tiles = fm_tiles<idx_t>(l);
+    be.memset(sc.present, 0, 8 * sizeof(uint32_t));
+    CAPS_LAUNCH(fm_probe_kernel, capped_grid(std::min<uint64_t>((n + 16ull * FM_NT - 1) / (16ull * FM_NT), 4096), FM_NT), FM_NT, be, dB, n, sc.present);
+    uint32_t pm[8];
+    be.d2h(pm, sc.present, sizeof pm);
+    be.sync();
+    uint32_t sigma = 0, syms = 0;
+    for (uint32_t k = 0; k < 256; ++k) {                 // signed-char order: 0x80 .. 0xFF, then 0x00 .. 0x7F
+        const uint32_t b = k ^ 0x80u;
+        if (!((pm[b / 32] >> (b % 32)) & 1u)) continue;
+        if (sigma < 4) syms |= b << (8 * sigma);
+        ++sigma;
+    }
+    if (sigma > 4) return fail(CAPS_SA_EALPHABET, "the BWT has more than 4 distinct bytes: the FM-index packs 2-bit codes");
+    h[FMH_SIGMA] = sigma;
+    h[FMH_SYMS] = syms;
+    const uint32_t tg = capped_grid(std::min<uint64_t>(n_tiles, 16384), FM_NT);
+    CAPS_LAUNCH(fm_tile_count_kernel, tg, FM_NT, be, dB, n, primary, n_tiles, syms, sigma, sc.cnt);
+    CAPS_LAUNCH(fm_scan_kernel, 4, FM_NT, be, sc.cnt, n_tiles, 0u, 4u, sc.total);
+    uint32_t* occ = reinterpret_cast<uint32_t*>(dIndex + l.off_occ);
+    CAPS_LAUNCH((fm_pack_kernel<idx_t>), tg, FM_NT, be, dB, n, primary, n_tiles, l.n_blocks, syms, sigma, (const uint64_t*)sc.cnt, occ);
+    be.d2h(tot, sc.total, 4 * sizeof(uint64_t));
+    if (s) {
+        // (the padding behind the two sections: the blob is the same bytes whatever the memory held)
+        const uint64_t mrank_end = l.off_mrank + l.n_blocks * sizeof(idx_t), samples_end = l.off_samples + l.n_samples * sizeof(idx_t);
+        if (l.off_samples > mrank_end) be.memset(dIndex + mrank_end, 0, l.off_samples - mrank_end);
+        if (l.total > samples_end) be.memset(dIndex + samples_end, 0, l.total - samples_end);
+    }
+    return CAPS_SA_OK;
+}
+// C[] into the header from the 4 totals (code 0 also counted the '$' row and the rows behind n)
+template <typename idx_t> void fm_header_counts(uint64_t* h, uint64_t* tot, uint64_t n, const FmLayout& l)
+{
+    const uint64_t pad = fm_tiles<idx_t>(l) * FM_TILE - (n + 1);
+    if (tot[0] < pad + 1 || tot[0] - pad - 1 + tot[1] + tot[2] + tot[3] != n) throw HipError("fm build: the symbol counts do not add up to n");
+    tot[0] -= pad + 1;
+    for (int c = 0; c < 4; ++c) h[FMH_C0 + c + 1] = h[FMH_C0 + c] + tot[c];
+}
+
+// the build on be's stream; synchronises (the alphabet and the totals are read back).  hdr_out: the header as written.
+template <typename idx_t>
+int run_fm_build(Backend& be, const uint8_t* dB, uint64_t n, uint64_t primary, const idx_t* dSA, uint32_t s, char* dIndex, uint64_t* hdr_out)
+{
+    if (!dSA) s = 0;
+    const FmLayout l = fm_layout(n, s, (int)sizeof(idx_t));
+    uint64_t h[FM_HDR_WORDS];
+    fm_header_init<idx_t>(h, n, primary, s, l);
     if (n == 0) {
         be.memset(dIndex + l.off_occ, 0, l.total - l.off_occ);
     } else {
         DevAllocs da(be);
-        const uint64_t n_tiles = (l.n_blocks * G::ROWS + FM_TILE - 1) / FM_TILE;
-        uint32_t* present = da.get<uint32_t>(8);
-        uint64_t* cnt = da.get<uint64_t>(FM_KEYS * n_tiles);
-        uint64_t* total = da.get<uint64_t>(FM_KEYS);
-        be.memset(present, 0, 8 * sizeof(uint32_t));
-        CAPS_LAUNCH(fm_probe_kernel, capped_grid(std::min<uint64_t>((n + 16ull * FM_NT - 1) / (16ull * FM_NT), 4096), FM_NT), FM_NT, be, dB, n, present);
-        uint32_t pm[8];
-        be.d2h(pm, present, sizeof pm);
-        be.sync();
-        uint32_t sigma = 0, syms = 0;
-        for (uint32_t k = 0; k < 256; ++k) {                 // signed-char order: 0x80 .. 0xFF, then 0x00 .. 0x7F
-            const uint32_t b = k ^ 0x80u;
-            if (!((pm[b / 32] >> (b % 32)) & 1u)) continue;
-            if (sigma < 4) syms |= b << (8 * sigma);
-            ++sigma;
-        }
-        if (sigma > 4) return fail(CAPS_SA_EALPHABET, "the BWT has more than 4 distinct bytes: the FM-index packs 2-bit codes");
-        h[FMH_SIGMA] = sigma;
-        h[FMH_SYMS] = syms;
-        const uint32_t tg = capped_grid(std::min<uint64_t>(n_tiles, 16384), FM_NT);
-        CAPS_LAUNCH(fm_tile_count_kernel, tg, FM_NT, be, dB, n, primary, n_tiles, syms, sigma, cnt);
-        CAPS_LAUNCH(fm_scan_kernel, 4, FM_NT, be, cnt, n_tiles, 0u, 4u, total);
-        uint32_t* occ = reinterpret_cast<uint32_t*>(dIndex + l.off_occ);
-        CAPS_LAUNCH((fm_pack_kernel<idx_t>), tg, FM_NT, be, dB, n, primary, n_tiles, l.n_blocks, syms, sigma, (const uint64_t*)cnt, occ);
+        const uint64_t n_tiles = fm_tiles<idx_t>(l);
+        FmScratch sc;
+        sc.present = da.get<uint32_t>(8);
+        sc.cnt = da.get<uint64_t>(FM_KEYS * n_tiles);
+        sc.total = da.get<uint64_t>(FM_KEYS);
         uint64_t tot[FM_KEYS] = {};
-        be.d2h(tot, total, 4 * sizeof(uint64_t));
+        if (int rc = fm_build_occ<idx_t>(be, dB, n, primary, s, l, dIndex, sc, h, tot)) return rc;
         if (s) {
+            const uint32_t tg = capped_grid(std::min<uint64_t>(n_tiles, 16384), FM_NT);
+            uint32_t* occ = reinterpret_cast<uint32_t*>(dIndex + l.off_occ);
             idx_t* mrank = reinterpret_cast<idx_t*>(dIndex + l.off_mrank);
             idx_t* samples = reinterpret_cast<idx_t*>(dIndex + l.off_samples);
-            // (the padding behind the two sections: the blob is the same bytes whatever the memory held)
-            const uint64_t mrank_end = l.off_mrank + l.n_blocks * sizeof(idx_t), samples_end = l.off_samples + l.n_samples * sizeof(idx_t);
-            if (l.off_samples > mrank_end) be.memset(dIndex + mrank_end, 0, l.off_samples - mrank_end);
-            if (l.total > samples_end) be.memset(dIndex + samples_end, 0, l.total - samples_end);
-            CAPS_LAUNCH((fm_mark_kernel<idx_t>), tg, FM_NT, be, dSA, n, n_tiles, l.n_blocks, s, occ, mrank, cnt);
-            CAPS_LAUNCH(fm_scan_kernel, 1, FM_NT, be, cnt, n_tiles, 4u, 1u, total);
+            CAPS_LAUNCH((fm_mark_kernel<idx_t>), tg, FM_NT, be, dSA, n, n_tiles, l.n_blocks, s, occ, mrank, sc.cnt);
+            CAPS_LAUNCH(fm_scan_kernel, 1, FM_NT, be, sc.cnt, n_tiles, 4u, 1u, sc.total);
             CAPS_LAUNCH((fm_sample_kernel<idx_t>), tg, FM_NT, be, dSA, n, n_tiles, l.n_blocks, s, (const uint32_t*)occ, mrank,
-                        (const uint64_t*)cnt, samples, l.n_samples);
-            be.d2h(tot + 4, total + 4, sizeof(uint64_t));
+                        (const uint64_t*)sc.cnt, samples, l.n_samples);
+            be.d2h(tot + 4, sc.total + 4, sizeof(uint64_t));
         }
         be.sync();
-        // code 0 also counted the '$' row and the rows behind n
-        const uint64_t pad = n_tiles * FM_TILE - (n + 1);
-        if (tot[0] < pad + 1 || tot[0] - pad - 1 + tot[1] + tot[2] + tot[3] != n) throw HipError("fm build: the symbol counts do not add up to n");
-        tot[0] -= pad + 1;
-        for (int c = 0; c < 4; ++c) h[FMH_C0 + c + 1] = h[FMH_C0 + c] + tot[c];
+        fm_header_counts<idx_t>(h, tot, n, l);
         if (s && tot[4] != l.n_samples)
             return fail(CAPS_SA_EINVAL, ("SA is not the suffix array of a text of n symbols: it holds " + std::to_string(tot[4]) + " multiples of sa_sample, a suffix array " +
                                          std::to_string(l.n_samples)).c_str());
@@ -1379,6 +1412,175 @@ int fm_build_host(const uint8_t* B, uint64_t n, uint64_t primary, const idx_t* S
         be.h2d(dB, B, n);
         if (SA) be.h2d(dSA, SA, n * sizeof(idx_t));
         if (int rc = run_fm_build<idx_t>(be, dB, n, primary, dSA, (uint32_t)s, hc.base, nullptr)) return rc;
+        be.d2h(index, hc.base, need);
+        be.sync();
+        fm_mark_resident(hc, index, need);
+        return CAPS_SA_OK;
+    });
+}
+
+// ---- FM-index from the BWT alone (include/caps_sa_hip.h caps_sa_hip_fm_build_from_bwt_*; kernels.h fm_walk_kernel) ------------------
+// The workspace: the words of the Occ build (FmScratch), the result words of the top walk, the staged rows (one per sample) and the
+// inverse BWT's splitter lists (inv_plan's levels: succ / len / off per node).  No array of n entries: n_samples entries of the
+// index width + 20 or 24 bytes per IBWT_S0 rows (+ 1/63 of that for the levels above) + 40 bytes per tile.
+struct FmBwtPlan {
+    uint32_t levels = 0;
+    uint64_t M[16] = {};
+    size_t off_present = 0, off_cnt = 0, off_total = 0, off_res = 0, off_stage = 0;
+    size_t off_succ[16] = {}, off_len[16] = {}, off_off[16] = {};
+    size_t bytes = 0;
+};
+template <typename idx_t> FmBwtPlan fm_bwt_plan(uint64_t n, uint32_t s)
+{
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const FmLayout l = fm_layout(n, s, (int)sizeof(idx_t));
+    FmBwtPlan p;
+    size_t o = 0;
+    p.off_present = o; o += 256;
+    p.off_total = o;   o += 256;
+    p.off_res = o;     o += 256;
+    p.off_cnt = o;     o += up(FM_KEYS * fm_tiles<idx_t>(l) * sizeof(uint64_t));
+    p.off_stage = o;   o += up(l.n_samples * sizeof(idx_t));
+    uint64_t m = n / IBWT_S0 + 1;
+    for (;;) {
+        p.M[p.levels] = m;
+        p.off_succ[p.levels] = o; o += up(m * sizeof(idx_t));
+        p.off_len[p.levels] = o;  o += up(m * sizeof(uint64_t));
+        p.off_off[p.levels] = o;  o += up(m * sizeof(uint64_t));
+        ++p.levels;
+        if (m <= IBWT_TOP) break;
+        m = (m - 1) / IBWT_S1 + 1;
+    }
+    p.bytes = o + 256;                               // (room to align the caller's base)
+    return p;
+}
+
+inline int fm_from_bwt_workspace_bytes(uint64_t n, uint32_t s, int idx_bytes, uint64_t* bytes)
+{
+    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (!fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be a power of two in 1 .. 1024");
+    *bytes = idx_bytes == 4 ? fm_bwt_plan<uint32_t>(n, s).bytes : fm_bwt_plan<uint64_t>(n, s).bytes;
+    return CAPS_SA_OK;
+}
+
+template <typename idx_t>
+int fm_check_from_bwt(const void* B, uint64_t n, uint64_t primary, uint64_t s, const void* index, uint64_t index_bytes, uint64_t* need)
+{
+    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
+    if (s == 0)
+        return fail(CAPS_SA_EINVAL, "sa_sample must be a power of two in 1 .. 1024 (an index without samples: caps_sa_hip_fm_build_* with a null SA)");
+    if (!fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be a power of two in 1 .. 1024");
+    if (!index) return fail(CAPS_SA_EINVAL, "null index");
+    if (n && !B) return fail(CAPS_SA_EINVAL, "null BWT");
+    if (n && primary >= n) return fail(CAPS_SA_EINVAL, "primary >= n");
+    *need = fm_layout(n, (uint32_t)s, (int)sizeof(idx_t)).total;
+    if (index_bytes < *need) return fail(CAPS_SA_EINVAL, "index_bytes too small (caps_sa_hip_fm_index_bytes)");
+    return CAPS_SA_OK;
+}
+
+// the build on be's stream, workspace at base (256-byte aligned); synchronises (alphabet, totals, the single-cycle check)
+template <typename idx_t>
+int run_fm_from_bwt(Backend& be, const uint8_t* dB, uint64_t n, uint64_t primary, uint32_t s, char* dIndex, char* base, const FmBwtPlan& p)
+{
+    const FmLayout l = fm_layout(n, s, (int)sizeof(idx_t));
+    uint64_t h[FM_HDR_WORDS];
+    fm_header_init<idx_t>(h, n, primary, s, l);
+    if (n == 0) {
+        be.memset(dIndex + l.off_occ, 0, l.total - l.off_occ);
+    } else {
+        const uint64_t n_tiles = fm_tiles<idx_t>(l);
+        FmScratch sc;
+        sc.present = reinterpret_cast<uint32_t*>(base + p.off_present);
+        sc.cnt = reinterpret_cast<uint64_t*>(base + p.off_cnt);
+        sc.total = reinterpret_cast<uint64_t*>(base + p.off_total);
+        uint64_t* res = reinterpret_cast<uint64_t*>(base + p.off_res);
+        idx_t* stage = reinterpret_cast<idx_t*>(base + p.off_stage);
+        auto succ = [&](uint32_t k) { return reinterpret_cast<idx_t*>(base + p.off_succ[k]); };
+        auto len = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.off_len[k]); };
+        auto off = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.off_off[k]); };
+        uint64_t tot[FM_KEYS] = {};
+        if (int rc = fm_build_occ<idx_t>(be, dB, n, primary, s, l, dIndex, sc, h, tot)) return rc;
+        be.sync();
+        fm_header_counts<idx_t>(h, tot, n, l);
+        FmView v;
+        if (int rc = fm_check_header(h, l.total, dIndex, v)) return rc;
+        uint32_t* occ = reinterpret_cast<uint32_t*>(dIndex + l.off_occ);
+        idx_t* mrank = reinterpret_cast<idx_t*>(dIndex + l.off_mrank);
+        idx_t* samples = reinterpret_cast<idx_t*>(dIndex + l.off_samples);
+        auto walk_grid = [](uint64_t walks) { return capped_grid(std::min<uint64_t>((walks + IBWT_Q - 1) / IBWT_Q, 8192), IBWT_NT); };
+        const uint32_t top = p.levels - 1;
+        CAPS_LAUNCH((fm_walk_kernel<idx_t, FMW_LINK0>), walk_grid(p.M[0]), IBWT_NT, be, v, p.M[0], succ(0), len(0), (const uint64_t*)nullptr,
+                    (uint32_t*)nullptr, (idx_t*)nullptr);
+        // the list levels of the inverse BWT as they are (they never touch LF)
+        for (uint32_t k = 1; k <= top; ++k)
+            CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_LINK>), walk_grid(p.M[k]), IBWT_NT, be, (const idx_t*)nullptr, n, p.M[k], p.M[k - 1],
+                        (const idx_t*)succ(k - 1), (const uint64_t*)len(k - 1), (uint64_t*)nullptr, succ(k), len(k),
+                        (const uint64_t*)nullptr, (const uint64_t*)nullptr, (uint8_t*)nullptr);
+        CAPS_LAUNCH((ibwt_top_kernel<idx_t>), 1, IBWT_NT, be, (const idx_t*)succ(top), (const uint64_t*)len(top), p.M[top], n, off(top), res);
+        uint64_t flag[3] = {0, 0, 0};
+        be.d2h(flag, res, sizeof flag);
+        be.sync();
+        if (flag[0] != 1) return fail(CAPS_SA_EINVAL, not_a_bwt_msg());
+        for (uint32_t k = top; k >= 1; --k)
+            CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_PROP>), walk_grid(p.M[k]), IBWT_NT, be, (const idx_t*)nullptr, n, p.M[k], p.M[k - 1],
+                        (const idx_t*)succ(k - 1), (const uint64_t*)len(k - 1), off(k - 1), (idx_t*)nullptr, (uint64_t*)nullptr,
+                        (const uint64_t*)off(k), (const uint64_t*)nullptr, (uint8_t*)nullptr);
+        CAPS_LAUNCH((fm_walk_kernel<idx_t, FMW_MARK>), walk_grid(p.M[0]), IBWT_NT, be, v, p.M[0], (idx_t*)nullptr, len(0), (const uint64_t*)off(0),
+                    occ, stage);
+        const uint32_t tg = capped_grid(std::min<uint64_t>(n_tiles, 16384), FM_NT);
+        CAPS_LAUNCH((fm_mark_kernel<idx_t, true>), tg, FM_NT, be, (const idx_t*)nullptr, n, n_tiles, l.n_blocks, s, occ, mrank, sc.cnt);
+        CAPS_LAUNCH(fm_scan_kernel, 1, FM_NT, be, sc.cnt, n_tiles, 4u, 1u, sc.total);
+        CAPS_LAUNCH((fm_mrank_abs_kernel<idx_t>), capped_grid(std::min<uint64_t>((l.n_blocks + FM_NT - 1) / FM_NT, 16384), FM_NT), FM_NT, be, mrank,
+                    l.n_blocks, n_tiles, (const uint64_t*)sc.cnt);
+        CAPS_LAUNCH((fm_place_kernel<idx_t>), capped_grid(std::min<uint64_t>((l.n_samples + FM_NT - 1) / FM_NT, 1u << 20), FM_NT), FM_NT, be, v,
+                    (const idx_t*)stage, samples);
+        be.d2h(tot + 4, sc.total + 4, sizeof(uint64_t));
+        be.sync();
+        if (tot[4] != l.n_samples) throw HipError("fm build from the BWT: the marked rows are not one per sample");
+    }
+    be.h2d(dIndex, h, sizeof h);
+    be.sync();
+    return CAPS_SA_OK;
+}
+
+template <typename idx_t>
+int fm_build_from_bwt_device(const void* dB, uint64_t n, uint64_t primary, uint64_t s, void* dIndex, uint64_t index_bytes, void* workspace,
+                             uint64_t workspace_bytes, void* stream)
+{
+    uint64_t need = 0;
+    if (int rc = fm_check_from_bwt<idx_t>(dB, n, primary, s, dIndex, index_bytes, &need)) return rc;
+    const FmBwtPlan p = fm_bwt_plan<idx_t>(n, (uint32_t)s);
+    if (workspace && workspace_bytes < p.bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_fm_from_bwt_workspace_bytes)");
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);                                    // a null workspace: allocated here, freed on return
+        if (!workspace) workspace = da.get<char>(p.bytes);
+        char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+        return run_fm_from_bwt<idx_t>(be, static_cast<const uint8_t*>(dB), n, primary, (uint32_t)s, static_cast<char*>(dIndex), base, p);
+    });
+}
+
+// host buffers: the BWT up, the index built at the head of the host-path block and downloaded; it stays there for the host queries
+template <typename idx_t>
+int fm_build_from_bwt_host(const uint8_t* B, uint64_t n, uint64_t primary, uint64_t s, void* index, uint64_t index_bytes, int device)
+{
+    uint64_t need = 0;
+    if (int rc = fm_check_from_bwt<idx_t>(B, n, primary, s, index, index_bytes, &need)) return rc;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        hc.fm_host = nullptr;
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const FmBwtPlan p = fm_bwt_plan<idx_t>(n, (uint32_t)s);
+        const size_t off_B = up(need), off_ws = off_B + up(n ? n : 1), total = off_ws + p.bytes;
+        fm_host_block(hc, be, device, total);
+        uint8_t* dB = reinterpret_cast<uint8_t*>(hc.base + off_B);
+        be.h2d(dB, B, n);
+        if (int rc = run_fm_from_bwt<idx_t>(be, dB, n, primary, (uint32_t)s, hc.base, hc.base + off_ws, p)) return rc;
         be.d2h(index, hc.base, need);
         be.sync();
         fm_mark_resident(hc, index, need);
@@ -1989,6 +2191,18 @@ int CAPS_API(fm_index_bytes)(uint64_t n, uint32_t sa_sample, int idx_bytes, uint
     { return caps::fm_build_host<IDX>(BWT, n, primary, SA, sa_sample, index, index_bytes, device); }
 CAPS_DEFINE_FM(u32, uint32_t)
 CAPS_DEFINE_FM(u64, uint64_t)
+int CAPS_API(fm_from_bwt_workspace_bytes)(uint64_t n, uint32_t sa_sample, int idx_bytes, uint64_t* bytes)
+{ return caps::fm_from_bwt_workspace_bytes(n, sa_sample, idx_bytes, bytes); }
+#define CAPS_FM_FROM_BWT(SFX, IDX)                                                                                                  \
+    int CAPS_API(fm_build_from_bwt_device_##SFX)(const void* dBWT, uint64_t n, uint64_t primary, uint32_t sa_sample, void* dIndex,  \
+                                                 uint64_t index_bytes, void* workspace, uint64_t workspace_bytes, void* stream)     \
+    { return caps::fm_build_from_bwt_device<IDX>(dBWT, n, primary, sa_sample, dIndex, index_bytes, workspace, workspace_bytes, stream); } \
+    int CAPS_API(fm_build_from_bwt_##SFX)(const uint8_t* BWT, uint64_t n, uint64_t primary, uint32_t sa_sample, void* index,        \
+                                          uint64_t index_bytes, int device)                                                        \
+    { return caps::fm_build_from_bwt_host<IDX>(BWT, n, primary, sa_sample, index, index_bytes, device); }
+CAPS_FM_FROM_BWT(u32, uint32_t)
+CAPS_FM_FROM_BWT(u64, uint64_t)
+#undef CAPS_FM_FROM_BWT
 int CAPS_API(fm_count_device)(const void* dIndex, uint64_t index_bytes, const void* dPatterns, const void* dPatOff, uint64_t q,
                               void* dFirst, void* dCount, void* stream)
 { return caps::fm_count_device(dIndex, index_bytes, dPatterns, dPatOff, q, dFirst, dCount, stream); }

@@ -5,7 +5,12 @@
 //     caps_sa --inverse-bwt IN.bwt OUT
 //     caps_sa <input_path> <output_path> [subproblem-count] --fm-index PATH [--fm-sample S]
 //     caps_sa --fm-search INDEX PATTERNS [--locate K]
+//     caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S]
 //
+// * --fm-from-bwt IN.bwt OUT.fm [--fm-sample S] (not in the reference): the FM-index WITH its SA samples from a file that --bwt
+//   wrote and nothing else (include/caps_sa_hip.h "FM-index from the BWT alone"): byte for byte what --fm-index writes for the
+//   same text.  IN is read and checked as --inverse-bwt does; 32-bit indices for n <= UINT32_MAX; every refusal comes before OUT
+//   is opened, OUT is written only after the build has succeeded.  Any other argument is refused;
 // * --fm-index PATH [--fm-sample S] (not in the reference): also write the FM-index of the (remapped) text to PATH (the blob of
 //   include/caps_sa_hip.h "FM-index", SA samples every S = 32 text positions; S a power of two, 1 .. 1024).  One GPU, no bounded
 //   context, like --bwt: refused before any file is opened;
@@ -152,6 +157,61 @@ static int fm_search_main(const std::vector<std::string>& args)
     return 0;
 }
 
+// a file that --bwt wrote (u64 n, u64 primary, n bytes) into data; false with the reason on stderr, prefixed by the option's name
+static bool read_bwt_file(const char* opt, const std::string& in_path, std::string& data, uint64_t& n, uint64_t& primary)
+{
+    {
+        std::ifstream in(in_path, std::ios::binary | std::ios::ate);
+        if (!in) { std::cerr << opt << ": " << in_path << " : cannot open\n"; return false; }
+        const std::streamsize size = in.tellg();
+        if (size < 0) { std::cerr << opt << ": " << in_path << " : cannot read\n"; return false; }
+        in.seekg(0);
+        data.resize(static_cast<size_t>(size));
+        if (size && !in.read(&data[0], size)) { std::cerr << opt << ": " << in_path << " : cannot read\n"; return false; }
+    }
+    if (data.size() < 16) {
+        std::cerr << opt << ": " << in_path << " is " << data.size() << " bytes, shorter than its 16-byte header (u64 n, u64 primary)\n";
+        return false;
+    }
+    std::memcpy(&n, data.data(), 8);
+    std::memcpy(&primary, data.data() + 8, 8);
+    if (data.size() - 16 != n) {
+        std::cerr << opt << ": " << in_path << " holds " << data.size() - 16 << " bytes after its header, its n says " << n << "\n";
+        return false;
+    }
+    if (n && primary >= n) { std::cerr << opt << ": primary " << primary << " >= n " << n << "\n"; return false; }
+    return true;
+}
+
+// caps_sa --fm-from-bwt IN OUT [--fm-sample S]: args = everything after the program name
+static int fm_from_bwt_main(const std::vector<std::string>& args)
+{
+    const char* usage = "--fm-from-bwt: usage: caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S] (no other option or argument)\n";
+    if ((args.size() != 3 && args.size() != 5) || args[0] != "--fm-from-bwt" || args[1].compare(0, 2, "--") == 0 ||
+        args[2].compare(0, 2, "--") == 0 || (args.size() == 5 && args[3] != "--fm-sample")) {
+        std::cerr << usage;
+        return EXIT_FAILURE;
+    }
+    size_t sample = 32;
+    if (args.size() == 5 && (!parse_count(args[4], sample) || sample < 1 || sample > 1024 || (sample & (sample - 1)))) {
+        std::cerr << "--fm-sample: a power of two in 1 .. 1024, please\n";
+        return EXIT_FAILURE;
+    }
+    std::string data;
+    uint64_t n = 0, primary = 0;
+    if (!read_bwt_file("--fm-from-bwt", args[1], data, n, primary)) return EXIT_FAILURE;
+    try {
+        const CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::build_from_bwt(reinterpret_cast<const uint8_t*>(data.data() + 16), n, primary,
+                                                                       static_cast<uint32_t>(sample));
+        fm.save(args[2]);
+        std::cerr << "FM-index: " << fm.size() << " bytes, SA samples every " << sample << " positions.\n";
+    } catch (const std::exception& e) {
+        std::cerr << e.what() << "\n";
+        return EXIT_FAILURE;
+    }
+    return 0;
+}
+
 // caps_sa --inverse-bwt IN OUT: args = everything after the program name
 static int inverse_bwt_main(const std::vector<std::string>& args)
 {
@@ -162,27 +222,8 @@ static int inverse_bwt_main(const std::vector<std::string>& args)
     const std::string& in_path = args[1];
     const std::string& out_path = args[2];
     std::string data;
-    {
-        std::ifstream in(in_path, std::ios::binary | std::ios::ate);
-        if (!in) { std::cerr << "--inverse-bwt: " << in_path << " : cannot open\n"; return EXIT_FAILURE; }
-        const std::streamsize size = in.tellg();
-        if (size < 0) { std::cerr << "--inverse-bwt: " << in_path << " : cannot read\n"; return EXIT_FAILURE; }
-        in.seekg(0);
-        data.resize(static_cast<size_t>(size));
-        if (size && !in.read(&data[0], size)) { std::cerr << "--inverse-bwt: " << in_path << " : cannot read\n"; return EXIT_FAILURE; }
-    }
-    if (data.size() < 16) {
-        std::cerr << "--inverse-bwt: " << in_path << " is " << data.size() << " bytes, shorter than its 16-byte header (u64 n, u64 primary)\n";
-        return EXIT_FAILURE;
-    }
     uint64_t n = 0, primary = 0;
-    std::memcpy(&n, data.data(), 8);
-    std::memcpy(&primary, data.data() + 8, 8);
-    if (data.size() - 16 != n) {
-        std::cerr << "--inverse-bwt: " << in_path << " holds " << data.size() - 16 << " bytes after its header, its n says " << n << "\n";
-        return EXIT_FAILURE;
-    }
-    if (n && primary >= n) { std::cerr << "--inverse-bwt: primary " << primary << " >= n " << n << "\n"; return EXIT_FAILURE; }
+    if (!read_bwt_file("--inverse-bwt", in_path, data, n, primary)) return EXIT_FAILURE;
     std::string text(static_cast<size_t>(n), '\0');
     try {
         CaPS_SA::inverse_bwt(reinterpret_cast<const uint8_t*>(data.data() + 16), n, primary, n ? &text[0] : nullptr);
@@ -202,6 +243,8 @@ int main(int argc, char* argv[])
         if (std::strcmp(argv[i], "--inverse-bwt") == 0) return inverse_bwt_main(std::vector<std::string>(argv + 1, argv + argc));
     for (int i = 1; i < argc; ++i)
         if (std::strcmp(argv[i], "--fm-search") == 0) return fm_search_main(std::vector<std::string>(argv + 1, argv + argc));
+    for (int i = 1; i < argc; ++i)
+        if (std::strcmp(argv[i], "--fm-from-bwt") == 0) return fm_from_bwt_main(std::vector<std::string>(argv + 1, argv + argc));
     std::vector<std::string> pos;
     bool pretty = false, bwt = false, fm = false, fm_sample_given = false;
     size_t gpus = 1, fm_sample = 32;
@@ -233,7 +276,8 @@ int main(int argc, char* argv[])
                      "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH> "
                      "<(optional)--fm-index PATH [--fm-sample S]>\n"
                      "       caps_sa --inverse-bwt IN.bwt OUT\n"
-                     "       caps_sa --fm-search INDEX PATTERNS [--locate K]\n";
+                     "       caps_sa --fm-search INDEX PATTERNS [--locate K]\n"
+                     "       caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S]\n";
         return EXIT_FAILURE;
     }
     size_t p = 0, ctx = 0;

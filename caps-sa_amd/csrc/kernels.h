@@ -5354,8 +5354,9 @@ HD uint32_t fm_mark_word(const idx_t* __restrict__ SA, uint64_t n, uint64_t r0, 
     return m;
 }
 
-// the mark pass: the mark words of every block, mrank[block] = the marks before the block IN ITS TILE, cnt[4][tile] = the tile's marks
-template <typename idx_t>
+// the mark pass: the mark words of every block, mrank[block] = the marks before the block IN ITS TILE, cnt[4][tile] = the tile's marks.
+// FROM_OCC: the mark words stand in the blocks already (fm_walk_kernel FMW_MARK set them; SA is not read): the ranks and counts alone.
+template <typename idx_t, bool FROM_OCC = false>
 GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_mark_kernel(KCTX const idx_t* __restrict__ SA, uint64_t n, uint64_t n_tiles, uint64_t n_blocks, uint32_t s,
                                                uint32_t* __restrict__ occ, idx_t* __restrict__ mrank, uint64_t* __restrict__ cnt)
 {
@@ -5370,9 +5371,13 @@ GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_mark_kernel(KCTX const idx_t* __restrict__ SA,
         for (uint32_t j = 0; j < FM_MROUNDS; ++j) {
             const uint64_t w0 = (tile * FM_MROUNDS + j) * FM_NT;                    // first mark word of the round
             PAR(tid) {
-                const uint32_t m = fm_mark_word<idx_t>(SA, n, (w0 + tid) * FM_MROWS, s);
                 const uint64_t blk = (w0 + tid) / G::MWN;
-                if (blk < n_blocks) occ[blk * G::BW + G::MW0 + tid % G::MWN] = m;
+                uint32_t m;
+                if (FROM_OCC) m = blk < n_blocks ? occ[blk * G::BW + G::MW0 + tid % G::MWN] : 0u;
+                else {
+                    m = fm_mark_word<idx_t>(SA, n, (w0 + tid) * FM_MROWS, s);
+                    if (blk < n_blocks) occ[blk * G::BW + G::MW0 + tid % G::MWN] = m;
+                }
                 tc[tid] = (uint32_t)__builtin_popcount(m);
             }
             SYNC();
@@ -5569,6 +5574,120 @@ GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_locate_kernel(KCTX FmView v, const uint64_t* _
                     }
                     if (!done) { ATOMIC_OR_U32(flags, 4u); res = (uint64_t)(idx_t)~(idx_t)0; }
                     pos[o] = res;
+                }
+            }
+        }
+    }
+}
+
+// ---- SA samples from the BWT alone (capi_impl.h fm_from_bwt_*; include/caps_sa_hip.h "FM-index from the BWT alone") -------------
+// LF^k(0), k = 1 .. n, is the row of text position n - k (k = n: the '$' row, position 0; k = n + 1: row 0 again), so a row's offset
+// on the cycle of row 0 is its SA value: neither T nor the SA is read.  LF comes from the finished Occ section, one block per step
+// (the inverse BWT's 4-byte table load, ibwt_walk_kernel, replaced by one line); the splitters are the inverse's (every IBWT_S0-th
+// row) and their list is ranked by its IBWT_LINK / ibwt_top_kernel / IBWT_PROP, which never touch LF.
+
+// LF of row r (<= n) from its block: the '$' row goes to row 0; kept inside 0 .. n whatever the block holds
+template <typename idx_t>
+HD uint64_t fm_lf_row(const FmView& v, uint64_t r)
+{
+    using G = FmGeom<idx_t>;
+    if (r == v.primary + 1) return 0;
+    const uint32_t* p = fm_block_of<idx_t>(v, r);
+    const uint32_t k = (uint32_t)(r % G::ROWS);
+    const uint32_t c = (p[G::CW0 + k / FM_WROWS] >> (2u * (k % FM_WROWS))) & 3u;
+    const uint64_t x = fm_c_of(v, c) + fm_block_occ<idx_t>(p, c, k, r > v.primary + 1);
+    return x <= v.n ? x : v.n;
+}
+
+// The two walks over the Occ section, in ibwt_walk_kernel's ranges of IBWT_Q walks per workgroup:
+//   FMW_LINK0  from splitter row j * S0 along LF to the next splitter: succ[j], len[j] (rows; at most n + 1 steps)
+//   FMW_MARK   from splitter row j * S0 at cycle offset off[j] for len[j] rows: the row at offset k in 1 .. n has text position
+//              p = n - k; when p is a multiple of s its mark bit is set (an atomic OR into the block's mark word: the lanes that
+//              pass through the block meanwhile read its counts and code words only) and stage[p / s] = the row (each slot once).
+//              Offset 0 is row 0, never marked; offset n is the '$' row (p = 0), marked.
+enum { FMW_LINK0 = 0, FMW_MARK = 1 };
+template <typename idx_t, int MODE>
+GLOBAL_FN LAUNCH_BOUNDS(IBWT_NT) fm_walk_kernel(KCTX FmView v, uint64_t walks, idx_t* __restrict__ succ, uint64_t* __restrict__ len,
+                                                 const uint64_t* __restrict__ off, uint32_t* occ, idx_t* __restrict__ stage)
+{
+    using G = FmGeom<idx_t>;
+    SHARED_ARRAY(uint32_t, q, 1);
+    const uint64_t ranges = (walks + IBWT_Q - 1) / IBWT_Q;
+    const uint32_t sh = (uint32_t)__builtin_ctz(v.s | (FM_MAX_SAMPLE << 1));
+    for (uint64_t rg = K_BLOCK_IDX; rg < ranges; rg += K_GRID_DIM) {               // block-uniform
+        PAR(tid) { if (tid == 0) q[0] = 0; }
+        SYNC();
+        PAR(tid) {
+            const uint64_t lo = rg * IBWT_Q, cnt = std::min<uint64_t>(IBWT_Q, walks - lo);
+            for (;;) {
+                const uint32_t i = FETCH_ADD_U32(&q[0], 1u);
+                if (i >= cnt) break;
+                const uint64_t j = lo + i;
+                uint64_t cur = j << IBWT_S0_LOG;
+                if (cur > v.n) continue;                                            // (never: walks = n / S0 + 1)
+                if (MODE == FMW_LINK0) {
+                    uint64_t steps = 0;
+                    do { cur = fm_lf_row<idx_t>(v, cur); ++steps; } while ((cur & (IBWT_S0 - 1)) != 0 && steps <= v.n);
+                    succ[j] = (idx_t)(cur >> IBWT_S0_LOG);
+                    len[j] = steps;
+                } else {
+                    const uint64_t o = off[j], steps = std::min<uint64_t>(len[j], v.n + 1);
+                    for (uint64_t t = 0; t < steps; ++t) {
+                        const uint64_t k = o + t;
+                        if (k > v.n || k < o) break;                                // (never, after the single-cycle check)
+                        const uint64_t p = v.n - k;
+                        if (k >= 1 && (p & (v.s - 1u)) == 0 && (p >> sh) < v.n_samples) {
+                            ATOMIC_OR_U32(&occ[(cur / G::ROWS) * G::BW + G::MW0 + (uint32_t)(cur % G::ROWS) / FM_MROWS], 1u << (cur % FM_MROWS));
+                            stage[p >> sh] = (idx_t)cur;
+                        }
+                        if (t + 1 < steps) cur = fm_lf_row<idx_t>(v, cur);
+                    }
+                }
+            }
+        }
+        SYNC();
+    }
+}
+
+// mrank[block] from tile-relative (fm_mark_kernel) to absolute: + the marks of the tiles before the block's (pre[4][tile], scanned)
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_mrank_abs_kernel(KCTX idx_t* __restrict__ mrank, uint64_t n_blocks, uint64_t n_tiles,
+                                                    const uint64_t* __restrict__ pre)
+{
+    using G = FmGeom<idx_t>;
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t b0 = (uint64_t)K_BLOCK_IDX * FM_NT; b0 < n_blocks; b0 += stride) { // block-uniform
+        PAR(tid) {
+            const uint64_t b = b0 + tid, tile = b * G::ROWS / FM_TILE;
+            if (b < n_blocks && tile < n_tiles) mrank[b] = (idx_t)(pre[4 * n_tiles + tile] + (uint64_t)mrank[b]);
+        }
+    }
+}
+
+// the samples in row order from the staged rows: samples[mrank[block of stage[i]] + marks below the row in its block] = i * s.
+// Every index is compared with its section's size before it is used (the query kernels' rule).
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_place_kernel(KCTX FmView v, const idx_t* __restrict__ stage, idx_t* __restrict__ samples)
+{
+    using G = FmGeom<idx_t>;
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t i0 = (uint64_t)K_BLOCK_IDX * FM_NT; i0 < v.n_samples; i0 += stride) { // block-uniform
+        PAR(tid) {
+            const uint64_t i = i0 + tid;
+            if (i < v.n_samples) {
+                const uint64_t r = (uint64_t)STREAM_LOAD(&stage[i]), blk = r / G::ROWS;
+                if (r <= v.n && blk < v.n_blocks) {
+                    const uint32_t* p = v.occ + blk * G::BW;
+                    const uint32_t k = (uint32_t)(r % G::ROWS);
+                    uint32_t below = 0;
+                    UNROLL
+                    for (uint32_t w = 0; w < G::MWN; ++w) {
+                        const uint32_t rows = k > 32 * w ? (k - 32 * w < 32 ? k - 32 * w : 32) : 0u;
+                        const uint32_t mw = p[G::MW0 + w];
+                        below += (uint32_t)__builtin_popcount(rows < 32 ? mw & ((1u << rows) - 1u) : mw);
+                    }
+                    const uint64_t si = (uint64_t)static_cast<const idx_t*>(v.mrank)[blk] + below;
+                    if (si < v.n_samples) samples[si] = (idx_t)(i * v.s);
                 }
             }
         }

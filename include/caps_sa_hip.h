@@ -396,6 +396,43 @@ int caps_sa_hip_fm_count(const void* index, uint64_t index_bytes, const uint8_t*
 int caps_sa_hip_fm_locate(const void* index, uint64_t index_bytes, const uint64_t* first, const uint64_t* count,
                           const uint64_t* out_off, uint64_t q, uint64_t* pos, int device);
 
+/* ---- FM-index from the BWT alone: the SA samples by LF walk -----------------------------
+ *
+ * The same blob as caps_sa_hip_fm_build_* with an SA, for a caller who holds (BWT, primary) and nothing else: dIndex receives
+ * exactly the bytes that caps_sa_hip_fm_build_device_* writes for (BWT, primary, SA, sa_sample), where SA is the suffix array of
+ * the text that this BWT inverts to. With the rows of the inverse BWT above, LF^k(0) for k = 1 .. n is the row of the suffix at
+ * text position n - k (k = n: the '$' row, position 0), so a row's offset on the LF cycle of row 0 is its SA value. The Occ section
+ * is built first and gives LF in one block per step; the rows 0 mod 64 cut the cycle into segments, the list of segments is ranked
+ * by the inverse BWT's list levels, and a second walk marks the rows whose position is a multiple of sa_sample. Neither the text nor
+ * the SA exists at any time.
+ *
+ * sa_sample: a power of two in 1 .. 1024. 0 is CAPS_SA_EINVAL (an index without samples: caps_sa_hip_fm_build_* with a null SA).
+ * Workspace: caps_sa_hip_fm_from_bwt_workspace_bytes(n, sa_sample, W) <= (number of samples) * W + 32 * (n / 64 + 1) + 2^20 bytes, W
+ * the index width -- no array of n entries. A NULL workspace is allocated and freed by the call; one that is too small is
+ * CAPS_SA_EINVAL. Errors, all CAPS_SA_EINVAL and checked before any allocation: a null pointer (dBWT may be null for n = 0),
+ * primary >= n for n >= 1, n > UINT32_MAX with _u32, index_bytes below caps_sa_hip_fm_index_bytes(n, sa_sample, W). More than 4
+ * distinct bytes: CAPS_SA_EALPHABET, decided before anything is written to the index. n = 0 succeeds: the blob of the format table,
+ * no samples and sa_sample in word 12. A (BWT, primary) that is not the BWT of any text (its LF mapping is not one cycle) is
+ * CAPS_SA_EINVAL with the message of the inverse BWT; the contents of the index are then unspecified. Every loop of the kernels is
+ * bounded by n + 1 steps whatever the input.
+ */
+
+/* Workspace of caps_sa_hip_fm_build_from_bwt_device_*, idx_bytes = 4 (_u32) or 8 (_u64). */
+int caps_sa_hip_fm_from_bwt_workspace_bytes(uint64_t n, uint32_t sa_sample, int idx_bytes, uint64_t* bytes);
+/* dBWT (n bytes), dIndex (index_bytes >= caps_sa_hip_fm_index_bytes(n, sa_sample, W), written; 64-byte aligned) and workspace (or
+ * NULL) are device pointers on the current device; the work runs on hip_stream and has completed on return (the alphabet, the
+ * symbol totals and the single-cycle check are read back). */
+int caps_sa_hip_fm_build_from_bwt_device_u32(const void* dBWT, uint64_t n, uint64_t primary, uint32_t sa_sample,
+                                             void* dIndex, uint64_t index_bytes, void* workspace, uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_fm_build_from_bwt_device_u64(const void* dBWT, uint64_t n, uint64_t primary, uint32_t sa_sample,
+                                             void* dIndex, uint64_t index_bytes, void* workspace, uint64_t workspace_bytes, void* hip_stream);
+/* Host buffers: the BWT up, the index built on `device` and downloaded into `index`. Runs on the device block of the host-buffer
+ * builds (calls serialised on it, the caller's current device restored); the index stays there for the host queries. */
+int caps_sa_hip_fm_build_from_bwt_u32(const uint8_t* BWT, uint64_t n, uint64_t primary, uint32_t sa_sample,
+                                      void* index, uint64_t index_bytes, int device);
+int caps_sa_hip_fm_build_from_bwt_u64(const uint8_t* BWT, uint64_t n, uint64_t primary, uint32_t sa_sample,
+                                      void* index, uint64_t index_bytes, int device);
+
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
 /* merge_sort (src/Suffix_Array.cpp:112-129) of an arbitrary list of cnt distinct suffix
