@@ -129,8 +129,8 @@ class SuffixArray:
 
 
 class FMIndex:
-    """FM-index over (BWT, primary) (include/caps_sa_hip.h "FM-index"): batched ``count`` and ``locate`` on the GPU for texts of at
-    most 4 distinct bytes.  The index is one blob (``blob``, np.uint8; ``nbytes``); ``save`` / ``load`` write and read exactly it."""
+    """FM-index over (BWT, primary) (include/caps_sa_hip.h "FM-index"): batched ``count``, ``locate`` and (after ``with_text_samples``)
+    ``extract`` on the GPU for texts of at most 4 distinct bytes.  The index is one blob (``blob``, np.uint8; ``nbytes``); ``save`` / ``load`` write and read exactly it."""
 
     def __init__(self, blob: np.ndarray, device: int = 0, _lib: CapsLib | None = None):
         self.blob = np.ascontiguousarray(blob, dtype=np.uint8)
@@ -140,6 +140,7 @@ class FMIndex:
             raise ValueError("not an FM-index blob")
         hdr = self.blob[:256].view(np.uint64)
         self._n, self._sample = int(hdr[2]), int(hdr[12])
+        self._text_sample = int(hdr[19]) if int(hdr[1]) == 2 else 0
 
     def _l(self) -> CapsLib:
         return self._lib or lib()
@@ -187,6 +188,22 @@ class FMIndex:
         off[1:] = np.cumsum(take, dtype=np.uint64)
         pos, _ = self._l().fm_locate(self.blob, first, count, off, self._device)
         return [pos[int(off[j]):int(off[j + 1])] for j in range(take.size)]
+
+    @property
+    def text_sample(self) -> int:
+        """The distance of the text-position samples that ``extract`` walks from; 0: a version-1 blob (no extract)."""
+        return self._text_sample
+
+    def with_text_samples(self, text_sample: int = 32) -> "FMIndex":
+        """A new FMIndex (format version 2, a larger blob) that also extracts: one row per text_sample text positions, derived from
+        the SA samples of this one.  An index without SA samples: CapsSaError with code -2."""
+        return FMIndex(self._l().fm_add_text_samples(self.blob, text_sample, self._device), self._device, self._lib)
+
+    def extract(self, starts, lengths) -> list:
+        """T[starts[j] : starts[j] + lengths[j]] for every j, as a list of ``bytes`` (needs ``with_text_samples``)."""
+        text, off = self._l().fm_extract(self.blob, starts, lengths, self._device)
+        raw = text.tobytes()
+        return [raw[int(off[j]):int(off[j + 1])] for j in range(off.size - 1)]
 
     def save(self, path: str) -> None:
         with open(path, "wb") as f:

@@ -121,7 +121,8 @@ SHARD_EXPORTS = ["shard_create", "shard_destroy", "shard_info", "shard_phase1", 
                  "shard_phase1_arrays", "shard_set_key_bits"]
 
 EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_bytes", "workspace_bytes", "workspace_bytes_ex", "release_cache", "host_alloc", "host_free", "gen_rand_seq",
-           "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_from_bwt_workspace_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device"] + SHARD_EXPORTS + [
+           "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_from_bwt_workspace_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device",
+           "fm_index_bytes_ex", "fm_add_text_samples", "fm_add_text_samples_device", "fm_extract_workspace_bytes", "fm_extract", "fm_extract_device"] + SHARD_EXPORTS + [
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
     for name in ("build", "build_multi", "build_device", "verify_device", "verify_slice_device", "sort_suffixes", "sort_segments", "merge",
@@ -182,6 +183,18 @@ class CapsLib:
         f("fm_count_device").argtypes = [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]
         f("fm_locate_device").restype = _ci
         f("fm_locate_device").argtypes = [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp]
+        f("fm_index_bytes_ex").restype = _ci
+        f("fm_index_bytes_ex").argtypes = [_u64, ctypes.c_uint32, ctypes.c_uint32, _ci, ctypes.POINTER(_u64)]
+        f("fm_add_text_samples").restype = _ci
+        f("fm_add_text_samples").argtypes = [_vp, _u64, ctypes.c_uint32, _ci]
+        f("fm_add_text_samples_device").restype = _ci
+        f("fm_add_text_samples_device").argtypes = [_vp, _u64, ctypes.c_uint32, _vp]
+        f("fm_extract_workspace_bytes").restype = _ci
+        f("fm_extract_workspace_bytes").argtypes = [_u64, ctypes.POINTER(_u64)]
+        f("fm_extract").restype = _ci
+        f("fm_extract").argtypes = [_vp, _u64, _vp, _vp, _u64, _vp, _ci]
+        f("fm_extract_device").restype = _ci
+        f("fm_extract_device").argtypes = [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp]
         f("fm_from_bwt_workspace_bytes").restype = _ci
         f("fm_from_bwt_workspace_bytes").argtypes = [_u64, ctypes.c_uint32, _ci, ctypes.POINTER(_u64)]
         for sfx in ("u32", "u64"):
@@ -515,6 +528,57 @@ class CapsLib:
                          stream: int = 0) -> None:
         self._check(self._f("fm_locate_device")(dIndex_ptr or None, index_bytes, dFirst_ptr or None, dCount_ptr or None, dOutOff_ptr or None, q,
                                                 dPos_ptr or None, stream or None))
+
+    # ------------------------------------------------------------------ FM-index: extract (include/caps_sa_hip.h "FM-index: extract")
+    def fm_index_bytes_ex(self, n: int, sa_sample: int = 32, text_sample: int = 32, idx_bits: int = 32) -> int:
+        """Bytes of the version-2 index of n symbols: SA samples every sa_sample, text-position samples every text_sample."""
+        out = _u64(0)
+        self._check(self._f("fm_index_bytes_ex")(n, sa_sample, text_sample, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    def fm_add_text_samples(self, index: np.ndarray, text_sample: int = 32, device: int = 0) -> np.ndarray:
+        """A NEW version-2 blob from a blob with SA samples (version 1, or version 2 at another distance): the blob extract needs."""
+        index = np.ascontiguousarray(index, dtype=np.uint8)
+        if index.size < 256:
+            raise ValueError("not an FM-index blob")
+        hdr = index[:256].view(np.uint64)
+        n, s, W, v1 = int(hdr[2]), int(hdr[12]), int(hdr[4]), int(hdr[18])
+        need = self.fm_index_bytes_ex(n, s, text_sample, 8 * W) if s and W in (4, 8) else index.size
+        blob = np.zeros(max(need, index.size), dtype=np.uint8)
+        blob[:index.size] = index
+        self._check(self._f("fm_add_text_samples")(blob.ctypes.data, blob.size, text_sample, device))
+        assert need >= v1
+        return blob[:need].copy() if blob.size != need else blob
+
+    def fm_add_text_samples_device(self, dIndex_ptr: int, index_bytes: int, text_sample: int = 32, stream: int = 0) -> None:
+        """In place in device memory: index_bytes is the capacity at dIndex_ptr (>= fm_index_bytes_ex)."""
+        self._check(self._f("fm_add_text_samples_device")(dIndex_ptr or None, index_bytes, text_sample, stream or None))
+
+    def fm_extract_workspace_bytes(self, q: int) -> int:
+        out = _u64(0)
+        self._check(self._f("fm_extract_workspace_bytes")(q, ctypes.byref(out)))
+        return out.value
+
+    def fm_extract(self, index: np.ndarray, starts, lengths, device: int = 0):
+        """(text np.uint8[sum of lengths], out_off u64[q + 1]): text[out_off[j] : out_off[j + 1]] = T[starts[j] : starts[j] + lengths[j]]."""
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint64)
+        if starts.shape != lengths.shape or starts.ndim != 1:
+            raise ValueError("starts and lengths: two 1-d arrays of one size")
+        q = starts.size
+        out_off = np.zeros(q + 1, dtype=np.uint64)
+        out_off[1:] = np.cumsum(lengths, dtype=np.uint64)
+        text = np.zeros(int(out_off[-1]), dtype=np.uint8)
+        self._check(self._f("fm_extract")(index.ctypes.data, index.size, starts.ctypes.data if q else None, out_off.ctypes.data, q,
+                                          text.ctypes.data if text.size else None, device))
+        return text, out_off
+
+    def fm_extract_device(self, dIndex_ptr: int, index_bytes: int, dStart_ptr: int, dOutOff_ptr: int, q: int, dText_ptr: int,
+                          dWS_ptr: int = 0, ws_bytes: int = 0, stream: int = 0) -> None:
+        """Device arrays: dStart u64[q], dOutOff u64[q + 1], dText u8[dOutOff[q]]; workspace dWS_ptr of ws_bytes
+        (fm_extract_workspace_bytes), or 0: allocated and freed by the call."""
+        self._check(self._f("fm_extract_device")(dIndex_ptr or None, index_bytes, dStart_ptr or None, dOutOff_ptr or None, q,
+                                                 dText_ptr or None, dWS_ptr or None, ws_bytes, stream or None))
 
     # ------------------------------------------------------------------ kernel-level entry points
     def sort_suffixes(self, T, idx, idx_bits: int = 32, device: int = 0):

@@ -19,13 +19,14 @@
 //  * construct_bwt() (not in the reference): construct() plus the Burrows-Wheeler transform (include/caps_sa_hip.h), one device;
 //    its n-byte buffer is allocated by the first construct_bwt(), so construct() callers pay nothing for it.
 //  * the free function inverse_bwt() (not in the reference): the text back from (BWT, primary).
-//  * the class FM_Index (not in the reference either): count and locate over (BWT, primary) and a sample of the SA.
+//  * the class FM_Index (not in the reference either): count, locate and extract over (BWT, primary) and a sample of the SA.
 #ifndef CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 #define CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 
 #include <cstdint>
 #include <cstddef>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <new>
 #include <stdexcept>
@@ -167,8 +168,8 @@ inline void inverse_bwt(const uint8_t* BWT, uint64_t n, uint64_t primary, char* 
                                  caps_sa_hip_last_error());
 }
 
-// FM-index over (BWT, primary) (include/caps_sa_hip.h "FM-index"; not in the reference): count and locate for batches of patterns
-// over texts of at most 4 distinct bytes.  The index is one blob (data(), size()); save / load write and read exactly it.  Every
+// FM-index over (BWT, primary) (include/caps_sa_hip.h "FM-index"; not in the reference): count and locate for batches of patterns,
+// extract for batches of text ranges (after add_text_samples), over texts of at most 4 distinct bytes.  The index is one blob (data(), size()); save / load write and read exactly it.  Every
 // error of the C ABI is thrown as std::runtime_error with its message.
 class FM_Index
 {
@@ -234,6 +235,49 @@ public:
         pos.assign(static_cast<std::size_t>(out_off[q]), 0);
         check(caps_sa_hip_fm_locate(blob_.data(), blob_.size(), first.data(), cnt.data(), out_off.data(), q, pos.data(), device_),
               "caps_sa_hip_fm_locate");
+    }
+
+    // Format version 2 in place (include/caps_sa_hip.h "FM-index: extract"): one row per t text positions behind the version-1
+    // sections, derived from the SA samples.  An index without samples, t below sa_sample or no power of two up to 1024: thrown.
+    void add_text_samples(uint32_t t = 32)
+    {
+        if (blob_.size() < 256) throw std::runtime_error("caps_sa_hip_fm_add_text_samples: not an FM-index blob");
+        uint64_t h[32];
+        std::memcpy(h, blob_.data(), sizeof h);
+        uint64_t bytes = blob_.size();                       // (without SA samples: the library refuses below, with its reason)
+        if (h[12] >= 1 && h[12] <= 1024)
+            check(caps_sa_hip_fm_index_bytes_ex(h[2], static_cast<uint32_t>(h[12]), t, h[4] == 8 ? 8 : 4, &bytes), "caps_sa_hip_fm_index_bytes_ex");
+        const std::size_t old = blob_.size();
+        if (bytes > old) blob_.resize(static_cast<std::size_t>(bytes));
+        const int rc = caps_sa_hip_fm_add_text_samples(blob_.data(), blob_.size(), t, device_);
+        if (rc != CAPS_SA_OK) blob_.resize(old);
+        check(rc, "caps_sa_hip_fm_add_text_samples");
+        blob_.resize(static_cast<std::size_t>(bytes));
+    }
+
+    // 0: a version-1 blob (no extract)
+    uint32_t text_sample() const
+    {
+        if (blob_.size() < 256) return 0;
+        uint64_t h[32];
+        std::memcpy(h, blob_.data(), sizeof h);
+        return h[1] == 2 ? static_cast<uint32_t>(h[19]) : 0;
+    }
+    uint64_t n() const
+    {
+        uint64_t v = 0;
+        if (blob_.size() >= 256) std::memcpy(&v, blob_.data() + 16, 8);
+        return v;
+    }
+
+    // text[out_off[j] .. out_off[j + 1]) = T[start[j] .. start[j] + out_off[j + 1] - out_off[j]); out_off.size() = start.size() + 1
+    void extract(const std::vector<uint64_t>& start, const std::vector<uint64_t>& out_off, std::string& text) const
+    {
+        const uint64_t q = start.size();
+        if (out_off.size() != q + 1) throw std::runtime_error("FM_Index::extract: out_off must have one entry more than start");
+        text.assign(static_cast<std::size_t>(out_off[q]), '\0');
+        check(caps_sa_hip_fm_extract(blob_.data(), blob_.size(), start.data(), out_off.data(), q,
+                                     text.empty() ? nullptr : reinterpret_cast<uint8_t*>(&text[0]), device_), "caps_sa_hip_fm_extract");
     }
 
     void save(const std::string& path) const

@@ -1151,10 +1151,10 @@ int inverse_bwt_host(const uint8_t* B, uint64_t n, uint64_t primary, char* T, in
 // ---- FM-index (include/caps_sa_hip.h caps_sa_hip_fm_*; kernels.h fm_*) ------------------------------------------------------------
 // The blob: a header of FM_HDR_WORDS 64-bit words, the Occ blocks, then (with samples) the per-block mark ranks and the samples.
 constexpr uint64_t FM_MAGIC = 0x31494D4653504143ull;      // "CAPSFMI1"
-constexpr uint64_t FM_VERSION = 1;
+constexpr uint64_t FM_VERSION = 1, FM_VERSION_TEXT = 2;    // 2: version 1 with samples + the text-position samples behind it
 constexpr uint32_t FM_HDR_WORDS = 32;
 enum { FMH_MAGIC = 0, FMH_VERSION, FMH_N, FMH_PRIMARY, FMH_IDX_BYTES, FMH_SIGMA, FMH_SYMS, FMH_C0, FMH_S = FMH_C0 + 5, FMH_NSAMPLES,
-       FMH_NBLOCKS, FMH_OFF_OCC, FMH_OFF_MRANK, FMH_OFF_SAMPLES, FMH_TOTAL };
+       FMH_NBLOCKS, FMH_OFF_OCC, FMH_OFF_MRANK, FMH_OFF_SAMPLES, FMH_TOTAL, FMH_T, FMH_NTEXT, FMH_OFF_ROWOF, FMH_TOTAL2 };
 
 struct FmLayout {
     uint64_t n_blocks = 0, n_samples = 0, off_occ = 0, off_mrank = 0, off_samples = 0, total = 0;
@@ -1173,6 +1173,20 @@ inline FmLayout fm_layout(uint64_t n, uint32_t s, int idx_bytes)
     return l;
 }
 inline bool fm_sample_ok(uint64_t s) { return s >= 1 && s <= FM_MAX_SAMPLE && (s & (s - 1)) == 0; }
+// version 2: rowof[m] behind the version-1 sections, one row per t text positions
+struct FmTextLayout {
+    uint64_t m = 0, off = 0, total = 0;
+};
+inline FmTextLayout fm_text_layout(const FmLayout& l, uint64_t n, uint64_t t, int idx_bytes)
+{
+    FmTextLayout tl;
+    tl.m = n ? (n - 1) / t + 1 : 0;
+    tl.off = l.total;
+    tl.total = tl.off + ((tl.m * (uint64_t)idx_bytes + 63) & ~uint64_t(63));
+    return tl;
+}
+// the bytes of the blob whose (checked) header is h
+inline uint64_t fm_blob_bytes(const uint64_t* h) { return h[FMH_VERSION] == FM_VERSION_TEXT ? h[FMH_TOTAL2] : h[FMH_TOTAL]; }
 
 inline int fm_index_bytes(uint64_t n, uint32_t s, int idx_bytes, uint64_t* bytes)
 {
@@ -1180,6 +1194,15 @@ inline int fm_index_bytes(uint64_t n, uint32_t s, int idx_bytes, uint64_t* bytes
     if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
     if (s && !fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be 0 (no samples) or a power of two in 1 .. 1024");
     *bytes = fm_layout(n, s, idx_bytes).total;
+    return CAPS_SA_OK;
+}
+inline int fm_index_bytes_ex(uint64_t n, uint32_t s, uint32_t t, int idx_bytes, uint64_t* bytes)
+{
+    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (!fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be a power of two in 1 .. 1024 (text samples need SA samples)");
+    if (!fm_sample_ok(t) || t < s) return fail(CAPS_SA_EINVAL, "text_sample must be a power of two in sa_sample .. 1024");
+    *bytes = fm_text_layout(fm_layout(n, s, idx_bytes), n, t, idx_bytes).total;
     return CAPS_SA_OK;
 }
 
@@ -1202,7 +1225,7 @@ inline uint64_t* fm_words(Backend& be)
 inline int fm_check_header(const uint64_t* h, uint64_t index_bytes, const void* dIndex, FmView& v)
 {
     if (h[FMH_MAGIC] != FM_MAGIC) return fail(CAPS_SA_EINVAL, "not an FM-index of this library (wrong magic)");
-    if (h[FMH_VERSION] != FM_VERSION) return fail(CAPS_SA_EINVAL, "FM-index of another format version");
+    if (h[FMH_VERSION] != FM_VERSION && h[FMH_VERSION] != FM_VERSION_TEXT) return fail(CAPS_SA_EINVAL, "FM-index of another format version");
     const uint64_t ib = h[FMH_IDX_BYTES], n = h[FMH_N], s = h[FMH_S];
     if (ib != 4 && ib != 8) return fail(CAPS_SA_EINVAL, "FM-index header: bad index width");
     if (ib == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "FM-index header: n does not fit its index width");
@@ -1229,6 +1252,20 @@ inline int fm_check_header(const uint64_t* h, uint64_t index_bytes, const void* 
     v.sigma = (uint32_t)h[FMH_SIGMA];
     v.syms = (uint32_t)h[FMH_SYMS];
     v.s = (uint32_t)s;
+    v.rowof = nullptr;
+    v.n_text_samples = 0;
+    v.t = 0;
+    if (h[FMH_VERSION] == FM_VERSION_TEXT) {
+        const uint64_t t = h[FMH_T];
+        if (!s || !fm_sample_ok(t) || t < s) return fail(CAPS_SA_EINVAL, "FM-index header: bad text sample distance");
+        const FmTextLayout tl = fm_text_layout(l, n, t, (int)ib);
+        if (h[FMH_NTEXT] != tl.m || h[FMH_OFF_ROWOF] != tl.off || h[FMH_TOTAL2] != tl.total)
+            return fail(CAPS_SA_EINVAL, "FM-index header: the text-sample section does not fit n, the index width and the sample distances");
+        if (tl.total > index_bytes) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than the FM-index (truncated blob)");
+        v.rowof = base + tl.off;
+        v.n_text_samples = tl.m;
+        v.t = (uint32_t)t;
+    }
     return CAPS_SA_OK;
 }
 
@@ -1724,7 +1761,7 @@ inline int fm_count_host(const void* index, uint64_t index_bytes, const uint8_t*
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
         auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-        const uint64_t blob = h[FMH_TOTAL];
+        const uint64_t blob = fm_blob_bytes(h);
         const size_t off_pat = up(blob), off_off = off_pat + up(pbytes + 1), off_first = off_off + up((q + 1) * 8), off_count = off_first + up(q * 8);
         fm_upload(hc, be, device, index, blob, off_count + up(q * 8));
         be.h2d(hc.base + off_pat, pat, pbytes);
@@ -1759,7 +1796,7 @@ inline int fm_locate_host(const void* index, uint64_t index_bytes, const uint64_
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
         auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-        const uint64_t blob = h[FMH_TOTAL];
+        const uint64_t blob = fm_blob_bytes(h);
         const size_t off_first = up(blob), off_count = off_first + up(q * 8), off_off = off_count + up(q * 8), off_pos = off_off + up((q + 1) * 8);
         fm_upload(hc, be, device, index, blob, off_pos + up(o_end * 8 + 8));
         be.h2d(hc.base + off_first, first, q * 8);
@@ -1768,6 +1805,220 @@ inline int fm_locate_host(const void* index, uint64_t index_bytes, const uint64_
         be.memset(hc.base + off_pos, 0xFF, o_end * 8 + 8);   // (slots beyond a query's hits come back as UINT64_MAX)
         if (int rc = run_fm_locate(be, hc.base, blob, h, hc.base + off_first, hc.base + off_count, hc.base + off_off, q, hc.base + off_pos)) return rc;
         be.d2h(pos + outoff[0], hc.base + off_pos + outoff[0] * 8, (o_end - outoff[0]) * 8);
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+
+// ---- text-position samples and extract (include/caps_sa_hip.h "FM-index: extract"; kernels.h fm_rowof_kernel, fm_extract_kernel) ----
+// in place at dIndex (capacity bytes): the blob with samples becomes version 2 at distance t; synchronises.  hdr: the header when the
+// caller has read it already; hdr_out: the header as written.  Nothing is written before every refusal of the arguments.
+inline int run_fm_add_text_samples(Backend& be, char* dIndex, uint64_t capacity, uint32_t t, const uint64_t* hdr, uint64_t* hdr_out)
+{
+    uint64_t h[FM_HDR_WORDS];
+    if (hdr) std::memcpy(h, hdr, sizeof h);
+    else { be.d2h(h, dIndex, sizeof h); be.sync(); }
+    FmView v;
+    if (int rc = fm_check_header(h, capacity, dIndex, v)) return rc;
+    if (v.s == 0) return fail(CAPS_SA_EUNSUPPORTED, "this FM-index was built without SA samples: text samples are taken from them");
+    if (t < v.s) return fail(CAPS_SA_EINVAL, "text_sample must be a power of two in sa_sample .. 1024");
+    const int W = (int)h[FMH_IDX_BYTES];
+    const FmTextLayout tl = fm_text_layout(fm_layout(v.n, v.s, W), v.n, t, W);
+    if (capacity < tl.total) return fail(CAPS_SA_EINVAL, "index_bytes too small (caps_sa_hip_fm_index_bytes_ex)");
+    const bool was_text = h[FMH_VERSION] == FM_VERSION_TEXT;
+    h[FMH_VERSION] = FM_VERSION;
+    for (uint32_t k = FMH_T; k < FM_HDR_WORDS; ++k) h[k] = 0;
+    uint32_t f = 0;
+    if (tl.total > tl.off) be.memset(dIndex + tl.off, 0, tl.total - tl.off);
+    if (v.n) {
+        uint64_t* words = fm_words(be);
+        uint32_t* flags = reinterpret_cast<uint32_t*>(words);
+        be.memset(words, 0, sizeof(uint64_t));
+        const uint64_t mark_words = v.n_blocks * (W == 4 ? FmGeom<uint32_t>::MWN : FmGeom<uint64_t>::MWN);
+        const uint32_t g = capped_grid(std::min<uint64_t>((mark_words + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+        const uint32_t cg = capped_grid(std::min<uint64_t>((tl.m + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+        if (W == 4) {
+            uint32_t* rowof = reinterpret_cast<uint32_t*>(dIndex + tl.off);
+            CAPS_LAUNCH((fm_rowof_kernel<uint32_t>), g, FM_NT, be, v, t, tl.m, rowof);
+            CAPS_LAUNCH((fm_rowof_check_kernel<uint32_t>), cg, FM_NT, be, (const uint32_t*)rowof, tl.m, v.n, flags);
+        } else {
+            uint64_t* rowof = reinterpret_cast<uint64_t*>(dIndex + tl.off);
+            CAPS_LAUNCH((fm_rowof_kernel<uint64_t>), g, FM_NT, be, v, t, tl.m, rowof);
+            CAPS_LAUNCH((fm_rowof_check_kernel<uint64_t>), cg, FM_NT, be, (const uint64_t*)rowof, tl.m, v.n, flags);
+        }
+        be.d2h(&f, flags, sizeof f);
+        be.sync();
+    }
+    if (!(f & 8u)) {
+        h[FMH_VERSION] = FM_VERSION_TEXT;
+        h[FMH_T] = t; h[FMH_NTEXT] = tl.m; h[FMH_OFF_ROWOF] = tl.off; h[FMH_TOTAL2] = tl.total;
+    }
+    if (!(f & 8u) || was_text) {                             // (refused: a version-1 header stays as it is, a version-2 one falls back to it)
+        be.h2d(dIndex, h, sizeof h);
+        be.sync();
+    }
+    if (hdr_out) std::memcpy(hdr_out, h, sizeof h);
+    if (f & 8u)
+        return fail(CAPS_SA_EINVAL, "the SA samples do not hold every multiple of text_sample once: the blob is not an index this library built");
+    return CAPS_SA_OK;
+}
+
+inline int fm_add_text_samples_device(void* dIndex, uint64_t index_bytes, uint32_t t, void* stream)
+{
+    if (!dIndex) return fail(CAPS_SA_EINVAL, "null index");
+    if (index_bytes < FM_HDR_WORDS * sizeof(uint64_t)) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than an FM-index header");
+    if (!fm_sample_ok(t)) return fail(CAPS_SA_EINVAL, "text_sample must be a power of two in sa_sample .. 1024");
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        return run_fm_add_text_samples(be, static_cast<char*>(dIndex), index_bytes, t, nullptr, nullptr);
+    });
+}
+
+// the host form: the version-1 part up (unless it is the blob there already), the section built behind it, header and section down.
+// The device copy is then the caller's new blob and is marked so: the next host query does not upload it again.
+inline int fm_add_text_samples_host(void* index, uint64_t index_bytes, uint32_t t, int device)
+{
+    uint64_t h[FM_HDR_WORDS];
+    FmView v;
+    if (!fm_sample_ok(t)) return fail(CAPS_SA_EINVAL, "text_sample must be a power of two in sa_sample .. 1024");
+    if (int rc = fm_host_header(index, index_bytes, h, v)) return rc;
+    if (v.s == 0) return fail(CAPS_SA_EUNSUPPORTED, "this FM-index was built without SA samples: text samples are taken from them");
+    if (t < v.s) return fail(CAPS_SA_EINVAL, "text_sample must be a power of two in sa_sample .. 1024");
+    const int W = (int)h[FMH_IDX_BYTES];
+    const FmTextLayout tl = fm_text_layout(fm_layout(v.n, v.s, W), v.n, t, W);
+    if (index_bytes < tl.total) return fail(CAPS_SA_EINVAL, "index_bytes too small (caps_sa_hip_fm_index_bytes_ex)");
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        const uint64_t room = std::max<uint64_t>(tl.total, fm_blob_bytes(h));    // (a version-2 blob at a smaller distance is the larger)
+        fm_upload(hc, be, device, index, fm_blob_bytes(h), (size_t)room + 256);
+        hc.fm_host = nullptr;                                // (the block is about to differ from the caller's blob)
+        uint64_t out[FM_HDR_WORDS];
+        std::memcpy(out, h, sizeof out);
+        const int rc = run_fm_add_text_samples(be, hc.base, room, t, h, out);
+        if (rc != CAPS_SA_OK && rc != CAPS_SA_EINVAL) return rc;
+        const std::string msg = last_error_ref();
+        std::memcpy(index, out, sizeof out);
+        if (rc == CAPS_SA_OK) {
+            if (tl.total > tl.off) be.d2h(static_cast<char*>(index) + tl.off, hc.base + tl.off, tl.total - tl.off);
+            be.sync();
+            fm_mark_resident(hc, index, tl.total);
+        }
+        last_error_ref() = msg;
+        return rc;
+    });
+}
+
+inline int fm_extract_workspace_bytes(uint64_t q, uint64_t* bytes)
+{
+    if (!bytes) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (q > (1ull << 56)) return fail(CAPS_SA_EINVAL, "too many queries");
+    *bytes = (((q + 1) * sizeof(uint64_t) + 255) & ~uint64_t(255)) + 256;
+    return CAPS_SA_OK;
+}
+
+// extract on device arrays; pre: u64[q + 1] of the workspace (256-byte aligned); `hdr` as in run_fm_count
+inline int run_fm_extract(Backend& be, const void* dIndex, uint64_t index_bytes, const uint64_t* hdr, const void* dStart, const void* dOutOff,
+                          uint64_t q, void* dText, uint64_t* pre)
+{
+    uint64_t h[FM_HDR_WORDS];
+    if (hdr) std::memcpy(h, hdr, sizeof h);
+    else { be.d2h(h, dIndex, sizeof h); be.sync(); }
+    FmView v;
+    if (int rc = fm_check_header(h, index_bytes, dIndex, v)) return rc;
+    if (h[FMH_VERSION] != FM_VERSION_TEXT)
+        return fail(CAPS_SA_EUNSUPPORTED, "this FM-index has no text-position samples (format version 1): caps_sa_hip_fm_add_text_samples first");
+    if (q == 0) return CAPS_SA_OK;
+    uint64_t* words = fm_words(be);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(words);
+    const uint32_t sh = (uint32_t)__builtin_ctz(v.t);
+    const uint32_t g = capped_grid(std::min<uint64_t>((q + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+    be.memset(words, 0, sizeof(uint64_t));
+    CAPS_LAUNCH(fm_extract_plan_kernel, g, FM_NT, be, static_cast<const uint64_t*>(dStart), static_cast<const uint64_t*>(dOutOff), q, v.n, sh, pre, flags);
+    CAPS_LAUNCH(fm_scan_kernel, 1, FM_NT, be, pre, q, 0u, 1u, pre + q);
+    uint32_t f = 0;
+    uint64_t lanes = 0;
+    be.d2h(&f, flags, sizeof f);
+    be.d2h(&lanes, pre + q, sizeof lanes);
+    be.sync();
+    if (f & 1u) return fail(CAPS_SA_EINVAL, "output offsets are not monotone");
+    if (f & 2u) return fail(CAPS_SA_EINVAL, "start + length > n");
+    if (lanes == 0) return CAPS_SA_OK;
+    if (!dText) return fail(CAPS_SA_EINVAL, "null pointer");
+    static const bool bytes_only = std::getenv("CAPS_SA_FM_EXTRACT_BYTES") != nullptr;      // (measurement: byte stores only)
+    const uint32_t eg = capped_grid(std::min<uint64_t>((lanes + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+    const uint64_t* s = static_cast<const uint64_t*>(dStart);
+    const uint64_t* o = static_cast<const uint64_t*>(dOutOff);
+    uint8_t* text = static_cast<uint8_t*>(dText);
+    if (h[FMH_IDX_BYTES] == 4) {
+        if (bytes_only) CAPS_LAUNCH((fm_extract_kernel<uint32_t, false>), eg, FM_NT, be, v, s, o, (const uint64_t*)pre, q, lanes, text, flags);
+        else CAPS_LAUNCH((fm_extract_kernel<uint32_t, true>), eg, FM_NT, be, v, s, o, (const uint64_t*)pre, q, lanes, text, flags);
+    } else {
+        if (bytes_only) CAPS_LAUNCH((fm_extract_kernel<uint64_t, false>), eg, FM_NT, be, v, s, o, (const uint64_t*)pre, q, lanes, text, flags);
+        else CAPS_LAUNCH((fm_extract_kernel<uint64_t, true>), eg, FM_NT, be, v, s, o, (const uint64_t*)pre, q, lanes, text, flags);
+    }
+    be.d2h(&f, flags, sizeof f);
+    be.sync();
+    if (f & 4u)
+        return fail(CAPS_SA_EINVAL, "an extract walk met the '$' row or row 0 below its text sample: the blob is not an index this library built");
+    return CAPS_SA_OK;
+}
+
+inline int fm_extract_device(const void* dIndex, uint64_t index_bytes, const void* dStart, const void* dOutOff, uint64_t q, void* dText,
+                             void* workspace, uint64_t workspace_bytes, void* stream)
+{
+    if (!dIndex) return fail(CAPS_SA_EINVAL, "null index");
+    if (index_bytes < FM_HDR_WORDS * sizeof(uint64_t)) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than an FM-index header");
+    if (q && (!dStart || !dOutOff)) return fail(CAPS_SA_EINVAL, "null pointer");
+    uint64_t need = 0;
+    if (int rc = fm_extract_workspace_bytes(q, &need)) return rc;
+    if (workspace && workspace_bytes < need) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_fm_extract_workspace_bytes)");
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);                                    // a null workspace: allocated here, freed on return
+        if (!workspace && q) workspace = da.get<char>(need);
+        uint64_t* pre = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+        return run_fm_extract(be, dIndex, index_bytes, nullptr, dStart, dOutOff, q, dText, pre);
+    });
+}
+
+inline int fm_extract_host(const void* index, uint64_t index_bytes, const uint64_t* start, const uint64_t* outoff, uint64_t q, uint8_t* text,
+                           int device)
+{
+    uint64_t h[FM_HDR_WORDS];
+    FmView v;
+    if (int rc = fm_host_header(index, index_bytes, h, v)) return rc;
+    if (h[FMH_VERSION] != FM_VERSION_TEXT)
+        return fail(CAPS_SA_EUNSUPPORTED, "this FM-index has no text-position samples (format version 1): caps_sa_hip_fm_add_text_samples first");
+    if (q == 0) return CAPS_SA_OK;
+    if (!outoff || !start) return fail(CAPS_SA_EINVAL, "null pointer");
+    for (uint64_t j = 0; j < q; ++j) {
+        if (outoff[j + 1] < outoff[j]) return fail(CAPS_SA_EINVAL, "output offsets are not monotone");
+        if (start[j] > v.n || outoff[j + 1] - outoff[j] > v.n - start[j]) return fail(CAPS_SA_EINVAL, "start + length > n");
+    }
+    const uint64_t o_begin = outoff[0], o_end = outoff[q];
+    if (o_end > o_begin && !text) return fail(CAPS_SA_EINVAL, "null pointer");
+    uint64_t ws = 0;
+    if (int rc = fm_extract_workspace_bytes(q, &ws)) return rc;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const uint64_t blob = fm_blob_bytes(h);
+        const size_t off_start = up(blob), off_off = off_start + up(q * 8), off_ws = off_off + up((q + 1) * 8), off_text = off_ws + up(ws);
+        fm_upload(hc, be, device, index, blob, off_text + up(o_end + 8));
+        be.h2d(hc.base + off_start, start, q * 8);
+        be.h2d(hc.base + off_off, outoff, (q + 1) * 8);
+        if (int rc = run_fm_extract(be, hc.base, blob, h, hc.base + off_start, hc.base + off_off, q, hc.base + off_text,
+                                    reinterpret_cast<uint64_t*>(hc.base + off_ws)))
+            return rc;
+        if (o_end > o_begin) be.d2h(text + o_begin, hc.base + off_text + o_begin, o_end - o_begin);
         be.sync();
         return CAPS_SA_OK;
     });
@@ -2203,6 +2454,19 @@ int CAPS_API(fm_from_bwt_workspace_bytes)(uint64_t n, uint32_t sa_sample, int id
 CAPS_FM_FROM_BWT(u32, uint32_t)
 CAPS_FM_FROM_BWT(u64, uint64_t)
 #undef CAPS_FM_FROM_BWT
+int CAPS_API(fm_index_bytes_ex)(uint64_t n, uint32_t sa_sample, uint32_t text_sample, int idx_bytes, uint64_t* bytes)
+{ return caps::fm_index_bytes_ex(n, sa_sample, text_sample, idx_bytes, bytes); }
+int CAPS_API(fm_add_text_samples_device)(void* dIndex, uint64_t index_bytes, uint32_t text_sample, void* stream)
+{ return caps::fm_add_text_samples_device(dIndex, index_bytes, text_sample, stream); }
+int CAPS_API(fm_add_text_samples)(void* index, uint64_t index_bytes, uint32_t text_sample, int device)
+{ return caps::fm_add_text_samples_host(index, index_bytes, text_sample, device); }
+int CAPS_API(fm_extract_workspace_bytes)(uint64_t q, uint64_t* bytes) { return caps::fm_extract_workspace_bytes(q, bytes); }
+int CAPS_API(fm_extract_device)(const void* dIndex, uint64_t index_bytes, const void* dStart, const void* dOutOff, uint64_t q, void* dText,
+                                void* workspace, uint64_t workspace_bytes, void* stream)
+{ return caps::fm_extract_device(dIndex, index_bytes, dStart, dOutOff, q, dText, workspace, workspace_bytes, stream); }
+int CAPS_API(fm_extract)(const void* index, uint64_t index_bytes, const uint64_t* start, const uint64_t* out_off, uint64_t q, uint8_t* text,
+                         int device)
+{ return caps::fm_extract_host(index, index_bytes, start, out_off, q, text, device); }
 int CAPS_API(fm_count_device)(const void* dIndex, uint64_t index_bytes, const void* dPatterns, const void* dPatOff, uint64_t q,
                               void* dFirst, void* dCount, void* stream)
 { return caps::fm_count_device(dIndex, index_bytes, dPatterns, dPatOff, q, dFirst, dCount, stream); }

@@ -3,10 +3,16 @@
 //
 //     caps_sa <input_path> <output_path> [subproblem-count] [bounded-context] [--pretty-print] [--gpus N] [--bwt PATH]
 //     caps_sa --inverse-bwt IN.bwt OUT
-//     caps_sa <input_path> <output_path> [subproblem-count] --fm-index PATH [--fm-sample S]
+//     caps_sa <input_path> <output_path> [subproblem-count] --fm-index PATH [--fm-sample S] [--fm-text-sample T]
 //     caps_sa --fm-search INDEX PATTERNS [--locate K]
-//     caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S]
+//     caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S] [--fm-text-sample T]
+//     caps_sa --fm-extract INDEX RANGES
 //
+// * --fm-text-sample T (not in the reference; with --fm-index PATH or --fm-from-bwt): the index is written in format version 2
+//   (include/caps_sa_hip.h "FM-index: extract"), with the row of every T-th text position; T a power of two, S .. 1024;
+// * --fm-extract INDEX RANGES (not in the reference): one "start length" pair per line of RANGES; per line the text
+//   T[start .. start + length) of the (remapped) text, from the index alone.  A malformed line, a range past n, an index of format
+//   version 1 and any other argument are refused before anything is printed;
 // * --fm-from-bwt IN.bwt OUT.fm [--fm-sample S] (not in the reference): the FM-index WITH its SA samples from a file that --bwt
 //   wrote and nothing else (include/caps_sa_hip.h "FM-index from the BWT alone"): byte for byte what --fm-index writes for the
 //   same text.  IN is read and checked as --inverse-bwt does; 32-bit indices for n <= UINT32_MAX; every refusal comes before OUT
@@ -73,7 +79,7 @@ static bool parse_count(const std::string& s, size_t& out)
 
 template <typename idx_t>
 static int run(const std::string& text, const std::string& out_path, size_t p, size_t ctx, bool pretty, const std::vector<int>& devices,
-               const std::string& bwt_path, const std::string& fm_path = std::string(), uint32_t fm_sample = 32)
+               const std::string& bwt_path, const std::string& fm_path = std::string(), uint32_t fm_sample = 32, uint32_t fm_text_sample = 0)
 {
     if (p > std::numeric_limits<idx_t>::max()) { std::cerr << "subproblem-count does not fit the index type\n"; return EXIT_FAILURE; }
     // the bounded-context mode replays the reference's merge history, one GPU thread per merge node -- the top levels
@@ -109,9 +115,12 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
         if (!bwt) return EXIT_FAILURE;
     }
     if (!fm_path.empty()) {
-        const CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::build<idx_t>(suf_arr.BWT(), suf_arr.n(), suf_arr.primary(), suf_arr.SA(), fm_sample);
+        CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::build<idx_t>(suf_arr.BWT(), suf_arr.n(), suf_arr.primary(), suf_arr.SA(), fm_sample);
+        if (fm_text_sample) fm.add_text_samples(fm_text_sample);
         fm.save(fm_path);
-        std::cerr << "FM-index: " << fm.size() << " bytes, SA samples every " << fm_sample << " positions.\n";
+        std::cerr << "FM-index: " << fm.size() << " bytes, SA samples every " << fm_sample << " positions";
+        if (fm_text_sample) std::cerr << ", text samples every " << fm_text_sample;
+        std::cerr << ".\n";
     }
     return 0;
 }
@@ -186,27 +195,103 @@ static bool read_bwt_file(const char* opt, const std::string& in_path, std::stri
 // caps_sa --fm-from-bwt IN OUT [--fm-sample S]: args = everything after the program name
 static int fm_from_bwt_main(const std::vector<std::string>& args)
 {
-    const char* usage = "--fm-from-bwt: usage: caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S] (no other option or argument)\n";
-    if ((args.size() != 3 && args.size() != 5) || args[0] != "--fm-from-bwt" || args[1].compare(0, 2, "--") == 0 ||
-        args[2].compare(0, 2, "--") == 0 || (args.size() == 5 && args[3] != "--fm-sample")) {
+    const char* usage = "--fm-from-bwt: usage: caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S] [--fm-text-sample T] (no other option or argument)\n";
+    if ((args.size() != 3 && args.size() != 5 && args.size() != 7) || args[0] != "--fm-from-bwt" || args[1].compare(0, 2, "--") == 0 ||
+        args[2].compare(0, 2, "--") == 0) {
         std::cerr << usage;
         return EXIT_FAILURE;
     }
-    size_t sample = 32;
-    if (args.size() == 5 && (!parse_count(args[4], sample) || sample < 1 || sample > 1024 || (sample & (sample - 1)))) {
-        std::cerr << "--fm-sample: a power of two in 1 .. 1024, please\n";
+    size_t sample = 32, text_sample = 0;
+    bool have_sample = false, have_text = false;
+    for (size_t i = 3; i < args.size(); i += 2) {            // each option once, with its value
+        if (args[i] == "--fm-sample" && !have_sample) have_sample = true;
+        else if (args[i] == "--fm-text-sample" && !have_text) have_text = true;
+        else { std::cerr << usage; return EXIT_FAILURE; }
+    }
+    for (size_t i = 3; i < args.size(); i += 2) {
+        if (args[i] == "--fm-sample" && (!parse_count(args[i + 1], sample) || sample < 1 || sample > 1024 || (sample & (sample - 1)))) {
+            std::cerr << "--fm-sample: a power of two in 1 .. 1024, please\n";
+            return EXIT_FAILURE;
+        }
+        if (args[i] == "--fm-text-sample" && (!parse_count(args[i + 1], text_sample) || text_sample < 1 || text_sample > 1024 || (text_sample & (text_sample - 1)))) {
+            std::cerr << "--fm-text-sample: a power of two in the --fm-sample distance .. 1024, please\n";
+            return EXIT_FAILURE;
+        }
+    }
+    if (have_text && text_sample < sample) {
+        std::cerr << "--fm-text-sample: a power of two in the --fm-sample distance .. 1024, please (--fm-sample is " << sample << ")\n";
         return EXIT_FAILURE;
     }
     std::string data;
     uint64_t n = 0, primary = 0;
     if (!read_bwt_file("--fm-from-bwt", args[1], data, n, primary)) return EXIT_FAILURE;
     try {
-        const CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::build_from_bwt(reinterpret_cast<const uint8_t*>(data.data() + 16), n, primary,
-                                                                       static_cast<uint32_t>(sample));
+        CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::build_from_bwt(reinterpret_cast<const uint8_t*>(data.data() + 16), n, primary,
+                                                                 static_cast<uint32_t>(sample));
+        if (have_text) fm.add_text_samples(static_cast<uint32_t>(text_sample));
         fm.save(args[2]);
-        std::cerr << "FM-index: " << fm.size() << " bytes, SA samples every " << sample << " positions.\n";
+        std::cerr << "FM-index: " << fm.size() << " bytes, SA samples every " << sample << " positions";
+        if (have_text) std::cerr << ", text samples every " << text_sample;
+        std::cerr << ".\n";
     } catch (const std::exception& e) {
         std::cerr << e.what() << "\n";
+        return EXIT_FAILURE;
+    }
+    return 0;
+}
+
+// caps_sa --fm-extract INDEX RANGES: args = everything after the program name
+static int fm_extract_main(const std::vector<std::string>& args)
+{
+    const char* usage = "--fm-extract: usage: caps_sa --fm-extract INDEX RANGES (no other option or argument)\n";
+    if (args.size() != 3 || args[0] != "--fm-extract" || args[1].compare(0, 2, "--") == 0 || args[2].compare(0, 2, "--") == 0) {
+        std::cerr << usage;
+        return EXIT_FAILURE;
+    }
+    std::string lines;
+    if (!read_input(args[2], lines)) { std::cerr << "--fm-extract: no ranges read\n"; return EXIT_FAILURE; }
+    std::vector<uint64_t> start, off(1, 0);
+    size_t line_no = 0;
+    for (size_t a = 0; a < lines.size();) {                  // "start length", one blank or tab between them, nothing else
+        size_t b = lines.find('\n', a);
+        if (b == std::string::npos) b = lines.size();
+        size_t e = b;
+        if (e > a && lines[e - 1] == '\r') --e;
+        ++line_no;
+        const std::string line = lines.substr(a, e - a);
+        const size_t sp = line.find_first_of(" \t");
+        size_t s = 0, len = 0;
+        if (sp == std::string::npos || !parse_count(line.substr(0, sp), s) || !parse_count(line.substr(sp + 1), len)) {
+            std::cerr << "--fm-extract: " << args[2] << " line " << line_no << ": expected \"start length\", two numbers\n";
+            return EXIT_FAILURE;
+        }
+        start.push_back(s);
+        off.push_back(off.back() + len);
+        a = b + 1;
+    }
+    try {
+        const CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::load(args[1]);
+        if (fm.size() < 256 || std::memcmp(fm.data(), "CAPSFMI1", 8) != 0) {
+            std::cerr << "--fm-extract: " << args[1] << " is not an FM-index of this library\n";
+            return EXIT_FAILURE;
+        }
+        if (fm.text_sample() == 0) {
+            std::cerr << "--fm-extract: " << args[1] << " has no text-position samples (format version 1): build it with --fm-text-sample T\n";
+            return EXIT_FAILURE;
+        }
+        for (size_t j = 0; j < start.size(); ++j)
+            if (start[j] > fm.n() || off[j + 1] - off[j] > fm.n() - start[j]) {
+                std::cerr << "--fm-extract: " << args[2] << " line " << j + 1 << ": the range ends past the text (n = " << fm.n() << ")\n";
+                return EXIT_FAILURE;
+            }
+        std::string text;
+        fm.extract(start, off, text);
+        for (size_t j = 0; j < start.size(); ++j) {
+            std::cout.write(text.data() + off[j], static_cast<std::streamsize>(off[j + 1] - off[j]));
+            std::cout << '\n';
+        }
+    } catch (const std::exception& e) {
+        std::cerr << "--fm-extract: " << e.what() << "\n";
         return EXIT_FAILURE;
     }
     return 0;
@@ -245,9 +330,11 @@ int main(int argc, char* argv[])
         if (std::strcmp(argv[i], "--fm-search") == 0) return fm_search_main(std::vector<std::string>(argv + 1, argv + argc));
     for (int i = 1; i < argc; ++i)
         if (std::strcmp(argv[i], "--fm-from-bwt") == 0) return fm_from_bwt_main(std::vector<std::string>(argv + 1, argv + argc));
+    for (int i = 1; i < argc; ++i)
+        if (std::strcmp(argv[i], "--fm-extract") == 0) return fm_extract_main(std::vector<std::string>(argv + 1, argv + argc));
     std::vector<std::string> pos;
-    bool pretty = false, bwt = false, fm = false, fm_sample_given = false;
-    size_t gpus = 1, fm_sample = 32;
+    bool pretty = false, bwt = false, fm = false, fm_sample_given = false, fm_text_given = false;
+    size_t gpus = 1, fm_sample = 32, fm_text_sample = 0;
     std::string bwt_path, fm_path;
     for (int i = 1; i < argc; ++i) {
         if (std::strcmp(argv[i], "--pretty-print") == 0) pretty = true;
@@ -266,6 +353,14 @@ int main(int argc, char* argv[])
                 return EXIT_FAILURE;
             }
         }
+        else if (std::strcmp(argv[i], "--fm-text-sample") == 0) {
+            fm_text_given = true;
+            if (i + 1 >= argc || !parse_count(argv[++i], fm_text_sample) || fm_text_sample < 1 || fm_text_sample > 1024 ||
+                (fm_text_sample & (fm_text_sample - 1))) {
+                std::cerr << "--fm-text-sample: a power of two in the --fm-sample distance .. 1024, please\n";
+                return EXIT_FAILURE;
+            }
+        }
         else if (std::strcmp(argv[i], "--locate") == 0) { std::cerr << "--locate: only with --fm-search\n"; return EXIT_FAILURE; }
         else if (std::strcmp(argv[i], "--gpus") == 0 && i + 1 < argc) {
             if (!parse_count(argv[++i], gpus) || gpus < 1 || gpus > 64) { std::cerr << "--gpus: a device count, please\n"; return EXIT_FAILURE; }
@@ -274,10 +369,11 @@ int main(int argc, char* argv[])
     if (pos.size() < 2) {
         std::cerr << "Usage: caps_sa <input_path> <output_path> <(optional)-subproblem-count> "
                      "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH> "
-                     "<(optional)--fm-index PATH [--fm-sample S]>\n"
+                     "<(optional)--fm-index PATH [--fm-sample S] [--fm-text-sample T]>\n"
                      "       caps_sa --inverse-bwt IN.bwt OUT\n"
                      "       caps_sa --fm-search INDEX PATTERNS [--locate K]\n"
-                     "       caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S]\n";
+                     "       caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S] [--fm-text-sample T]\n"
+                     "       caps_sa --fm-extract INDEX RANGES\n";
         return EXIT_FAILURE;
     }
     size_t p = 0, ctx = 0;
@@ -295,6 +391,11 @@ int main(int argc, char* argv[])
     }
     // --fm-index: the same manners
     if (fm_sample_given && !fm) { std::cerr << "--fm-sample: only with --fm-index PATH\n"; return EXIT_FAILURE; }
+    if (fm_text_given && !fm) { std::cerr << "--fm-text-sample: only with --fm-index PATH or --fm-from-bwt\n"; return EXIT_FAILURE; }
+    if (fm_text_given && fm_text_sample < fm_sample) {
+        std::cerr << "--fm-text-sample: a power of two in the --fm-sample distance .. 1024, please (--fm-sample is " << fm_sample << ")\n";
+        return EXIT_FAILURE;
+    }
     if (fm) {
         if (fm_path.empty()) { std::cerr << "--fm-index: missing output path (--fm-index PATH)\n"; return EXIT_FAILURE; }
         if (gpus > 1) { std::cerr << "--fm-index: the index is built on one GPU; --gpus " << gpus << " has no BWT to build it from\n"; return EXIT_FAILURE; }
@@ -326,8 +427,8 @@ int main(int argc, char* argv[])
 
     std::cerr << "Text length: " << text.size() << ".\n";
     try {
-        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample);
-        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample);
+        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample);
+        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample);
     } catch (const std::exception& e) {
         std::cerr << e.what() << "\n";
         return EXIT_FAILURE;

@@ -5138,6 +5138,10 @@ struct FmView {
     const void* mrank;                         // idx_t[n_blocks]
     const void* samples;                       // idx_t[n_samples]
     uint32_t sigma, syms, s;                   // syms: byte k = the letter of code k
+    // format version 2 (else null, 0, 0): rowof[k] = the row of the suffix at text position k * t, idx_t[n_text_samples]
+    const void* rowof;
+    uint64_t n_text_samples;
+    uint32_t t;
 };
 
 // the code of byte b under the alphabet (syms, sigma): the number of letters below it in signed-char order (b need not be a letter)
@@ -5688,6 +5692,151 @@ GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_place_kernel(KCTX FmView v, const idx_t* __res
                     }
                     const uint64_t si = (uint64_t)static_cast<const idx_t*>(v.mrank)[blk] + below;
                     if (si < v.n_samples) samples[si] = (idx_t)(i * v.s);
+                }
+            }
+        }
+    }
+}
+
+
+// ---- text-position samples and extract (capi_impl.h fm_add_text_samples_* / fm_extract_*; include/caps_sa_hip.h "FM-index: extract") --
+// rowof[k] = the row of the suffix at text position k * t is the inverse of the SA samples at the multiples of t (s | t: every one of
+// them is a sample), so it comes from the finished blob alone.  extract walks LF DOWN the text from the sample above a chunk of t
+// positions: the stored code of the row of the suffix at e is T[e - 1].
+
+// one lane per mark word: the samples of its marked rows (samples[mrank[block] + marks below], the locate kernel's rule); a sample
+// v = k * t gives rowof[k] = the row.  Every sample index and every k is compared with its section's size before it is used.
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_rowof_kernel(KCTX FmView v, uint32_t t, uint64_t m, idx_t* __restrict__ rowof)
+{
+    using G = FmGeom<idx_t>;
+    const uint64_t words = v.n_blocks * G::MWN, stride = (uint64_t)K_GRID_DIM * FM_NT;
+    const uint32_t sh = (uint32_t)__builtin_ctz(t | (FM_MAX_SAMPLE << 1));
+    for (uint64_t w0 = (uint64_t)K_BLOCK_IDX * FM_NT; w0 < words; w0 += stride) {  // block-uniform
+        PAR(tid) {
+            const uint64_t w = w0 + tid;
+            if (w < words) {
+                const uint64_t blk = w / G::MWN;
+                const uint32_t* p = v.occ + blk * G::BW + G::MW0;
+                uint32_t mk = p[w % G::MWN];
+                if (mk) {
+                    uint64_t a = (uint64_t)static_cast<const idx_t*>(v.mrank)[blk];
+                    for (uint32_t i = 0; i < (uint32_t)(w % G::MWN); ++i) a += (uint32_t)__builtin_popcount(p[i]);
+                    while (mk) {
+                        const uint32_t b = (uint32_t)__builtin_ctz(mk);
+                        mk &= mk - 1;
+                        const uint64_t r = w * FM_MROWS + b;
+                        if (a < v.n_samples && r >= 1 && r <= v.n) {
+                            const uint64_t val = (uint64_t)STREAM_LOAD(&static_cast<const idx_t*>(v.samples)[a]);
+                            if ((val & (t - 1u)) == 0 && (val >> sh) < m) rowof[val >> sh] = (idx_t)r;
+                        }
+                        ++a;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// every rowof[k] is a row of the index, 1 .. n (a slot still 0: its sample is missing or stands twice) -- else flag 8
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_rowof_check_kernel(KCTX const idx_t* __restrict__ rowof, uint64_t m, uint64_t n, uint32_t* __restrict__ flags)
+{
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t k0 = (uint64_t)K_BLOCK_IDX * FM_NT; k0 < m; k0 += stride) {       // block-uniform
+        PAR(tid) {
+            const uint64_t k = k0 + tid;
+            if (k < m) {
+                const uint64_t r = (uint64_t)STREAM_LOAD(&rowof[k]);
+                if (r == 0 || r > n) ATOMIC_OR_U32(flags, 8u);
+            }
+        }
+    }
+}
+
+// extract's entry checks and plan: off[0 .. q] monotone (flag 1), start + len <= n without overflow (flag 2); cnt[j] = the chunks
+// [k * t, (k + 1) * t) that query j touches (0 for an empty or refused one), scanned by fm_scan_kernel afterwards
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_extract_plan_kernel(KCTX const uint64_t* __restrict__ start, const uint64_t* __restrict__ off, uint64_t q,
+                                                       uint64_t n, uint32_t sh, uint64_t* __restrict__ cnt, uint32_t* __restrict__ flags)
+{
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t j0 = (uint64_t)K_BLOCK_IDX * FM_NT; j0 < q; j0 += stride) {       // block-uniform
+        PAR(tid) {
+            const uint64_t j = j0 + tid;
+            if (j < q) {
+                const uint64_t a = off[j], b = off[j + 1], s = start[j], len = b >= a ? b - a : 0;
+                uint32_t f = b < a ? 1u : 0u;
+                if (s > n || len > n - s) f |= 2u;
+                cnt[j] = !f && len ? ((s + len - 1) >> sh) - (s >> sh) + 1 : 0;
+                if (f) ATOMIC_OR_U32(flags, f);
+            }
+        }
+    }
+}
+
+// extract: one lane per (query, chunk) pair g in [0, lanes): its query j by bisection over the scanned chunk counts pre[0 .. q]
+// (the locate kernel's over off), its chunk k = start / t + (g - pre[j]).  From E = min((k + 1) t, n), row rowof[k + 1] (row 0 for
+// E = n: the suffix at n, L[0] = T[n - 1]), down to max(k t, start): at most t steps, each one block.  A byte goes out when its
+// position lies below start + len.  WORDS: the letters are gathered in a register and an aligned 32-bit word of text is stored as
+// one word only when all 4 of its bytes are this lane's; the bytes at both ends of the lane's range are byte stores (the
+// neighbouring bytes belong to other lanes: never read, never rewritten).  flag 4: a rowof index outside its section, or the '$'
+// row or row 0 met in mid-walk.
+template <typename idx_t, bool WORDS>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_extract_kernel(KCTX FmView v, const uint64_t* __restrict__ start, const uint64_t* __restrict__ off,
+                                                  const uint64_t* __restrict__ pre, uint64_t q, uint64_t lanes, uint8_t* __restrict__ text,
+                                                  uint32_t* __restrict__ flags)
+{
+    using G = FmGeom<idx_t>;
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    const uint32_t sh = (uint32_t)__builtin_ctz(v.t | (FM_MAX_SAMPLE << 1));
+    for (uint64_t g0 = (uint64_t)K_BLOCK_IDX * FM_NT; g0 < lanes; g0 += stride) {   // block-uniform
+        PAR(tid) {
+            const uint64_t g = g0 + tid;
+            if (g < lanes) {
+                uint64_t a = 0, b = q;                                              // the last j with pre[j] <= g
+                while (b - a > 1) { const uint64_t mid = a + (b - a) / 2; if (pre[mid] <= g) a = mid; else b = mid; }
+                const uint64_t s = start[a], o = off[a], o1 = off[a + 1], k = (s >> sh) + (g - pre[a]);
+                if (pre[a] <= g && o1 >= o && s <= v.n && o1 - o <= v.n - s && k <= (v.n >> sh)) {
+                    const uint64_t hi = s + (o1 - o), lo = std::max<uint64_t>(k << sh, s), E = std::min<uint64_t>((k + 1) << sh, v.n);
+                    bool ok = true;
+                    uint64_t r = 0;
+                    if (E < v.n) {
+                        if (k + 1 < v.n_text_samples) r = std::min<uint64_t>((uint64_t)static_cast<const idx_t*>(v.rowof)[k + 1], v.n);
+                        else ok = false;
+                    }
+                    uint32_t acc = 0, have = 0;                                     // WORDS: the bytes gathered at wp .. wp + have - 1
+                    uint8_t* wp = nullptr;
+                    for (uint64_t e = E; ok && e > lo; --e) {
+                        if (r == v.primary + 1 || (r == 0 && e != v.n)) { ok = false; break; }
+                        const uint32_t* p = fm_block_of<idx_t>(v, r);
+                        const uint32_t kk = (uint32_t)(r % G::ROWS);
+                        const uint32_t c = (p[G::CW0 + kk / FM_WROWS] >> (2u * (kk % FM_WROWS))) & 3u;
+                        if (e - 1 < hi) {
+                            uint8_t* dst = text + o + (e - 1 - s);
+                            const uint32_t letter = (v.syms >> (8u * c)) & 0xFFu;
+                            if (WORDS) {
+                                const uint32_t at = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u);
+                                acc |= letter << (8u * at);
+                                ++have;
+                                wp = dst;
+                                if (at == 0) {
+                                    if (have == 4) *reinterpret_cast<uint32_t*>(dst) = acc;
+                                    else for (uint32_t i = 0; i < have; ++i) dst[i] = (uint8_t)(acc >> (8u * i));
+                                    acc = 0;
+                                    have = 0;
+                                }
+                            } else {
+                                *dst = (uint8_t)letter;
+                            }
+                        }
+                        const uint64_t x = fm_c_of(v, c) + fm_block_occ<idx_t>(p, c, kk, r > v.primary + 1);
+                        r = x <= v.n ? x : v.n;
+                    }
+                    if (WORDS && have) {
+                        const uint32_t at = (uint32_t)(reinterpret_cast<uintptr_t>(wp) & 3u);
+                        for (uint32_t i = 0; i < have; ++i) wp[i] = (uint8_t)(acc >> (8u * (at + i)));
+                    }
+                    if (!ok) ATOMIC_OR_U32(flags, 4u);
                 }
             }
         }

@@ -316,7 +316,8 @@ int caps_sa_hip_inverse_bwt_u64(const uint8_t* BWT, uint64_t n, uint64_t primary
  *             walk by sa_sample LF steps
  * caps_sa_hip_fm_index_bytes(n, 32, 4) = 0.66 n, (n, 32, 8) = 0.78 n, (n, 0, 4) = 0.5 n bytes (+ the header).
  *
- * The blob, byte by byte (format version 1; every number little-endian). W = the index width in bytes (4 or 8), ROWS = 128 for
+ * The blob, byte by byte (format version 1; every number little-endian; version 2 -- "FM-index: extract" below -- appends one
+ * section and sets words 1 and 19 .. 22). W = the index width in bytes (4 or 8), ROWS = 128 for
  * W = 4 and 256 for W = 8. The header is 32 64-bit words:
  *   word  0        magic: the 8 bytes "CAPSFMI1" (0x31494D4653504143)
  *   word  1        format version = 1
@@ -432,6 +433,63 @@ int caps_sa_hip_fm_build_from_bwt_u32(const uint8_t* BWT, uint64_t n, uint64_t p
                                       void* index, uint64_t index_bytes, int device);
 int caps_sa_hip_fm_build_from_bwt_u64(const uint8_t* BWT, uint64_t n, uint64_t primary, uint32_t sa_sample,
                                       void* index, uint64_t index_bytes, int device);
+
+/* ---- FM-index: extract -- text substrings from the index alone ---------------------------
+ *
+ * extract(i, l) = T[i .. i + l), the third operation of a self-index: a caller who keeps only the blob can show the flanks of a hit,
+ * verify a match or cut a window of the text, without the text and without inverting the whole BWT. The stored code of the row of
+ * the suffix at text position e is T[e - 1] and LF leads from that row to the row of the suffix at e - 1, so the text is read
+ * DOWNWARDS from any position whose row is known. Format version 2 adds those rows for every text_sample-th position.
+ *
+ * The blob, format version 2: a version-1 blob WITH samples plus one section behind it. Words 0 and 2 .. 18 and every byte of the
+ * Occ, mark-rank and sample sections are those of version 1 (word 18 keeps its meaning: the end of the version-1 sections).
+ *   word  1        format version = 2
+ *   word  19       text_sample t: a power of two with sa_sample <= t <= 1024
+ *   word  20       m = number of text samples = (n - 1) / t + 1 (0 when n = 0)
+ *   word  21       offset of the section = word 18
+ *   word  22       total = word 21 + m * W rounded up to a multiple of 64
+ *   words 23 .. 31 zero
+ * Section: rowof[k], W bytes each, k = 0 .. m - 1: the row, in 1 .. n, of the suffix that starts at text position k * t (1 + its
+ * SA rank), so rowof[0] = primary + 1. The padding is zero. count and locate give on a version-2 blob what they give on its
+ * version-1 part; a reader of version 1 refuses version 2 by its version word.
+ *
+ * caps_sa_hip_fm_add_text_samples_*: in place, a version-1 blob WITH samples becomes version 2 (a version-2 blob: its section is
+ * rebuilt at the new distance). The section comes from the blob itself -- a marked row r carries the sample v = samples[mrank[block]
+ * + marks below r in its block]; v a multiple of t gives rowof[v / t] = r; sa_sample divides t, so every multiple of t is a sample
+ * -- in one pass over the mark words and the samples: the same call serves blobs built with the SA, from the BWT alone, or read
+ * from a file. index_bytes is the CAPACITY of the buffer: below caps_sa_hip_fm_index_bytes_ex(n, sa_sample, t, W) is
+ * CAPS_SA_EINVAL with nothing written. An index without samples: CAPS_SA_EUNSUPPORTED. t not a power of two in sa_sample .. 1024:
+ * CAPS_SA_EINVAL. n = 0 succeeds with m = 0. A blob whose samples leave a rowof slot empty or outside 1 .. n (a sample missing or
+ * twice: not an index this library built) is CAPS_SA_EINVAL and its header says version 1. The host form rewrites the caller's blob
+ * (header and section) and leaves the device copy of the host queries equal to it.
+ *
+ * caps_sa_hip_fm_extract_*: query j asks for len_j = dOutOff[j + 1] - dOutOff[j] bytes from text position dStart[j]:
+ *   dText[dOutOff[j] .. dOutOff[j + 1]) = T[dStart[j] .. dStart[j] + len_j)
+ * as the original letters (header word 6). The positions are cut into chunks [k t, (k + 1) t); one GPU lane serves one (query,
+ * chunk) pair, starts at the chunk's upper end E = min((k + 1) t, n) in row rowof[k + 1] (row 0 for E = n: no sample is needed at
+ * the text's end) and takes at most t LF steps, one Occ block each, down to max(k t, start): a query of length l costs about
+ * l + t steps on l / t + 1 lanes, and extract(0, n) runs over the whole GPU. Bytes of dText outside every range are not written.
+ * Workspace: caps_sa_hip_fm_extract_workspace_bytes(q) = 8 (q + 1) bytes and alignment slack, the scanned chunk counts; NULL is
+ * allocated and freed by the call. Errors: the header is checked on the host as for count; a version-1 blob is
+ * CAPS_SA_EUNSUPPORTED; non-monotone dOutOff, start + len > n (computed without overflow), a null pointer with q > 0, a workspace
+ * that is too small: CAPS_SA_EINVAL with nothing written. q = 0 and a batch of empty ranges succeed. The kernel compares every row,
+ * block and rowof index with its section's size before it is used; a walk that meets the '$' row or row 0 below its sample means
+ * the blob is not an index this library built: CAPS_SA_EINVAL, dText unspecified.
+ */
+
+/* Size of a version-2 index: sa_sample a power of two in 1 .. 1024, text_sample a power of two in sa_sample .. 1024. */
+int caps_sa_hip_fm_index_bytes_ex(uint64_t n, uint32_t sa_sample, uint32_t text_sample, int idx_bytes, uint64_t* bytes);
+/* dIndex: a device pointer on the current device, index_bytes its capacity; runs on hip_stream and has completed on return. */
+int caps_sa_hip_fm_add_text_samples_device(void* dIndex, uint64_t index_bytes, uint32_t text_sample, void* hip_stream);
+/* The same on a blob in host memory (index_bytes: the capacity of the buffer), on the device block of the host-buffer builds. */
+int caps_sa_hip_fm_add_text_samples(void* index, uint64_t index_bytes, uint32_t text_sample, int device);
+int caps_sa_hip_fm_extract_workspace_bytes(uint64_t q, uint64_t* bytes);
+/* dStart: u64[q], dOutOff: u64[q + 1], dText: u8[dOutOff[q]] (written), workspace (or NULL): device pointers on the current device. */
+int caps_sa_hip_fm_extract_device(const void* dIndex, uint64_t index_bytes, const void* dStart, const void* dOutOff, uint64_t q,
+                                  void* dText, void* workspace, uint64_t workspace_bytes, void* hip_stream);
+/* The same on host buffers; the index is uploaded as for caps_sa_hip_fm_count. text[out_off[0] .. out_off[q]) is written. */
+int caps_sa_hip_fm_extract(const void* index, uint64_t index_bytes, const uint64_t* start, const uint64_t* out_off, uint64_t q,
+                           uint8_t* text, int device);
 
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
