@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from ._binding import CapsLib, CapsSaError, Stats, Shard, ShardInfo, EXPORTS  # noqa: F401
+from ._binding import CapsLib, CapsSaError, Stats, Shard, ShardInfo, EXPORTS, MEM_DTYPE  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CAPS_SA_LIB selects a tuning variant built by `make variant` (benchmarking only).
@@ -129,8 +129,8 @@ class SuffixArray:
 
 
 class FMIndex:
-    """FM-index over (BWT, primary) (include/caps_sa_hip.h "FM-index"): batched ``count``, ``locate`` and (after ``with_text_samples``)
-    ``extract`` on the GPU for texts of at most 4 distinct bytes.  The index is one blob (``blob``, np.uint8; ``nbytes``); ``save`` / ``load`` write and read exactly it."""
+    """FM-index over (BWT, primary) (include/caps_sa_hip.h "FM-index"): batched ``count``, ``locate``, ``matching_statistics``, ``mems`` and (after
+    ``with_text_samples``) ``extract`` on the GPU for texts of at most 4 distinct bytes.  The index is one blob (``blob``, np.uint8; ``nbytes``); ``save`` / ``load`` write and read exactly it."""
 
     def __init__(self, blob: np.ndarray, device: int = 0, _lib: CapsLib | None = None):
         self.blob = np.ascontiguousarray(blob, dtype=np.uint8)
@@ -188,6 +188,24 @@ class FMIndex:
         off[1:] = np.cumsum(take, dtype=np.uint64)
         pos, _ = self._l().fm_locate(self.blob, first, count, off, self._device)
         return [pos[int(off[j]):int(off[j + 1])] for j in range(take.size)]
+
+    def matching_statistics(self, patterns, max_len: int = 0, intervals: bool = False):
+        """Per pattern P an np.uint32 array L of len(P) entries: L[e - 1] = the length of the longest piece of P ending at e that
+        occurs in the text (at most max_len when max_len > 0; 0 when P[e - 1] is no letter of the index).  intervals=True:
+        (L, first, count) lists -- the piece's occurrences are SA[first : first + count].  Needs no SA samples."""
+        ln, first, count, off = self._l().fm_match(self.blob, patterns, max_len, intervals, self._device)
+        cut = [(int(off[j] - off[0]), int(off[j + 1] - off[0])) for j in range(off.size - 1)]
+        lens = [ln[a:b] for a, b in cut]
+        if not intervals:
+            return lens
+        return lens, [first[a:b] for a, b in cut], [count[a:b] for a, b in cut]
+
+    def mems(self, patterns, min_len: int = 1) -> list:
+        """Per pattern its maximal exact matches of at least min_len bytes, by increasing end: a structured array with the fields
+        ``start`` (within the pattern), ``length``, ``first`` and ``count`` (occurrences SA[first : first + count])."""
+        rec, off = self._l().fm_mems(self.blob, patterns, min_len, self._device)
+        rec = rec[["start", "length", "first", "count"]]
+        return [rec[int(off[j]):int(off[j + 1])] for j in range(off.size - 1)]
 
     @property
     def text_sample(self) -> int:

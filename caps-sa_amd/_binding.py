@@ -122,13 +122,18 @@ SHARD_EXPORTS = ["shard_create", "shard_destroy", "shard_info", "shard_phase1", 
 
 EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_bytes", "workspace_bytes", "workspace_bytes_ex", "release_cache", "host_alloc", "host_free", "gen_rand_seq",
            "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_from_bwt_workspace_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device",
-           "fm_index_bytes_ex", "fm_add_text_samples", "fm_add_text_samples_device", "fm_extract_workspace_bytes", "fm_extract", "fm_extract_device"] + SHARD_EXPORTS + [
+           "fm_index_bytes_ex", "fm_add_text_samples", "fm_add_text_samples_device", "fm_extract_workspace_bytes", "fm_extract", "fm_extract_device",
+           "fm_match", "fm_match_device", "fm_mems_workspace_bytes", "fm_mems", "fm_mems_device"] + SHARD_EXPORTS + [
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
     for name in ("build", "build_multi", "build_device", "verify_device", "verify_slice_device", "sort_suffixes", "sort_segments", "merge",
                  "upper_bound", "lcp", "build_bwt", "bwt_device", "inverse_bwt", "inverse_bwt_device", "fm_build", "fm_build_device",
                  "fm_build_from_bwt", "fm_build_from_bwt_device")
 ]
+
+
+# a MEM record of fm_mems (include/caps_sa_hip.h "FM-index: matching statistics"): 32 bytes, little-endian
+MEM_DTYPE = np.dtype([("pattern", "<u8"), ("start", "<u4"), ("length", "<u4"), ("first", "<u8"), ("count", "<u8")])
 
 
 class CapsSaError(RuntimeError):
@@ -195,6 +200,16 @@ class CapsLib:
         f("fm_extract").argtypes = [_vp, _u64, _vp, _vp, _u64, _vp, _ci]
         f("fm_extract_device").restype = _ci
         f("fm_extract_device").argtypes = [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp]
+        f("fm_match").restype = _ci
+        f("fm_match").argtypes = [_vp, _u64, _vp, _vp, _u64, ctypes.c_uint32, _vp, _vp, _vp, _ci]
+        f("fm_match_device").restype = _ci
+        f("fm_match_device").argtypes = [_vp, _u64, _vp, _vp, _u64, ctypes.c_uint32, _vp, _vp, _vp, _vp]
+        f("fm_mems_workspace_bytes").restype = _ci
+        f("fm_mems_workspace_bytes").argtypes = [_u64, _u64, ctypes.POINTER(_u64)]
+        f("fm_mems").restype = _ci
+        f("fm_mems").argtypes = [_vp, _u64, _vp, _vp, _u64, ctypes.c_uint32, _vp, _vp, _u64, _ci]
+        f("fm_mems_device").restype = _ci
+        f("fm_mems_device").argtypes = [_vp, _u64, _vp, _vp, _u64, ctypes.c_uint32, _vp, _vp, _u64, _vp, _u64, _vp]
         f("fm_from_bwt_workspace_bytes").restype = _ci
         f("fm_from_bwt_workspace_bytes").argtypes = [_u64, ctypes.c_uint32, _ci, ctypes.POINTER(_u64)]
         for sfx in ("u32", "u64"):
@@ -579,6 +594,58 @@ class CapsLib:
         (fm_extract_workspace_bytes), or 0: allocated and freed by the call."""
         self._check(self._f("fm_extract_device")(dIndex_ptr or None, index_bytes, dStart_ptr or None, dOutOff_ptr or None, q,
                                                  dText_ptr or None, dWS_ptr or None, ws_bytes, stream or None))
+
+    # ------------------------------------------------------------------ FM-index: matching statistics and MEMs
+    def fm_match(self, index: np.ndarray, patterns, max_len: int = 0, intervals: bool = False, device: int = 0):
+        """(len np.uint32[total], first, count, pat_off): slot pat_off[j] - pat_off[0] + e - 1 holds L[e] of pattern j, the longest
+        piece ending at e that occurs in the text (at most max_len when max_len > 0); first / count (np.uint64, its SA interval) are
+        None unless intervals.  patterns as for fm_count."""
+        cat, off = patterns if isinstance(patterns, tuple) else self._patterns(patterns)
+        cat = np.ascontiguousarray(cat, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        q = off.size - 1
+        total = int(off[-1] - off[0]) if q > 0 else 0
+        ln = np.zeros(total, dtype=np.uint32)
+        first = np.zeros(total, dtype=np.uint64) if intervals else None
+        count = np.zeros(total, dtype=np.uint64) if intervals else None
+        self._check(self._f("fm_match")(index.ctypes.data, index.size, cat.ctypes.data if cat.size else None, off.ctypes.data, q, max_len,
+                                        ln.ctypes.data, first.ctypes.data if intervals else None, count.ctypes.data if intervals else None,
+                                        device))
+        return ln, first, count, off
+
+    def fm_match_device(self, dIndex_ptr: int, index_bytes: int, dPat_ptr: int, dPatOff_ptr: int, q: int, max_len: int, dLen_ptr: int,
+                        dFirst_ptr: int = 0, dCount_ptr: int = 0, stream: int = 0) -> None:
+        """Device arrays: dPatOff u64[q + 1], dLen u32[total], dFirst / dCount u64[total] or 0 (not written)."""
+        self._check(self._f("fm_match_device")(dIndex_ptr or None, index_bytes, dPat_ptr or None, dPatOff_ptr or None, q, max_len,
+                                               dLen_ptr or None, dFirst_ptr or None, dCount_ptr or None, stream or None))
+
+    def fm_mems_workspace_bytes(self, total_pattern_bytes: int, q: int) -> int:
+        out = _u64(0)
+        self._check(self._f("fm_mems_workspace_bytes")(total_pattern_bytes, q, ctypes.byref(out)))
+        return out.value
+
+    def fm_mems(self, index: np.ndarray, patterns, min_len: int = 1, device: int = 0):
+        """(records, mem_off): the maximal exact matches of at least min_len bytes as a structured array (MEM_DTYPE: pattern, start,
+        length, first, count) in (pattern, increasing end) order; records[mem_off[j] : mem_off[j + 1]] are pattern j's.  The
+        counting call, then the writing call."""
+        cat, off = patterns if isinstance(patterns, tuple) else self._patterns(patterns)
+        cat = np.ascontiguousarray(cat, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        q = off.size - 1
+        mem_off = np.zeros(q + 1, dtype=np.uint64)
+        args = (index.ctypes.data, index.size, cat.ctypes.data if cat.size else None, off.ctypes.data, q, min_len, mem_off.ctypes.data)
+        self._check(self._f("fm_mems")(*args, None, 0, device))
+        mems = np.zeros(int(mem_off[-1]), dtype=MEM_DTYPE)
+        if mems.size:
+            self._check(self._f("fm_mems")(*args, mems.ctypes.data, mems.size, device))
+        return mems, mem_off
+
+    def fm_mems_device(self, dIndex_ptr: int, index_bytes: int, dPat_ptr: int, dPatOff_ptr: int, q: int, min_len: int, dMemOff_ptr: int,
+                       dMems_ptr: int = 0, mem_capacity: int = 0, dWS_ptr: int = 0, ws_bytes: int = 0, stream: int = 0) -> None:
+        """Device arrays: dMemOff u64[q + 1] (always written), dMems 32-byte records or 0 (the counting call); workspace dWS_ptr of
+        ws_bytes (fm_mems_workspace_bytes), or 0: allocated and freed by the call."""
+        self._check(self._f("fm_mems_device")(dIndex_ptr or None, index_bytes, dPat_ptr or None, dPatOff_ptr or None, q, min_len,
+                                              dMemOff_ptr or None, dMems_ptr or None, mem_capacity, dWS_ptr or None, ws_bytes, stream or None))
 
     # ------------------------------------------------------------------ kernel-level entry points
     def sort_suffixes(self, T, idx, idx_bits: int = 32, device: int = 0):

@@ -19,7 +19,7 @@
 //  * construct_bwt() (not in the reference): construct() plus the Burrows-Wheeler transform (include/caps_sa_hip.h), one device;
 //    its n-byte buffer is allocated by the first construct_bwt(), so construct() callers pay nothing for it.
 //  * the free function inverse_bwt() (not in the reference): the text back from (BWT, primary).
-//  * the class FM_Index (not in the reference either): count, locate and extract over (BWT, primary) and a sample of the SA.
+//  * the class FM_Index (not in the reference either): count, locate, matching statistics, MEMs and extract over (BWT, primary) and a sample of the SA.
 #ifndef CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 #define CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 
@@ -235,6 +235,44 @@ public:
         pos.assign(static_cast<std::size_t>(out_off[q]), 0);
         check(caps_sa_hip_fm_locate(blob_.data(), blob_.size(), first.data(), cnt.data(), out_off.data(), q, pos.data(), device_),
               "caps_sa_hip_fm_locate");
+    }
+
+    // Matching statistics (include/caps_sa_hip.h "FM-index: matching statistics"): slot off[j] - off[0] + e - 1 of len = L[e] of
+    // pattern j, the longest piece ending at e that occurs in the text (at most max_len when max_len > 0); first / cnt: its SA
+    // interval, or null: not computed.  Needs no SA samples.
+    void matching_statistics(const std::string& patterns, const std::vector<uint64_t>& off, std::vector<uint32_t>& len,
+                             std::vector<uint64_t>* first = nullptr, std::vector<uint64_t>* cnt = nullptr, uint32_t max_len = 0) const
+    {
+        const uint64_t q = off.empty() ? 0 : off.size() - 1, total = q ? off[q] - off[0] : 0;
+        len.assign(static_cast<std::size_t>(total), 0);
+        if (first) first->assign(static_cast<std::size_t>(total), 0);
+        if (cnt) cnt->assign(static_cast<std::size_t>(total), 0);
+        check(caps_sa_hip_fm_match(blob_.data(), blob_.size(), reinterpret_cast<const uint8_t*>(patterns.data()), off.data(), q, max_len,
+                                   len.data(), first ? first->data() : nullptr, cnt ? cnt->data() : nullptr, device_), "caps_sa_hip_fm_match");
+    }
+
+    // A maximal exact match: P[start .. start + length) of pattern `pattern` occurs at SA[first .. first + count) and can be
+    // extended neither to the left nor to the right.  The 32-byte record of the C ABI.
+    struct Mem {
+        uint64_t pattern;
+        uint32_t start, length;
+        uint64_t first, count;
+    };
+
+    // The MEMs of at least min_len bytes in (pattern, increasing end) order; mems[mem_off[j] .. mem_off[j + 1]) are pattern j's.
+    // The counting call, then the writing call.
+    void mems(const std::string& patterns, const std::vector<uint64_t>& off, uint32_t min_len, std::vector<uint64_t>& mem_off,
+              std::vector<Mem>& mems) const
+    {
+        static_assert(sizeof(Mem) == 32, "the record of caps_sa_hip_fm_mems");
+        const uint64_t q = off.empty() ? 0 : off.size() - 1;
+        mem_off.assign(static_cast<std::size_t>(q + 1), 0);
+        const uint8_t* pat = reinterpret_cast<const uint8_t*>(patterns.data());
+        check(caps_sa_hip_fm_mems(blob_.data(), blob_.size(), pat, off.data(), q, min_len, mem_off.data(), nullptr, 0, device_), "caps_sa_hip_fm_mems");
+        mems.assign(static_cast<std::size_t>(mem_off[q]), Mem());
+        if (!mems.empty())
+            check(caps_sa_hip_fm_mems(blob_.data(), blob_.size(), pat, off.data(), q, min_len, mem_off.data(), mems.data(), mems.size(), device_),
+                  "caps_sa_hip_fm_mems");
     }
 
     // Format version 2 in place (include/caps_sa_hip.h "FM-index: extract"): one row per t text positions behind the version-1

@@ -2024,6 +2024,274 @@ inline int fm_extract_host(const void* index, uint64_t index_bytes, const uint64
     });
 }
 
+// ---- matching statistics and MEMs (include/caps_sa_hip.h "FM-index: matching statistics"; kernels.h fm_match_kernel, fm_mem_*) ----
+constexpr uint64_t FM_MAX_PATTERN = 0xFFFFFFFFull;           // bytes of a pattern: len[], a MEM's start and length are 32-bit
+constexpr uint64_t FM_MEM_BYTES = 32;
+
+// the entry checks of both calls on the caller's device offsets: monotone, no pattern above FM_MAX_PATTERN; -> [o_begin, o_end)
+inline int fm_match_offsets(Backend& be, const void* dPatOff, uint64_t q, uint64_t n, uint64_t& o_begin, uint64_t& o_end)
+{
+    uint64_t* words = fm_words(be);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(words);
+    const uint32_t g = capped_grid(std::min<uint64_t>((q + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+    be.memset(words, 0, sizeof(uint64_t));
+    CAPS_LAUNCH(fm_check_kernel, g, FM_NT, be, static_cast<const uint64_t*>(dPatOff), q, (const uint64_t*)nullptr, (const uint64_t*)nullptr, n, flags);
+    CAPS_LAUNCH(fm_patlen_check_kernel, g, FM_NT, be, static_cast<const uint64_t*>(dPatOff), q, FM_MAX_PATTERN, flags);
+    uint32_t f = 0;
+    be.d2h(&f, flags, sizeof f);
+    be.d2h(&o_begin, dPatOff, sizeof(uint64_t));
+    be.d2h(&o_end, static_cast<const uint64_t*>(dPatOff) + q, sizeof(uint64_t));
+    be.sync();
+    if (f & 1u) return fail(CAPS_SA_EINVAL, "pattern offsets are not monotone");
+    if (f & 16u) return fail(CAPS_SA_EINVAL, "a pattern is longer than 2^32 - 1 bytes");
+    return CAPS_SA_OK;
+}
+
+// the match kernel over [o_begin, o_end) (not empty); n = 0: every length 0
+inline void launch_fm_match(Backend& be, const FmView& v, int W, const void* dPat, const void* dPatOff, uint64_t q, uint64_t o_begin, uint64_t o_end,
+                            uint32_t max_len, uint32_t* len, uint64_t* first, uint64_t* count)
+{
+    const uint64_t total = o_end - o_begin;
+    if (v.n == 0) {
+        be.memset(len, 0, total * sizeof(uint32_t));
+        if (first) be.memset(first, 0, total * sizeof(uint64_t));
+        if (count) be.memset(count, 0, total * sizeof(uint64_t));
+        return;
+    }
+    const uint32_t g = capped_grid(std::min<uint64_t>((total + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+    if (W == 4)
+        CAPS_LAUNCH((fm_match_kernel<uint32_t>), g, FM_NT, be, v, static_cast<const uint8_t*>(dPat), static_cast<const uint64_t*>(dPatOff), q, o_begin,
+                    o_end, max_len, len, first, count);
+    else
+        CAPS_LAUNCH((fm_match_kernel<uint64_t>), g, FM_NT, be, v, static_cast<const uint8_t*>(dPat), static_cast<const uint64_t*>(dPatOff), q, o_begin,
+                    o_end, max_len, len, first, count);
+}
+
+// matching statistics on device arrays; `hdr` as in run_fm_count
+inline int run_fm_match(Backend& be, const void* dIndex, uint64_t index_bytes, const uint64_t* hdr, const void* dPat, const void* dPatOff, uint64_t q,
+                        uint32_t max_len, void* dLen, void* dFirst, void* dCount)
+{
+    uint64_t h[FM_HDR_WORDS];
+    if (hdr) std::memcpy(h, hdr, sizeof h);
+    else { be.d2h(h, dIndex, sizeof h); be.sync(); }
+    FmView v;
+    if (int rc = fm_check_header(h, index_bytes, dIndex, v)) return rc;
+    if (q == 0) return CAPS_SA_OK;
+    uint64_t o_begin = 0, o_end = 0;
+    if (int rc = fm_match_offsets(be, dPatOff, q, v.n, o_begin, o_end)) return rc;
+    if (o_end == o_begin) return CAPS_SA_OK;
+    if (!dPat || !dLen) return fail(CAPS_SA_EINVAL, "null pointer");
+    launch_fm_match(be, v, (int)h[FMH_IDX_BYTES], dPat, dPatOff, q, o_begin, o_end, max_len, static_cast<uint32_t*>(dLen),
+                    static_cast<uint64_t*>(dFirst), static_cast<uint64_t*>(dCount));
+    be.sync();
+    return CAPS_SA_OK;
+}
+
+inline int fm_match_device(const void* dIndex, uint64_t index_bytes, const void* dPat, const void* dPatOff, uint64_t q, uint32_t max_len,
+                           void* dLen, void* dFirst, void* dCount, void* stream)
+{
+    if (!dIndex) return fail(CAPS_SA_EINVAL, "null index");
+    if (index_bytes < FM_HDR_WORDS * sizeof(uint64_t)) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than an FM-index header");
+    if (q && (!dPatOff || !dLen)) return fail(CAPS_SA_EINVAL, "null pointer");
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        return run_fm_match(be, dIndex, index_bytes, nullptr, dPat, dPatOff, q, max_len, dLen, dFirst, dCount);
+    });
+}
+
+// the host checks of the pattern arrays of both calls
+inline int fm_match_host_check(const uint8_t* pat, const uint64_t* patoff, uint64_t q)
+{
+    if (!patoff) return fail(CAPS_SA_EINVAL, "null pointer");
+    for (uint64_t j = 0; j < q; ++j) {
+        if (patoff[j + 1] < patoff[j]) return fail(CAPS_SA_EINVAL, "pattern offsets are not monotone");
+        if (patoff[j + 1] - patoff[j] > FM_MAX_PATTERN) return fail(CAPS_SA_EINVAL, "a pattern is longer than 2^32 - 1 bytes");
+    }
+    if (patoff[q] && !pat) return fail(CAPS_SA_EINVAL, "null pointer");
+    return CAPS_SA_OK;
+}
+
+inline int fm_match_host(const void* index, uint64_t index_bytes, const uint8_t* pat, const uint64_t* patoff, uint64_t q, uint32_t max_len,
+                         uint32_t* len, uint64_t* first, uint64_t* count, int device)
+{
+    uint64_t h[FM_HDR_WORDS];
+    FmView v;
+    if (int rc = fm_host_header(index, index_bytes, h, v)) return rc;
+    if (q == 0) return CAPS_SA_OK;
+    if (!len) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (int rc = fm_match_host_check(pat, patoff, q)) return rc;
+    const uint64_t pbytes = patoff[q], total = patoff[q] - patoff[0];
+    if (total == 0) return CAPS_SA_OK;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const uint64_t blob = fm_blob_bytes(h);
+        const size_t off_pat = up(blob), off_off = off_pat + up(pbytes + 1), off_len = off_off + up((q + 1) * 8), off_first = off_len + up(total * 4),
+                     off_count = off_first + up(first ? total * 8 : 0);
+        fm_upload(hc, be, device, index, blob, off_count + up(count ? total * 8 : 0));
+        be.h2d(hc.base + off_pat, pat, pbytes);
+        be.h2d(hc.base + off_off, patoff, (q + 1) * 8);
+        if (int rc = run_fm_match(be, hc.base, blob, h, hc.base + off_pat, hc.base + off_off, q, max_len, hc.base + off_len,
+                                  first ? hc.base + off_first : nullptr, count ? hc.base + off_count : nullptr))
+            return rc;
+        be.d2h(len, hc.base + off_len, total * 4);
+        if (first) be.d2h(first, hc.base + off_first, total * 8);
+        if (count) be.d2h(count, hc.base + off_count, total * 8);
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+
+// workspace of the MEM calls: len u32[total + 1] | first, count u64[total] each | flags -> slots u64[padded] | the columns' totals ->
+// bases u64[cols], 256-byte aligned each.  The total + 1 flags are scanned as `cols` columns of `per` slots, one workgroup each.
+constexpr uint64_t FM_MEM_COLS = 1024, FM_MEM_COL_MIN = 1u << 16;
+struct FmMemPlan { size_t off_len, off_first, off_count, off_slot, off_base, bytes; uint64_t cols, per, padded; };
+inline FmMemPlan fm_mem_plan(uint64_t total)
+{
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    FmMemPlan p;
+    p.cols = std::min<uint64_t>(FM_MEM_COLS, (total + 1 + FM_MEM_COL_MIN - 1) / FM_MEM_COL_MIN);
+    p.per = (total + 1 + p.cols - 1) / p.cols;
+    p.padded = p.cols * p.per;
+    p.off_len = 0;
+    p.off_first = p.off_len + up((total + 1) * 4);
+    p.off_count = p.off_first + up(total * 8);
+    p.off_slot = p.off_count + up(total * 8);
+    p.off_base = p.off_slot + up(p.padded * 8);
+    p.bytes = p.off_base + up(FM_MEM_COLS * 8);
+    return p;
+}
+inline int fm_mems_workspace_bytes(uint64_t total, uint64_t q, uint64_t* bytes)
+{
+    if (!bytes) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (total > (1ull << 56) || q > (1ull << 56)) return fail(CAPS_SA_EINVAL, "too many pattern bytes or patterns");
+    *bytes = fm_mem_plan(total).bytes + 256;
+    return CAPS_SA_OK;
+}
+
+// MEMs on device arrays.  dMemOff is written whenever the header and the offsets pass (offsets_written); ws: 256-byte aligned, or
+// null: allocated here once the pattern bytes are known.  `hdr` as in run_fm_count.
+inline int run_fm_mems(Backend& be, DevAllocs& da, const void* dIndex, uint64_t index_bytes, const uint64_t* hdr, const void* dPat, const void* dPatOff,
+                       uint64_t q, uint32_t min_len, void* dMemOff, void* dMems, uint64_t mem_capacity, char* ws, uint64_t ws_bytes,
+                       bool* offsets_written)
+{
+    if (offsets_written) *offsets_written = false;
+    uint64_t h[FM_HDR_WORDS];
+    if (hdr) std::memcpy(h, hdr, sizeof h);
+    else { be.d2h(h, dIndex, sizeof h); be.sync(); }
+    FmView v;
+    if (int rc = fm_check_header(h, index_bytes, dIndex, v)) return rc;
+    if (q == 0) {
+        if (dMemOff) { be.memset(dMemOff, 0, sizeof(uint64_t)); be.sync(); }
+        if (offsets_written) *offsets_written = dMemOff != nullptr;
+        return CAPS_SA_OK;
+    }
+    uint64_t o_begin = 0, o_end = 0;
+    if (int rc = fm_match_offsets(be, dPatOff, q, v.n, o_begin, o_end)) return rc;
+    const uint64_t total = o_end - o_begin;
+    if (total == 0 || v.n == 0) {
+        be.memset(dMemOff, 0, (q + 1) * sizeof(uint64_t));
+        be.sync();
+        if (offsets_written) *offsets_written = true;
+        return CAPS_SA_OK;
+    }
+    if (!dPat) return fail(CAPS_SA_EINVAL, "null pointer");
+    const FmMemPlan p = fm_mem_plan(total);
+    if (ws && ws_bytes < p.bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_fm_mems_workspace_bytes)");
+    if (!ws) ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(da.get<char>(p.bytes + 256)) + 255) & ~uintptr_t(255));
+    uint32_t* len = reinterpret_cast<uint32_t*>(ws + p.off_len);
+    uint64_t* first = reinterpret_cast<uint64_t*>(ws + p.off_first);
+    uint64_t* count = reinterpret_cast<uint64_t*>(ws + p.off_count);
+    uint64_t* slot = reinterpret_cast<uint64_t*>(ws + p.off_slot);
+    uint64_t* colbase = reinterpret_cast<uint64_t*>(ws + p.off_base);
+    uint64_t* words = fm_words(be);
+    const uint64_t* off = static_cast<const uint64_t*>(dPatOff);
+    launch_fm_match(be, v, (int)h[FMH_IDX_BYTES], dPat, dPatOff, q, o_begin, o_end, 0u, len, dMems ? first : nullptr, dMems ? count : nullptr);
+    const uint32_t g = capped_grid(std::min<uint64_t>((p.padded + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+    const uint32_t qg = capped_grid(std::min<uint64_t>((q + 1 + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+    CAPS_LAUNCH(fm_mem_flag_kernel, g, FM_NT, be, (const uint32_t*)len, off, q, total, p.padded, std::max<uint32_t>(min_len, 1u), slot);
+    CAPS_LAUNCH(fm_scan_kernel, (uint32_t)p.cols, FM_NT, be, slot, p.per, 0u, (uint32_t)p.cols, colbase);
+    CAPS_LAUNCH(fm_scan_kernel, 1, FM_NT, be, colbase, p.cols, 0u, 1u, words + 1);
+    CAPS_LAUNCH(fm_mem_off_kernel, qg, FM_NT, be, (const uint64_t*)slot, (const uint64_t*)colbase, p.per, off, q, total, static_cast<uint64_t*>(dMemOff));
+    uint64_t found = 0;
+    be.d2h(&found, words + 1, sizeof found);
+    be.sync();
+    if (offsets_written) *offsets_written = true;
+    if (!dMems) return CAPS_SA_OK;
+    if (found > mem_capacity) return fail(CAPS_SA_EINVAL, "mem_capacity is smaller than the number of MEMs (dMemOff[q]; a call with dMems = NULL counts them)");
+    if (found) {
+        CAPS_LAUNCH(fm_mem_write_kernel, g, FM_NT, be, (const uint32_t*)len, (const uint64_t*)first, (const uint64_t*)count, (const uint64_t*)slot,
+                    (const uint64_t*)colbase, p.per, off, q, total, mem_capacity, static_cast<uint64_t*>(dMems));
+        be.sync();
+    }
+    return CAPS_SA_OK;
+}
+
+inline int fm_mems_device(const void* dIndex, uint64_t index_bytes, const void* dPat, const void* dPatOff, uint64_t q, uint32_t min_len,
+                          void* dMemOff, void* dMems, uint64_t mem_capacity, void* workspace, uint64_t workspace_bytes, void* stream)
+{
+    if (!dIndex) return fail(CAPS_SA_EINVAL, "null index");
+    if (index_bytes < FM_HDR_WORDS * sizeof(uint64_t)) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than an FM-index header");
+    if (!dMemOff || (q && !dPatOff)) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (reinterpret_cast<uintptr_t>(dMems) & 7u) return fail(CAPS_SA_EINVAL, "dMems must be 8-byte aligned");
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);                                    // a null workspace: allocated here, freed on return
+        char* ws = nullptr;
+        uint64_t ws_bytes = 0;
+        if (workspace) {
+            ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+            const uint64_t slack = (uint64_t)(ws - static_cast<char*>(workspace));
+            ws_bytes = workspace_bytes > slack ? workspace_bytes - slack : 0;
+        }
+        return run_fm_mems(be, da, dIndex, index_bytes, nullptr, dPat, dPatOff, q, min_len, dMemOff, dMems, mem_capacity, ws, ws_bytes, nullptr);
+    });
+}
+
+inline int fm_mems_host(const void* index, uint64_t index_bytes, const uint8_t* pat, const uint64_t* patoff, uint64_t q, uint32_t min_len,
+                        uint64_t* memoff, void* mems, uint64_t mem_capacity, int device)
+{
+    uint64_t h[FM_HDR_WORDS];
+    FmView v;
+    if (int rc = fm_host_header(index, index_bytes, h, v)) return rc;
+    if (!memoff) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (q == 0) { memoff[0] = 0; return CAPS_SA_OK; }
+    if (int rc = fm_match_host_check(pat, patoff, q)) return rc;
+    const uint64_t pbytes = patoff[q], total = patoff[q] - patoff[0];
+    if (total == 0 || v.n == 0) { std::memset(memoff, 0, (q + 1) * 8); return CAPS_SA_OK; }
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        DevAllocs da(be);
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const uint64_t blob = fm_blob_bytes(h), room = mems ? std::min(mem_capacity, total) : 0;
+        const FmMemPlan p = fm_mem_plan(total);
+        const size_t off_pat = up(blob), off_off = off_pat + up(pbytes + 1), off_memoff = off_off + up((q + 1) * 8), off_ws = off_memoff + up((q + 1) * 8),
+                     off_mems = off_ws + up(p.bytes);
+        fm_upload(hc, be, device, index, blob, off_mems + up(room * FM_MEM_BYTES + 8));
+        be.h2d(hc.base + off_pat, pat, pbytes);
+        be.h2d(hc.base + off_off, patoff, (q + 1) * 8);
+        bool written = false;
+        const int rc = run_fm_mems(be, da, hc.base, blob, h, hc.base + off_pat, hc.base + off_off, q, min_len, hc.base + off_memoff,
+                                   mems ? hc.base + off_mems : nullptr, mem_capacity, hc.base + off_ws, p.bytes, &written);
+        if (written) {
+            be.d2h(memoff, hc.base + off_memoff, (q + 1) * 8);
+            be.sync();
+        }
+        if (rc) return rc;
+        if (mems && memoff[q]) be.d2h(mems, hc.base + off_mems, memoff[q] * FM_MEM_BYTES);
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+
 // Text on the device for the kernel-level entry points.
 struct DevText {
     uint8_t* raw = nullptr;
@@ -2479,6 +2747,20 @@ int CAPS_API(fm_count)(const void* index, uint64_t index_bytes, const uint8_t* p
 int CAPS_API(fm_locate)(const void* index, uint64_t index_bytes, const uint64_t* first, const uint64_t* count, const uint64_t* out_off,
                         uint64_t q, uint64_t* pos, int device)
 { return caps::fm_locate_host(index, index_bytes, first, count, out_off, q, pos, device); }
+int CAPS_API(fm_match_device)(const void* dIndex, uint64_t index_bytes, const void* dPatterns, const void* dPatOff, uint64_t q, uint32_t max_len,
+                              void* dLen, void* dFirst, void* dCount, void* stream)
+{ return caps::fm_match_device(dIndex, index_bytes, dPatterns, dPatOff, q, max_len, dLen, dFirst, dCount, stream); }
+int CAPS_API(fm_match)(const void* index, uint64_t index_bytes, const uint8_t* patterns, const uint64_t* pat_off, uint64_t q, uint32_t max_len,
+                       uint32_t* len, uint64_t* first, uint64_t* count, int device)
+{ return caps::fm_match_host(index, index_bytes, patterns, pat_off, q, max_len, len, first, count, device); }
+int CAPS_API(fm_mems_workspace_bytes)(uint64_t total_pattern_bytes, uint64_t q, uint64_t* bytes)
+{ return caps::fm_mems_workspace_bytes(total_pattern_bytes, q, bytes); }
+int CAPS_API(fm_mems_device)(const void* dIndex, uint64_t index_bytes, const void* dPatterns, const void* dPatOff, uint64_t q, uint32_t min_len,
+                             void* dMemOff, void* dMems, uint64_t mem_capacity, void* workspace, uint64_t workspace_bytes, void* stream)
+{ return caps::fm_mems_device(dIndex, index_bytes, dPatterns, dPatOff, q, min_len, dMemOff, dMems, mem_capacity, workspace, workspace_bytes, stream); }
+int CAPS_API(fm_mems)(const void* index, uint64_t index_bytes, const uint8_t* patterns, const uint64_t* pat_off, uint64_t q, uint32_t min_len,
+                      uint64_t* mem_off, void* mems, uint64_t mem_capacity, int device)
+{ return caps::fm_mems_host(index, index_bytes, patterns, pat_off, q, min_len, mem_off, mems, mem_capacity, device); }
 
 
 struct caps_sa_shard { std::unique_ptr<caps::ShardBase> impl; };

@@ -5,9 +5,14 @@
 //     caps_sa --inverse-bwt IN.bwt OUT
 //     caps_sa <input_path> <output_path> [subproblem-count] --fm-index PATH [--fm-sample S] [--fm-text-sample T]
 //     caps_sa --fm-search INDEX PATTERNS [--locate K]
+//     caps_sa --fm-mems INDEX PATTERNS [--min-len L]
 //     caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S] [--fm-text-sample T]
 //     caps_sa --fm-extract INDEX RANGES
 //
+// * --fm-mems INDEX PATTERNS [--min-len L] (not in the reference): one pattern per line of PATTERNS, remapped like the text; per
+//   line the number of its maximal exact matches of at least L (default 1) bytes against the text (include/caps_sa_hip.h "FM-index:
+//   matching statistics"), then "start:length:count" for each by increasing end: start within the pattern, count = its occurrences
+//   in the text.  Works on any index file, with or without samples.  Any other argument is refused;
 // * --fm-text-sample T (not in the reference; with --fm-index PATH or --fm-from-bwt): the index is written in format version 2
 //   (include/caps_sa_hip.h "FM-index: extract"), with the row of every T-th text position; T a power of two, S .. 1024;
 // * --fm-extract INDEX RANGES (not in the reference): one "start length" pair per line of RANGES; per line the text
@@ -157,6 +162,48 @@ static int fm_search_main(const std::vector<std::string>& args)
             std::cout << cnt[j];
             if (locate)
                 for (uint64_t t = out_off[j]; t < out_off[j + 1]; ++t) std::cout << ' ' << pos[t];
+            std::cout << '\n';
+        }
+    } catch (const std::exception& e) {
+        std::cerr << e.what() << "\n";
+        return EXIT_FAILURE;
+    }
+    return 0;
+}
+
+// caps_sa --fm-mems INDEX PATTERNS [--min-len L]: args = everything after the program name
+static int fm_mems_main(const std::vector<std::string>& args)
+{
+    const char* usage = "--fm-mems: usage: caps_sa --fm-mems INDEX PATTERNS [--min-len L] (no other option or argument)\n";
+    if (args.size() < 3 || args[0] != "--fm-mems" || (args.size() != 3 && args.size() != 5)) { std::cerr << usage; return EXIT_FAILURE; }
+    size_t min_len = 1;
+    if (args.size() == 5 && (args[3] != "--min-len" || !parse_count(args[4], min_len) || min_len < 1 || min_len > 0xFFFFFFFFull)) {
+        std::cerr << usage;
+        return EXIT_FAILURE;
+    }
+    if (args[1].compare(0, 2, "--") == 0 || args[2].compare(0, 2, "--") == 0) { std::cerr << usage; return EXIT_FAILURE; }
+    std::string lines;
+    if (!read_input(args[2], lines)) return EXIT_FAILURE;
+    try {
+        const CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::load(args[1]);
+        static const char lookup[4] = {'A', 'C', 'T', 'G'};
+        std::string pats;
+        std::vector<uint64_t> off(1, 0);
+        for (size_t a = 0; a < lines.size();) {
+            size_t b = lines.find('\n', a);
+            if (b == std::string::npos) b = lines.size();
+            size_t e = b;
+            if (e > a && lines[e - 1] == '\r') --e;
+            for (size_t j = a; j < e; ++j) pats.push_back(lookup[(std::toupper(static_cast<unsigned char>(lines[j])) & 0x6) >> 1]);
+            off.push_back(pats.size());
+            a = b + 1;
+        }
+        std::vector<uint64_t> mem_off;
+        std::vector<CaPS_SA::FM_Index::Mem> mems;
+        fm.mems(pats, off, static_cast<uint32_t>(min_len), mem_off, mems);
+        for (size_t j = 0; j + 1 < off.size(); ++j) {
+            std::cout << mem_off[j + 1] - mem_off[j];
+            for (uint64_t t = mem_off[j]; t < mem_off[j + 1]; ++t) std::cout << ' ' << mems[t].start << ':' << mems[t].length << ':' << mems[t].count;
             std::cout << '\n';
         }
     } catch (const std::exception& e) {
@@ -329,6 +376,8 @@ int main(int argc, char* argv[])
     for (int i = 1; i < argc; ++i)
         if (std::strcmp(argv[i], "--fm-search") == 0) return fm_search_main(std::vector<std::string>(argv + 1, argv + argc));
     for (int i = 1; i < argc; ++i)
+        if (std::strcmp(argv[i], "--fm-mems") == 0) return fm_mems_main(std::vector<std::string>(argv + 1, argv + argc));
+    for (int i = 1; i < argc; ++i)
         if (std::strcmp(argv[i], "--fm-from-bwt") == 0) return fm_from_bwt_main(std::vector<std::string>(argv + 1, argv + argc));
     for (int i = 1; i < argc; ++i)
         if (std::strcmp(argv[i], "--fm-extract") == 0) return fm_extract_main(std::vector<std::string>(argv + 1, argv + argc));
@@ -362,6 +411,7 @@ int main(int argc, char* argv[])
             }
         }
         else if (std::strcmp(argv[i], "--locate") == 0) { std::cerr << "--locate: only with --fm-search\n"; return EXIT_FAILURE; }
+        else if (std::strcmp(argv[i], "--min-len") == 0) { std::cerr << "--min-len: only with --fm-mems\n"; return EXIT_FAILURE; }
         else if (std::strcmp(argv[i], "--gpus") == 0 && i + 1 < argc) {
             if (!parse_count(argv[++i], gpus) || gpus < 1 || gpus > 64) { std::cerr << "--gpus: a device count, please\n"; return EXIT_FAILURE; }
         } else pos.push_back(argv[i]);
@@ -372,6 +422,7 @@ int main(int argc, char* argv[])
                      "<(optional)--fm-index PATH [--fm-sample S] [--fm-text-sample T]>\n"
                      "       caps_sa --inverse-bwt IN.bwt OUT\n"
                      "       caps_sa --fm-search INDEX PATTERNS [--locate K]\n"
+                     "       caps_sa --fm-mems INDEX PATTERNS [--min-len L]\n"
                      "       caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S] [--fm-text-sample T]\n"
                      "       caps_sa --fm-extract INDEX RANGES\n";
         return EXIT_FAILURE;

@@ -5584,6 +5584,132 @@ GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_locate_kernel(KCTX FmView v, const uint64_t* _
     }
 }
 
+// ---- matching statistics and maximal exact matches (capi_impl.h fm_match_* / fm_mems_*; include/caps_sa_hip.h "FM-index: matching
+// statistics") ------------------------------------------------------------------------------------------------------------------
+// For end e of pattern P (1 <= e <= m): L[e] = the longest l <= e (<= max_len when max_len > 0) such that P[e - l .. e) occurs in
+// the text, and its SA interval.  Nothing but the Occ blocks, C[] and the '$' row rule is read: an index without samples answers.
+
+// one lane per (pattern, end): slot o in [o_begin, o_end) = [patoff[0], patoff[q]), its pattern j by bisection over patoff (the
+// locate kernel's over off), e = o - patoff[j] + 1.  The count kernel's loop from byte e - 1 leftwards; the last non-empty (lo, hi)
+// is kept, and the walk ends at an empty interval, a byte that is no letter, the pattern's first byte or after max_len steps: at
+// most min(e, max_len) steps whatever the body holds.  len is written always, first / count when they are not null.
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_match_kernel(KCTX FmView v, const uint8_t* __restrict__ pat, const uint64_t* __restrict__ patoff, uint64_t q,
+                                                uint64_t o_begin, uint64_t o_end, uint32_t max_len, uint32_t* __restrict__ len,
+                                                uint64_t* __restrict__ first, uint64_t* __restrict__ count)
+{
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t o0 = o_begin + (uint64_t)K_BLOCK_IDX * FM_NT; o0 < o_end; o0 += stride) {     // block-uniform
+        PAR(tid) {
+            const uint64_t o = o0 + tid;
+            if (o < o_end) {
+                uint64_t a = 0, b = q;                                              // the last j with patoff[j] <= o
+                while (b - a > 1) { const uint64_t mid = a + (b - a) / 2; if (patoff[mid] <= o) a = mid; else b = mid; }
+                const uint64_t p0 = patoff[a];
+                uint64_t steps = p0 <= o ? o - p0 + 1 : 0;                          // e: the bytes at and left of o in its pattern
+                if (max_len && steps > max_len) steps = max_len;
+                uint64_t lo = 0, hi = v.n + 1;
+                uint32_t l = 0;
+                for (uint64_t i = 0; i < steps; ++i) {
+                    const uint32_t byte = pat[o - i], c = fm_code_of(v.syms, v.sigma, byte);
+                    if (!fm_is_letter(v.syms, v.sigma, byte, c)) break;
+                    const uint64_t l2 = fm_lf<idx_t>(v, c, lo), h2 = fm_lf<idx_t>(v, c, hi);     // (independent: issued together)
+                    if (l2 >= h2) break;
+                    lo = l2;
+                    hi = h2;
+                    ++l;
+                }
+                const bool hit = l != 0 && lo != 0;                                 // (lo >= C[0] = 1 after a step)
+                len[o - o_begin] = hit ? l : 0u;
+                if (first) first[o - o_begin] = hit ? lo - 1 : 0;
+                if (count) count[o - o_begin] = hit ? hi - lo : 0;
+            }
+        }
+    }
+}
+
+// a pattern longer than limit bytes: flag 16 (a MEM's start and length are 32-bit fields, len[] is u32)
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_patlen_check_kernel(KCTX const uint64_t* __restrict__ off, uint64_t q, uint64_t limit, uint32_t* __restrict__ flags)
+{
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t j0 = (uint64_t)K_BLOCK_IDX * FM_NT; j0 < q; j0 += stride) {       // block-uniform
+        PAR(tid) {
+            const uint64_t j = j0 + tid;
+            if (j < q && off[j + 1] > off[j] && off[j + 1] - off[j] > limit) ATOMIC_OR_U32(flags, 16u);
+        }
+    }
+}
+
+// the MEM rule, one lane per slot t in [0, total]: the match ending at e is a MEM of at least min_len bytes iff L[e] >= min_len and
+// it cannot be extended to the right: e = m, or L[e + 1] <= L[e] (a byte P[e] that is no letter gives L[e + 1] = 0, so the rule
+// covers it).  It is left-maximal by construction.  flag[total .. padded) = 0.  The flags are scanned by fm_scan_kernel as columns
+// of `per` slots, one workgroup each, and the columns' totals once more: the record slot of t is slot[t] + colbase[t / per].
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_mem_flag_kernel(KCTX const uint32_t* __restrict__ len, const uint64_t* __restrict__ patoff, uint64_t q,
+                                                   uint64_t total, uint64_t padded, uint32_t min_len, uint64_t* __restrict__ flag)
+{
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT, o_begin = patoff[0];
+    for (uint64_t t0 = (uint64_t)K_BLOCK_IDX * FM_NT; t0 < padded; t0 += stride) {  // block-uniform
+        PAR(tid) {
+            const uint64_t t = t0 + tid;
+            if (t < total) {
+                const uint64_t o = o_begin + t;
+                uint64_t a = 0, b = q;                                              // the last j with patoff[j] <= o
+                while (b - a > 1) { const uint64_t mid = a + (b - a) / 2; if (patoff[mid] <= o) a = mid; else b = mid; }
+                const uint32_t l = len[t];
+                const bool last = o + 1 >= patoff[a + 1];                           // e = m
+                flag[t] = l >= min_len && (last || len[t + 1] <= l) ? 1u : 0u;
+            } else if (t < padded) {
+                flag[t] = 0;
+            }
+        }
+    }
+}
+
+// memoff[j] = the MEMs of the patterns before j: the scanned flags at pattern j's first slot (memoff[q] = all of them)
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_mem_off_kernel(KCTX const uint64_t* __restrict__ slot, const uint64_t* __restrict__ colbase, uint64_t per,
+                                                  const uint64_t* __restrict__ patoff, uint64_t q, uint64_t total, uint64_t* __restrict__ memoff)
+{
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT, o_begin = patoff[0];
+    for (uint64_t j0 = (uint64_t)K_BLOCK_IDX * FM_NT; j0 <= q; j0 += stride) {      // block-uniform
+        PAR(tid) {
+            const uint64_t j = j0 + tid;
+            if (j <= q) {
+                const uint64_t t = std::min<uint64_t>(patoff[j] >= o_begin ? patoff[j] - o_begin : 0, total);
+                memoff[j] = slot[t] + colbase[t / per];
+            }
+        }
+    }
+}
+
+// the records, 4 words of 64 bits each: pattern | start + (length << 32) | first | count, at the slot the scan gave: (pattern,
+// increasing end) order.  A slot is a MEM's when the scan moves on behind it; one at or beyond cap is not written.
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_mem_write_kernel(KCTX const uint32_t* __restrict__ len, const uint64_t* __restrict__ first,
+                                                    const uint64_t* __restrict__ count, const uint64_t* __restrict__ slot,
+                                                    const uint64_t* __restrict__ colbase, uint64_t per,
+                                                    const uint64_t* __restrict__ patoff, uint64_t q, uint64_t total, uint64_t cap,
+                                                    uint64_t* __restrict__ mems)
+{
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT, o_begin = patoff[0];
+    for (uint64_t t0 = (uint64_t)K_BLOCK_IDX * FM_NT; t0 < total; t0 += stride) {   // block-uniform
+        PAR(tid) {
+            const uint64_t t = t0 + tid;
+            if (t < total) {
+                const uint64_t at = slot[t] + colbase[t / per];
+                if (slot[t + 1] + colbase[(t + 1) / per] != at && at < cap) {
+                    const uint64_t o = o_begin + t;
+                    uint64_t a = 0, b = q;                                          // the last j with patoff[j] <= o
+                    while (b - a > 1) { const uint64_t mid = a + (b - a) / 2; if (patoff[mid] <= o) a = mid; else b = mid; }
+                    const uint64_t e = o - patoff[a] + 1, l = len[t];
+                    mems[4 * at] = a;
+                    mems[4 * at + 1] = ((e - l) & 0xFFFFFFFFull) | (l << 32);
+                    mems[4 * at + 2] = first[t];
+                    mems[4 * at + 3] = count[t];
+                }
+            }
+        }
+    }
+}
+
 // ---- SA samples from the BWT alone (capi_impl.h fm_from_bwt_*; include/caps_sa_hip.h "FM-index from the BWT alone") -------------
 // LF^k(0), k = 1 .. n, is the row of text position n - k (k = n: the '$' row, position 0; k = n + 1: row 0 again), so a row's offset
 // on the cycle of row 0 is its SA value: neither T nor the SA is read.  LF comes from the finished Occ section, one block per step

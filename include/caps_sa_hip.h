@@ -491,6 +491,50 @@ int caps_sa_hip_fm_extract_device(const void* dIndex, uint64_t index_bytes, cons
 int caps_sa_hip_fm_extract(const void* index, uint64_t index_bytes, const uint64_t* start, const uint64_t* out_off, uint64_t q,
                            uint8_t* text, int device);
 
+/* ---- FM-index: matching statistics and maximal exact matches ------------------------------
+ *
+ * count answers for a whole pattern; a read with one wrong base counts 0. The seeding question of a read mapper is asked for every
+ * position instead. Let P be a pattern of m bytes and T the indexed text. For an END e in 1 .. m:
+ *   L[e]                 the largest l <= e such that P[e - l .. e) occurs in T (0 when P[e - 1] is no letter of the index); with a
+ *                        cap max_len > 0 additionally l <= max_len
+ *   (first[e], count[e]) the SA interval of P[e - L[e] .. e) in count's convention: the occurrences are SA[first .. first + count).
+ *                        L[e] = 0 gives first = count = 0 (not the empty pattern's (0, n)).
+ * Without a cap L[e + 1] <= L[e] + 1, and the match ending at e is left-maximal by construction. It is a maximal exact match (MEM)
+ * iff L[e] >= 1 and e = m, or P[e] is no letter, or L[e + 1] <= L[e]; every MEM of P against T arises so, exactly once. (P[e] no
+ * letter gives L[e + 1] = 0: the third condition covers the second.)
+ *
+ * Nothing is read but the Occ blocks, C[] and the '$' row: both calls work on version-1 and version-2 blobs, with or without SA
+ * samples. One GPU lane serves one (pattern, end) pair and runs count's backward search from byte e - 1 leftwards, both LF
+ * lookups of a step issued together, until the interval is empty, a byte is no letter, the pattern's first byte is passed or
+ * max_len steps are done: at most min(e, max_len) steps for any blob body, every row and block clamped as in count.
+ *
+ * total = dPatOff[q] - dPatOff[0]; output slot dPatOff[j] - dPatOff[0] + e - 1 belongs to end e of pattern j. dLen is u32[total];
+ * dFirst / dCount are u64[total] each, or NULL (each on its own): not written.
+ *
+ * caps_sa_hip_fm_mems_*: the MEMs of at least min_len bytes (0 is treated as 1), without a cap, as records of 32 bytes
+ *   u64 pattern index | u32 start within the pattern | u32 length | u64 first | u64 count          (little-endian)
+ * in (pattern, increasing end) order; dMemOff[j] .. dMemOff[j + 1] are the records of pattern j (u64[q + 1], always written).
+ * dMems = NULL is the counting call: only dMemOff is written. dMems non-null (8-byte aligned) with dMemOff[q] > mem_capacity
+ * (in records) is CAPS_SA_EINVAL: dMemOff is still valid and no record is written. Workspace:
+ * caps_sa_hip_fm_mems_workspace_bytes(total, q) -- 28 bytes per pattern byte (lengths, intervals, record slots) and at most
+ * 24 KiB; NULL is allocated and freed by the call.
+ *
+ * Errors follow count's: the header is checked on the host first; a null pointer with q > 0 and non-monotone offsets are
+ * CAPS_SA_EINVAL, and so is a pattern longer than 2^32 - 1 bytes. q = 0 succeeds (dMemOff[0] = 0). n = 0: every length is 0 and
+ * there are no MEMs.
+ */
+int caps_sa_hip_fm_match_device(const void* dIndex, uint64_t index_bytes, const void* dPatterns, const void* dPatOff, uint64_t q,
+                                uint32_t max_len, void* dLen, void* dFirst, void* dCount, void* hip_stream);
+/* The same on host buffers; the index is uploaded as for caps_sa_hip_fm_count. */
+int caps_sa_hip_fm_match(const void* index, uint64_t index_bytes, const uint8_t* patterns, const uint64_t* pat_off, uint64_t q,
+                         uint32_t max_len, uint32_t* len, uint64_t* first, uint64_t* count, int device);
+int caps_sa_hip_fm_mems_workspace_bytes(uint64_t total_pattern_bytes, uint64_t q, uint64_t* bytes);
+int caps_sa_hip_fm_mems_device(const void* dIndex, uint64_t index_bytes, const void* dPatterns, const void* dPatOff, uint64_t q,
+                               uint32_t min_len, void* dMemOff, void* dMems, uint64_t mem_capacity, void* workspace,
+                               uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_fm_mems(const void* index, uint64_t index_bytes, const uint8_t* patterns, const uint64_t* pat_off, uint64_t q,
+                        uint32_t min_len, uint64_t* mem_off, void* mems, uint64_t mem_capacity, int device);
+
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
 /* merge_sort (src/Suffix_Array.cpp:112-129) of an arbitrary list of cnt distinct suffix
