@@ -74,6 +74,9 @@ constexpr uint32_t kMaxPasses = 96;
 #define CAPS_DIRECT_SUB 8
 #endif
 constexpr uint32_t DIRECT_SUB = CAPS_DIRECT_SUB;
+// Which hand-overs of the direct path travel as (key, index) records when CAPS_SA_RECORDS does not say (run_direct): bit 0 =
+// level A -> level B.
+constexpr uint32_t DIRECT_RECORDS_DEFAULT = 1;
 // Quantile mode of the direct path (skewed keys): mean bucket size (sampling noise on top: sigma = 1 / sqrt(QUANTILE_SPB)) and
 // samples drawn per bucket.
 #ifndef CAPS_BUCKET_Q_32NDS
@@ -463,6 +466,8 @@ struct SortOpts {
     uint32_t sub = 1;             // > 1: every `sub` consecutive segments are sub-streams of one parent and share its buckets
     const uint64_t* in_key = nullptr;   // non-null: the elements are read from these arrays (indexed like the segments)
     const void* in_sa = nullptr;        //   instead of `cur`, which then only receives results
+    bool in_records = false;            // in_key points at KeySaRec records (kernels.h; 32-bit indices, 64-bit keys), in_sa is unused:
+                                        //   the stream of level A of the direct path.  Bucketed sorts only: the scatter reads them
     const uint8_t* gshift = nullptr;    // non-null with range_mode 2: 32-bit keys (text.h key32_of), the parents' shifts
     bool k32 = false;                   // the elements (in_key, read as uint32_t) carry 32-bit keys; slots only: when a slot
                                         //   overflows the sort gives up (SortResult::failed) and the caller falls back to 64-bit keys
@@ -564,6 +569,9 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
         // where the elements are read from (SRC_ARRAYS / SRC_RUNS): `cur`, unless the caller keeps them elsewhere
         const uint64_t* src_key = o.in_key ? o.in_key : (const uint64_t*)cur.key;
         const idx_t* src_sa = o.in_key ? static_cast<const idx_t*>(o.in_sa) : (const idx_t*)cur.sa;
+        const bool rec_in = o.in_records;
+        if (rec_in && (sizeof(idx_t) != 4 || !o.in_key || from_text || o.runs || o.k32))
+            throw std::invalid_argument("records: (64-bit key, 32-bit index) arrays given by the caller");
         // bucket ids kept between count and scatter (quantile splits of arrays): in the LCP array of the scatter's destination
         // (`oth`: nothing writes LCPs there before the scatter has read the ids back)
         uint16_t* bid = nullptr;
@@ -581,8 +589,20 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
                         (const BucketParams*)bk.params, (const uint64_t*)bk.bstart, sub_start, (uint64_t)cap, static_cast<idx_t*>(bk.cursor),       \
                         okey, osa, fbps, gfirst, o.knots, (const uint16_t*)nullptr, (const uint32_t*)nullptr, 1u, o.knots_per_parent, o.sub, \
                         (const uint16_t*)bid, Spill<idx_t>())
+#define CAPS_SCATTER_LAUNCH_REC(MAP_)                                                                                        \
+            CAPS_LAUNCH((bucket_scatter_kernel<idx_t, BITS, SRC_ARRAYS, MAP_, uint64_t, false, true>), n_tiles, TILE_NT, be, psd, P, n_words, tbase, \
+                        src_key, src_sa, rsrc, (const BucketParams*)bk.params, (const uint64_t*)bk.bstart, sub_start, (uint64_t)cap,               \
+                        static_cast<idx_t*>(bk.cursor), okey, osa, fbps, gfirst, o.knots, (const uint16_t*)nullptr, (const uint32_t*)nullptr, 1u,   \
+                        o.knots_per_parent, o.sub, (const uint16_t*)bid, Spill<idx_t>())
             const uint64_t* nokey = nullptr;
             const idx_t* nosa = nullptr;
+            if (rec_in) {
+                if constexpr (sizeof(idx_t) == 4) {
+                    if (by_knots) CAPS_SCATTER_LAUNCH_REC(MAP_SPLIT);
+                    else if (grouped) CAPS_SCATTER_LAUNCH_REC(MAP_GROUPED);
+                    else CAPS_SCATTER_LAUNCH_REC(MAP_LINEAR);
+                }
+            } else
             if (from_text) { if (grouped) CAPS_SCATTER_LAUNCH(SRC_TEXT, MAP_GROUPED, nokey, nosa); else CAPS_SCATTER_LAUNCH(SRC_TEXT, MAP_LINEAR, nokey, nosa); }
             else if (runs) { if (grouped) CAPS_SCATTER_LAUNCH(SRC_RUNS, MAP_GROUPED, src_key, src_sa);
                              else CAPS_SCATTER_LAUNCH(SRC_RUNS, MAP_LINEAR, src_key, src_sa); }
@@ -590,6 +610,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
             else { if (grouped) CAPS_SCATTER_LAUNCH(SRC_ARRAYS, MAP_GROUPED, src_key, src_sa);
                    else CAPS_SCATTER_LAUNCH(SRC_ARRAYS, MAP_LINEAR, src_key, src_sa); }
 #undef CAPS_SCATTER_LAUNCH
+#undef CAPS_SCATTER_LAUNCH_REC
             BackendEvent s1 = be.record();
             if (o.scatter_clock) { o.scatter_clock->spans.push_back({s0, s1}); o.scatter_clock->elems.push_back(n_elems); }
         };
@@ -725,11 +746,15 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
                 be.h2d(sp.count, &fixed, sizeof(uint64_t));
                 if (fixed) be.memset(sp.bucket, 0xFF, (size_t)fixed * sizeof(uint32_t));
                 BackendEvent s0 = be.record();
-                CAPS_LAUNCH((bucket_scatter_kernel<idx_t, BITS, SRC_ARRAYS, MAP_SPLIT, uint64_t, true>), n_tiles, TILE_NT, be, psd, P, (uint64_t)0,
-                            (uint64_t)0, src_key, src_sa, rsrc, (const BucketParams*)bk.params, (const uint64_t*)bk.bstart,
-                            (const uint64_t*)nullptr, cap_s, static_cast<idx_t*>(bk.cursor), slot_key, slot_sa,
-                            (const BucketParams*)nullptr, (const uint32_t*)nullptr, o.knots, (const uint16_t*)nullptr,
-                            (const uint32_t*)nullptr, 1u, o.knots_per_parent, o.sub, (const uint16_t*)nullptr, sp);
+#define CAPS_SPILL_SCATTER_LAUNCH(REC_)                                                                                       \
+                CAPS_LAUNCH((bucket_scatter_kernel<idx_t, BITS, SRC_ARRAYS, MAP_SPLIT, uint64_t, true, REC_>), n_tiles, TILE_NT, be, psd, P, (uint64_t)0, \
+                            (uint64_t)0, src_key, src_sa, rsrc, (const BucketParams*)bk.params, (const uint64_t*)bk.bstart,         \
+                            (const uint64_t*)nullptr, cap_s, static_cast<idx_t*>(bk.cursor), slot_key, slot_sa,                     \
+                            (const BucketParams*)nullptr, (const uint32_t*)nullptr, o.knots, (const uint16_t*)nullptr,              \
+                            (const uint32_t*)nullptr, 1u, o.knots_per_parent, o.sub, (const uint16_t*)nullptr, sp)
+                if (rec_in) { if constexpr (sizeof(idx_t) == 4) CAPS_SPILL_SCATTER_LAUNCH(true); }
+                else CAPS_SPILL_SCATTER_LAUNCH(false);
+#undef CAPS_SPILL_SCATTER_LAUNCH
                 uint64_t spilled = 0;
                 be.d2h(&spilled, sp.count, sizeof spilled);
                 CAPS_LAUNCH((widen_kernel<idx_t>), (bk.nb_cap + 255) / 256, 256, be, (const idx_t*)static_cast<idx_t*>(bk.cursor),
@@ -785,7 +810,15 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
             else if (runs)
                 CAPS_LAUNCH((bucket_count_kernel<idx_t, BITS, SRC_RUNS>), pgrid, TILE_NT, be, psd, P, n_words, tbase, src_key, rsrc,
                             cparams, cstart, ccount, no_tab, 0u, 1u, (uint16_t*)nullptr);
-            else if (by_knots)
+            else if (rec_in && by_knots) {
+                if constexpr (sizeof(idx_t) == 4)
+                    CAPS_LAUNCH((bucket_count_kernel<idx_t, BITS, SRC_ARRAYS, MAP_SPLIT, true>), pgrid, TILE_NT, be, psd, P, n_words, tbase, src_key,
+                                rsrc, cparams, cstart, ccount, o.knots, o.knots_per_parent, o.sub, bid);
+            } else if (rec_in) {
+                if constexpr (sizeof(idx_t) == 4)
+                    CAPS_LAUNCH((bucket_count_kernel<idx_t, BITS, SRC_ARRAYS, MAP_LINEAR, true>), pgrid, TILE_NT, be, psd, P, n_words, tbase, src_key,
+                                rsrc, cparams, cstart, ccount, no_tab, 0u, 1u, (uint16_t*)nullptr);
+            } else if (by_knots)
                 CAPS_LAUNCH((bucket_count_kernel<idx_t, BITS, SRC_ARRAYS, MAP_SPLIT>), pgrid, TILE_NT, be, psd, P, n_words, tbase, src_key, rsrc,
                             cparams, cstart, ccount, o.knots, o.knots_per_parent, o.sub, bid);
             else
@@ -812,6 +845,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
         } else if (!slot_cap) {
             slot_cap = TILE_E;                           // the tile sort reads the slots, writes `cur`
         }
+
         mark("bucket scatter");
         n_tiles = (uint32_t)out2[0];
         max_len = out2[1];
@@ -876,6 +910,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
     BackendEvent t0 = be.record();
     if (o.seg_ends && segs.seg_start == s.seg_start)
         throw std::invalid_argument("segments in fixed-capacity regions must be bucketed (results are written compactly)");
+    if (o.in_records && segs.seg_start == s.seg_start) throw std::invalid_argument("records are read by the bucket split only");
     const uint64_t* in_key = slot_cap ? slot_key : (o.in_key && segs.seg_start == s.seg_start) ? o.in_key : cur.key;
     const idx_t* in_sa = slot_cap ? slot_sa : (o.in_key && segs.seg_start == s.seg_start) ? static_cast<const idx_t*>(o.in_sa) : cur.sa;
     const uint8_t* no_shift = nullptr;
@@ -1403,7 +1438,7 @@ private:
     uint32_t passes1_ = 0, passes2_ = 0, passesS_ = 0;
     BackendEvent e2_, e3_, e4_, e5_, e6_, e7_, la0_, la1_;
     uint64_t max_part_ = 0;
-    uint32_t path_direct_ = 0, path_fallback_ = 0, direct_groups_ = 0, direct_quantile_ = 0, direct_k32_ = 0, run_buckets_ = 0;
+    uint32_t path_direct_ = 0, path_fallback_ = 0, direct_groups_ = 0, direct_quantile_ = 0, direct_k32_ = 0, direct_records_ = 0, run_buckets_ = 0;
     uint64_t direct_max_group_ = 0;
     uint64_t tie_groups_ = 0, tie_elems_ = 0;
     uint32_t tie_levels_ = 0;
@@ -1716,6 +1751,16 @@ private:
         const bool k32 = allow_k32 && !quantile && BITS == 2 && keys_env && std::string(keys_env) == "32";
         direct_k32_ = k32 ? 1u : 0u;
         idx_t* a_sa = reinterpret_cast<idx_t*>(reinterpret_cast<char*>(A.key) + (uint64_t)n_streams * capA * (k32 ? sizeof(uint32_t) : sizeof(uint64_t)));
+        // Records (kernels.h KeySaRec; CAPS_SA_RECORDS, a mask: bit 0 = this, 0 = two arrays everywhere; bit 1, level B's slots
+        // as records, was measured slower and is not built: DESIGN 5.3): level A hands every stream to level B as 12-byte
+        // (key, index) records in the stream's own region -- same elements, same bytes, one contiguous segment per appended
+        // run instead of two.  32-bit indices with 64-bit keys; 64-bit indices stay on two arrays.
+        const char* la = std::getenv("CAPS_SA_LEVEL_A");
+        const bool big_tiles = k32 || !(la && std::string(la) == "tile");
+        const char* rec_env = std::getenv("CAPS_SA_RECORDS");
+        const uint32_t rec_want = rec_env ? (uint32_t)std::atoi(rec_env) : DIRECT_RECORDS_DEFAULT;
+        const bool rec_a = (rec_want & 1u) != 0 && sizeof(idx_t) == 4 && !k32 && big_tiles;
+        direct_records_ = rec_a ? 1u : 0u;
         if (k32) CAPS_LAUNCH(group_shift_kernel, (K1 + 255) / 256, 256, be_, (const uint64_t*)pl_.gkey, K1, pl_.gshift);
         if (quantile) {
             // more samples, sorted in the (still idle) big buffers; their quantiles are the bucket boundaries and, every KPG-th, the group keys
@@ -1764,8 +1809,6 @@ private:
         be_.h2d(pl_.bk.bstart, b01, sizeof b01);
         be_.memset(pl_.dcur, 0, (size_t)n_streams * sizeof(idx_t));
         // CAPS_SA_LEVEL_A=tile: the same distribution by bucket_scatter_kernel<SRC_TEXT, MAP_SPLIT> on TILE_E positions (cross-check)
-        const char* la = std::getenv("CAPS_SA_LEVEL_A");
-        const bool big_tiles = k32 || !(la && std::string(la) == "tile");
         {
             BackendEvent s0 = be_.record();
             if (k32)
@@ -1773,7 +1816,13 @@ private:
                             packed_words(n, BITS), (uint64_t)0, n, (const uint64_t*)pl_.gkey, K1, (const uint16_t*)pl_.glut,
                             (const uint32_t*)(dflag + 1), SUB, capA, pl_.dcur, reinterpret_cast<uint32_t*>(a_key), a_sa, 0u, 1u,
                             (const uint64_t*)rstart, (const uint64_t*)rcap, (const uint8_t*)pl_.gshift, 0u, K1);
-            else if (big_tiles)
+            else if (rec_a) {
+                if constexpr (sizeof(idx_t) == 4)
+                    CAPS_LAUNCH((group_scatter_kernel<idx_t, BITS, uint64_t, true>), (uint32_t)((n + GA_E - 1) / GA_E), TILE_NT, be_,
+                                (const uint32_t*)pl_.P, packed_words(n, BITS), (uint64_t)0, n, (const uint64_t*)pl_.gkey, K1,
+                                (const uint16_t*)pl_.glut, (const uint32_t*)(dflag + 1), SUB, capA, pl_.dcur, a_key, a_sa, 0u, 1u,
+                                (const uint64_t*)rstart, (const uint64_t*)rcap, (const uint8_t*)nullptr, 0u, K1);
+            } else if (big_tiles)
                 CAPS_LAUNCH((group_scatter_kernel<idx_t, BITS>), (uint32_t)((n + GA_E - 1) / GA_E), TILE_NT, be_, (const uint32_t*)pl_.P,
                             packed_words(n, BITS), (uint64_t)0, n, (const uint64_t*)pl_.gkey, K1, (const uint16_t*)pl_.glut,
                             (const uint32_t*)(dflag + 1), SUB, capA, pl_.dcur, a_key, a_sa, 0u, 1u, (const uint64_t*)rstart, (const uint64_t*)rcap,
@@ -1838,6 +1887,7 @@ private:
         if (k32) { o2.k32 = true; o2.range_mode = 2; o2.gshift = pl_.gshift; }
         o2.in_key = a_key;
         o2.in_sa = a_sa;
+        o2.in_records = rec_a;                        // (a_key then points at the records)
         // large groups of equal keys (tandem arrays, repeat families) are not compared through the text but re-keyed deeper after
         // the sort (kernels.h "Deferred ties"); the flags live in the fine-count table, idle outside the equalised split
         if (defer && !k32 && !std::getenv("CAPS_SA_NO_DEFER")) o2.defer_flags = pl_.bk.fcount;
@@ -2007,6 +2057,7 @@ private:
             st->result_waves = sink_served_ ? waves_used_ : 1u;
             st->n_devices = 1;
             st->direct_key_bits = path_direct_ && direct_k32_ ? 32u : 64u;
+            st->direct_records = path_direct_ ? direct_records_ : 0u;
             st->direct_max_group = direct_max_group_;
             st->level_a_ms = direct_groups_ ? be_.elapsed_ms(la0_, la1_) : 0.0;
             st->slot_splits = slot_stats_[0];

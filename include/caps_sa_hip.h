@@ -103,6 +103,11 @@ typedef struct caps_sa_stats {
      * redone with it (the stream ran full), and the elements that took the stream */
     uint32_t knot_slot_splits, knot_slot_splits_redone;
     uint64_t spill_entries;
+    /* direct path: which hand-overs between its passes travelled as 12-byte (64-bit key, 32-bit index) records instead of a key
+     * array and an index array -- a mask, bit 0 = level A -> level B (the only hand-over built so; the other bits are 0).  The environment
+     * variable CAPS_SA_RECORDS chooses, 0 = none; always 0 with 64-bit indices, with 32-bit keys, and for a build that did not take
+     * the direct path */
+    uint32_t direct_records;
 } caps_sa_stats;
 
 /* sizeof(caps_sa_stats) / sizeof(caps_sa_shard_info) of THIS library.  Both structs grow at their end from release to release and
