@@ -130,42 +130,59 @@ class SuffixArray:
 
 class FMIndex:
     """FM-index over (BWT, primary) (include/caps_sa_hip.h "FM-index"): batched ``count``, ``locate``, ``matching_statistics``, ``mems`` and (after
-    ``with_text_samples``) ``extract`` on the GPU for texts of at most 4 distinct bytes.  The index is one blob (``blob``, np.uint8; ``nbytes``); ``save`` / ``load`` write and read exactly it."""
+    ``with_text_samples``) ``extract`` on the GPU for texts of at most 4 distinct bytes; ``wide=True`` builds the wide format for 1 .. 256 distinct bytes (everything but ``extract``).  The index is one blob (``blob``, np.uint8; ``nbytes``); ``save`` / ``load`` write and read exactly it."""
 
     def __init__(self, blob: np.ndarray, device: int = 0, _lib: CapsLib | None = None):
         self.blob = np.ascontiguousarray(blob, dtype=np.uint8)
         self._device = device
         self._lib = _lib
-        if self.blob.size < 256 or bytes(self.blob[:8]) != b"CAPSFMI1":
+        if self.blob.size < 256 or bytes(self.blob[:8]) not in (b"CAPSFMI1", b"CAPSFMW1"):
             raise ValueError("not an FM-index blob")
         hdr = self.blob[:256].view(np.uint64)
-        self._n, self._sample = int(hdr[2]), int(hdr[12])
-        self._text_sample = int(hdr[19]) if int(hdr[1]) == 2 else 0
+        self._wide = bytes(self.blob[:8]) == b"CAPSFMW1"
+        self._n, self._sample, self._sigma = int(hdr[2]), int(hdr[12]), int(hdr[5])
+        self._text_sample = int(hdr[19]) if int(hdr[1]) == 2 and not self._wide else 0
 
     def _l(self) -> CapsLib:
         return self._lib or lib()
 
     @classmethod
     def from_bwt(cls, BWT, primary: int, SA=None, sa_sample: int = 32, idx_bits: int | None = None, device: int = 0,
-                 _lib: CapsLib | None = None) -> "FMIndex":
-        """SA = None: an index that counts; with the suffix array it also locates (every sa_sample-th text position is kept)."""
+                 _lib: CapsLib | None = None, wide: bool = False) -> "FMIndex":
+        """SA = None: an index that counts; with the suffix array it also locates (every sa_sample-th text position is kept).
+        wide=True: the wide format, 1 .. 256 distinct bytes."""
+        if wide:
+            return cls((_lib or lib()).fm_build_wide(BWT, primary, SA, sa_sample, idx_bits, device), device, _lib)
         return cls((_lib or lib()).fm_build(BWT, primary, SA, sa_sample, idx_bits, device), device, _lib)
 
     @classmethod
     def from_bwt_only(cls, BWT, primary: int, sa_sample: int = 32, idx_bits: int | None = None, device: int = 0,
-                      _lib: CapsLib | None = None) -> "FMIndex":
+                      _lib: CapsLib | None = None, wide: bool = False) -> "FMIndex":
         """An index that locates from (BWT, primary) ALONE: the SA samples come from an LF walk over the index itself, the blob is
-        the one ``from_bwt`` builds with the suffix array.  Not the BWT of any text: CapsSaError with code -1."""
+        the one ``from_bwt`` builds with the suffix array.  Not the BWT of any text: CapsSaError with code -1.  wide=True: not
+        built for the wide format, CapsSaError with code -2."""
+        if wide:
+            raise CapsSaError(-2, "the build from the BWT alone is not built for the wide format (build with the suffix array: from_bwt(..., wide=True))")
         return cls((_lib or lib()).fm_build_from_bwt(BWT, primary, sa_sample, idx_bits, device), device, _lib)
 
     @classmethod
-    def from_suffix_array(cls, sa_obj: "SuffixArray", sa_sample: int = 32) -> "FMIndex":
+    def from_suffix_array(cls, sa_obj: "SuffixArray", sa_sample: int = 32, wide: bool = False) -> "FMIndex":
         """From a constructed ``SuffixArray(..., bwt=True)``."""
-        return cls.from_bwt(sa_obj.BWT(), sa_obj.primary(), sa_obj.SA(), sa_sample, sa_obj._bits, sa_obj._device)
+        return cls.from_bwt(sa_obj.BWT(), sa_obj.primary(), sa_obj.SA(), sa_sample, sa_obj._bits, sa_obj._device, wide=wide)
 
     @property
     def n(self) -> int:
         return self._n
+
+    @property
+    def wide(self) -> bool:
+        """The wide format ("CAPSFMW1"): 1 .. 256 distinct bytes, no extract."""
+        return self._wide
+
+    @property
+    def sigma(self) -> int:
+        """The number of distinct bytes of the indexed text."""
+        return self._sigma
 
     @property
     def nbytes(self) -> int:

@@ -124,12 +124,13 @@ SHARD_EXPORTS = ["shard_create", "shard_destroy", "shard_info", "shard_phase1", 
 EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_bytes", "workspace_bytes", "workspace_bytes_ex", "release_cache", "host_alloc", "host_free", "gen_rand_seq",
            "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_from_bwt_workspace_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device",
            "fm_index_bytes_ex", "fm_add_text_samples", "fm_add_text_samples_device", "fm_extract_workspace_bytes", "fm_extract", "fm_extract_device",
-           "fm_match", "fm_match_device", "fm_mems_workspace_bytes", "fm_mems", "fm_mems_device"] + SHARD_EXPORTS + [
+           "fm_match", "fm_match_device", "fm_mems_workspace_bytes", "fm_mems", "fm_mems_device", "fm_wide_index_bytes",
+           "fm_wide_workspace_bytes"] + SHARD_EXPORTS + [
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
     for name in ("build", "build_multi", "build_device", "verify_device", "verify_slice_device", "sort_suffixes", "sort_segments", "merge",
                  "upper_bound", "lcp", "build_bwt", "bwt_device", "inverse_bwt", "inverse_bwt_device", "fm_build", "fm_build_device",
-                 "fm_build_from_bwt", "fm_build_from_bwt_device")
+                 "fm_build_from_bwt", "fm_build_from_bwt_device", "fm_build_wide", "fm_build_wide_device")
 ]
 
 
@@ -213,7 +214,15 @@ class CapsLib:
         f("fm_mems_device").argtypes = [_vp, _u64, _vp, _vp, _u64, ctypes.c_uint32, _vp, _vp, _u64, _vp, _u64, _vp]
         f("fm_from_bwt_workspace_bytes").restype = _ci
         f("fm_from_bwt_workspace_bytes").argtypes = [_u64, ctypes.c_uint32, _ci, ctypes.POINTER(_u64)]
+        f("fm_wide_index_bytes").restype = _ci
+        f("fm_wide_index_bytes").argtypes = [_u64, ctypes.c_uint32, ctypes.c_uint32, _ci, ctypes.POINTER(_u64)]
+        f("fm_wide_workspace_bytes").restype = _ci
+        f("fm_wide_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
         for sfx in ("u32", "u64"):
+            f(f"fm_build_wide_{sfx}").restype = _ci
+            f(f"fm_build_wide_{sfx}").argtypes = [_vp, _u64, _u64, _vp, ctypes.c_uint32, _vp, _u64, _ci]
+            f(f"fm_build_wide_device_{sfx}").restype = _ci
+            f(f"fm_build_wide_device_{sfx}").argtypes = [_vp, _u64, _u64, _vp, ctypes.c_uint32, _vp, _u64, _vp, _u64, _vp]
             f(f"fm_build_from_bwt_{sfx}").restype = _ci
             f(f"fm_build_from_bwt_{sfx}").argtypes = [_vp, _u64, _u64, ctypes.c_uint32, _vp, _u64, _ci]
             f(f"fm_build_from_bwt_device_{sfx}").restype = _ci
@@ -468,6 +477,46 @@ class CapsLib:
         sfx, _ = _sfx(idx_bits)
         self._check(self._f(f"fm_build_device_{sfx}")(dBWT_ptr or None, n, int(primary), dSA_ptr or None, sa_sample, dIndex_ptr or None,
                                                       index_bytes, stream or None))
+
+    # ------------------------------------------------------------------ the wide format (include/caps_sa_hip.h "FM-index: the wide format")
+    def fm_wide_index_bytes(self, n: int, sigma: int = 0, sa_sample: int = 32, idx_bits: int = 32) -> int:
+        """Bytes of the wide index of n symbols over sigma distinct bytes (0: unknown, sized for 256)."""
+        out = _u64(0)
+        self._check(self._f("fm_wide_index_bytes")(n, sigma, sa_sample, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    def fm_wide_workspace_bytes(self, n: int, idx_bits: int = 32) -> int:
+        """Device workspace of fm_build_wide_device: two code buffers of n + 1 bytes and the tile counts."""
+        out = _u64(0)
+        self._check(self._f("fm_wide_workspace_bytes")(n, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    def fm_build_wide(self, BWT, primary: int, SA=None, sa_sample: int = 32, idx_bits: int | None = None, device: int = 0) -> np.ndarray:
+        """The wide index of (BWT, primary), 1 .. 256 distinct bytes, as one np.uint8 blob; arguments as for fm_build."""
+        B = self._text(BWT)
+        n = int(B.size)
+        if idx_bits is None:
+            idx_bits = 64 if (SA is not None and np.asarray(SA).dtype.itemsize == 8) or n > 0xFFFFFFFF else 32
+        sfx, dt = _sfx(idx_bits)
+        if SA is not None:
+            SA = np.ascontiguousarray(SA, dtype=dt)
+            if SA.size != n:
+                raise ValueError("SA must be the whole suffix array: n entries")
+        sigma = int(np.unique(B).size) if n else 1
+        blob = np.zeros(self.fm_wide_index_bytes(n, sigma, sa_sample if SA is not None else 0, idx_bits), dtype=np.uint8)
+        self._check(self._f(f"fm_build_wide_{sfx}")(B.ctypes.data if n else None, n, int(primary) if n else 0,
+                                                    SA.ctypes.data if SA is not None else None, sa_sample, blob.ctypes.data, blob.size, device))
+        total = int(blob[:256].view(np.uint64)[18])
+        assert total == blob.size, (total, blob.size)
+        return blob
+
+    def fm_build_wide_device(self, dBWT_ptr: int, n: int, primary: int, dSA_ptr: int, sa_sample: int, dIndex_ptr: int, index_capacity: int,
+                             dWS_ptr: int = 0, ws_bytes: int = 0, idx_bits: int = 32, stream: int = 0) -> None:
+        """The wide index in device memory; its size is header word 18 (at most fm_wide_index_bytes(n, 0, ..)).  Workspace dWS_ptr of
+        ws_bytes (fm_wide_workspace_bytes), or 0: allocated and freed by the call."""
+        sfx, _ = _sfx(idx_bits)
+        self._check(self._f(f"fm_build_wide_device_{sfx}")(dBWT_ptr or None, n, int(primary), dSA_ptr or None, sa_sample, dIndex_ptr or None,
+                                                           index_capacity, dWS_ptr or None, ws_bytes, stream or None))
 
     def fm_from_bwt_workspace_bytes(self, n: int, sa_sample: int = 32, idx_bits: int = 32) -> int:
         """Device workspace of fm_build_from_bwt_device: one entry per sample and O(n / 64) list nodes, no array of n entries."""

@@ -170,7 +170,9 @@ inline void inverse_bwt(const uint8_t* BWT, uint64_t n, uint64_t primary, char* 
 
 // FM-index over (BWT, primary) (include/caps_sa_hip.h "FM-index"; not in the reference): count and locate for batches of patterns,
 // extract for batches of text ranges (after add_text_samples), over texts of at most 4 distinct bytes.  The index is one blob (data(), size()); save / load write and read exactly it.  Every
-// error of the C ABI is thrown as std::runtime_error with its message.
+// error of the C ABI is thrown as std::runtime_error with its message.  build_wide makes the wide format (include/caps_sa_hip.h
+// "FM-index: the wide format") for 1 .. 256 distinct bytes: count, locate, matching_statistics and mems work on either blob,
+// add_text_samples and extract throw the ABI's error on a wide one.
 class FM_Index
 {
 public:
@@ -212,8 +214,44 @@ public:
         return fm;
     }
 
+    // The wide format, for a BWT of 1 .. 256 distinct bytes; SA as in build().  The blob is sized for the bytes that occur (counted
+    // here, one pass over the BWT) and cut to the size the library reports in its header.
+    template <typename idx_t>
+    static FM_Index build_wide(const uint8_t* BWT, uint64_t n, uint64_t primary, const idx_t* SA, uint32_t sa_sample = 32, int device = 0)
+    {
+        static_assert(std::is_same<idx_t, uint32_t>::value || std::is_same<idx_t, uint64_t>::value, "uint32_t or uint64_t");
+        FM_Index fm;
+        fm.device_ = device;
+        bool seen[256] = {};
+        uint32_t sigma = 0;
+        if (BWT)
+            for (uint64_t i = 0; i < n; ++i)
+                if (!seen[BWT[i]]) { seen[BWT[i]] = true; ++sigma; }
+        uint64_t bytes = 0;
+        check(caps_sa_hip_fm_wide_index_bytes(n, sigma, SA ? sa_sample : 0, (int)sizeof(idx_t), &bytes), "caps_sa_hip_fm_wide_index_bytes");
+        fm.blob_.resize(static_cast<std::size_t>(bytes));
+        if (sizeof(idx_t) == 4)
+            check(caps_sa_hip_fm_build_wide_u32(BWT, n, primary, reinterpret_cast<const uint32_t*>(SA), sa_sample, fm.blob_.data(), bytes, device),
+                  "caps_sa_hip_fm_build_wide_u32");
+        else
+            check(caps_sa_hip_fm_build_wide_u64(BWT, n, primary, reinterpret_cast<const uint64_t*>(SA), sa_sample, fm.blob_.data(), bytes, device),
+                  "caps_sa_hip_fm_build_wide_u64");
+        uint64_t total = 0;
+        std::memcpy(&total, fm.blob_.data() + 18 * 8, 8);      // header word 18: the blob's size
+        if (total <= bytes) fm.blob_.resize(static_cast<std::size_t>(total));
+        return fm;
+    }
+
     const uint8_t* data() const { return blob_.data(); }
     std::size_t size() const { return blob_.size(); }
+    bool wide() const { return blob_.size() >= 256 && std::memcmp(blob_.data(), "CAPSFMW1", 8) == 0; }
+    // the number of distinct bytes of the text (header word 5 of both formats)
+    uint32_t sigma() const
+    {
+        uint64_t v = 0;
+        if (blob_.size() >= 256) std::memcpy(&v, blob_.data() + 40, 8);
+        return static_cast<uint32_t>(v);
+    }
 
     // patterns: the concatenated bytes, off[j] .. off[j + 1] the j-th of them (off.size() = q + 1) -> first / count, q entries each
     void count(const std::string& patterns, const std::vector<uint64_t>& off, std::vector<uint64_t>& first, std::vector<uint64_t>& cnt) const

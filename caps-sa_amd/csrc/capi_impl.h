@@ -1319,7 +1319,7 @@ int fm_build_occ(Backend& be, const uint8_t* dB, uint64_t n, uint64_t primary, u
         if (sigma < 4) syms |= b << (8 * sigma);
         ++sigma;
     }
-    if (sigma > 4) return fail(CAPS_SA_EALPHABET, "the BWT has more than 4 distinct bytes: the FM-index packs 2-bit codes");
+    if (sigma > 4) return fail(CAPS_SA_EALPHABET, "the BWT has more than 4 distinct bytes: the FM-index packs 2-bit codes (caps_sa_hip_fm_build_wide_* builds the wide index for 1 .. 256)");
     h[FMH_SIGMA] = sigma;
     h[FMH_SYMS] = syms;
     const uint32_t tg = capped_grid(std::min<uint64_t>(n_tiles, 16384), FM_NT);
@@ -1625,6 +1625,352 @@ int fm_build_from_bwt_host(const uint8_t* B, uint64_t n, uint64_t primary, uint6
     });
 }
 
+// ---- the wide FM-index (include/caps_sa_hip.h "FM-index: the wide format"; kernels.h fmw_*) -----------------------------------------
+// header | table section (FMW_TAB_BYTES) | Lv level sections of n_blocks blocks | mark ranks | samples (the last two as in version 1)
+constexpr uint64_t FMW_MAGIC = 0x31574D4653504143ull;     // "CAPSFMW1"
+constexpr uint64_t FMW_VERSION = 1;
+// words 2 .. 4 and 12 .. 18 are version 1's (FMH_*: word 15 = the offset of level 0); the wide format's own:
+enum { FMWH_LV = 6, FMWH_OFF_TAB = 7, FMWH_LEVEL_BYTES = 8 };
+
+inline uint32_t fmw_levels(uint64_t sigma)
+{
+    uint32_t lv = 1;
+    while (lv < FMW_MAX_LV && (1ull << (2 * lv)) < sigma) ++lv;
+    return lv;
+}
+struct FmwLayout {
+    uint32_t Lv = 1;
+    uint64_t n_blocks = 0, n_samples = 0, off_tab = 0, off_lev0 = 0, level_bytes = 0, off_mrank = 0, off_samples = 0, total = 0;
+};
+inline FmwLayout fmw_layout(uint64_t n, uint64_t sigma, uint32_t s, int idx_bytes)
+{
+    auto up = [](uint64_t b) { return (b + 63) & ~uint64_t(63); };
+    const uint64_t rows = idx_bytes == 4 ? 128 : 256;
+    FmwLayout l;
+    l.Lv = fmw_levels(sigma);
+    l.n_blocks = (n + 1) / rows + 1;
+    l.n_samples = s && n ? (n - 1) / s + 1 : 0;
+    l.off_tab = FM_HDR_WORDS * sizeof(uint64_t);
+    l.off_lev0 = l.off_tab + FMW_TAB_BYTES;
+    l.level_bytes = l.n_blocks * (rows / 2);
+    l.off_mrank = l.off_lev0 + l.Lv * l.level_bytes;
+    l.off_samples = l.off_mrank + (s ? up(l.n_blocks * (uint64_t)idx_bytes) : 0);
+    l.total = l.off_samples + (s ? up(l.n_samples * (uint64_t)idx_bytes) : 0);
+    return l;
+}
+inline int fmw_index_bytes(uint64_t n, uint32_t sigma, uint32_t s, int idx_bytes, uint64_t* bytes)
+{
+    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (s && !fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be 0 (no samples) or a power of two in 1 .. 1024");
+    if (sigma > 256) return fail(CAPS_SA_EINVAL, "sigma must be 0 (unknown) or 1 .. 256");
+    *bytes = fmw_layout(n, sigma ? sigma : 256, s, idx_bytes).total;
+    return CAPS_SA_OK;
+}
+
+// the host's image of the table section
+struct FmwTable {
+    uint64_t w[FMW_TAB_BYTES / 8];
+    FmwTable() { std::memset(w, 0, sizeof w); }
+    uint8_t* letters() { return reinterpret_cast<uint8_t*>(w) + FMW_TAB_LETTERS; }
+    uint8_t* code_of() { return reinterpret_cast<uint8_t*>(w) + FMW_TAB_CODE; }
+    uint64_t* C() { return w + FMW_TAB_C / 8; }
+    uint64_t* zone() { return w + FMW_TAB_ZONE / 8; }
+    uint64_t* Z() { return w + FMW_TAB_Z / 8; }
+};
+// letters[] and code_of[] from the byte set (256 bits), in signed-char order; -> sigma
+inline uint32_t fmw_alphabet(const uint32_t* present, FmwTable& t)
+{
+    uint32_t sigma = 0;
+    for (uint32_t k = 0; k < 256; ++k) {                 // signed-char order: 0x80 .. 0xFF, then 0x00 .. 0x7F
+        const uint32_t b = k ^ 0x80u;
+        t.code_of()[b] = (uint8_t)(sigma < 256 ? sigma : 255);     // (the letters below b; 255 letters below 0x7F at most)
+        if ((present[b / 32] >> (b % 32)) & 1u) t.letters()[sigma++] = (uint8_t)b;
+    }
+    return sigma;
+}
+// zone[] and Z[][] from C[] (n >= 1): K[c] = the rows 0 .. n that store code c -- the letters of code c, and the '$' row with code
+// 0.  Level l orders the rows by (digit l - 1, .., digit 0), so code c comes from position 0 to the number of rows whose code has a
+// smaller digit-reversed value.
+inline void fmw_zones(uint64_t sigma, uint32_t Lv, const uint64_t* C, uint64_t* zone, uint64_t* Z)
+{
+    uint64_t K[256];
+    for (uint32_t c = 0; c < 256; ++c) K[c] = c < sigma ? C[c + 1] - C[c] + (c == 0 ? 1 : 0) : 0;
+    // (one pass per table, every call: the codes in digit-reversed order by a 256-entry bucket array, then a running sum)
+    uint32_t by_rev[256];
+    for (uint32_t r = 0; r < 256; ++r) by_rev[r] = 256;
+    for (uint32_t c = 0; c < sigma; ++c) {
+        uint32_t r = 0;
+        for (uint32_t l = 0; l < Lv; ++l) r = 4 * r + ((c >> (2 * l)) & 3u);
+        by_rev[r] = c;
+    }
+    for (uint32_t c = 0; c < 256; ++c) zone[c] = 0;
+    uint64_t below = 0;
+    for (uint32_t r = 0; r < 256; ++r)
+        if (by_rev[r] < 256) { zone[by_rev[r]] = below; below += K[by_rev[r]]; }
+    for (uint32_t i = 0; i < 4 * FMW_MAX_LV; ++i) Z[i] = 0;
+    for (uint32_t l = 0; l < Lv; ++l) {
+        uint64_t per[4] = {0, 0, 0, 0};
+        for (uint32_t k = 0; k < sigma; ++k) per[(k >> (2 * (Lv - 1 - l))) & 3u] += K[k];
+        for (uint32_t d = 1; d < 4; ++d) Z[4 * l + d] = Z[4 * l + d - 1] + per[d - 1];
+    }
+}
+
+// header and table section, checked on the host before any kernel reads the body; fills v (what the shared host code reads: n, s,
+// the sample counts) and w (the wide kernels' view of the blob at dIndex)
+inline int fmw_check(const uint64_t* h, const uint64_t* tab, uint64_t index_bytes, const void* dIndex, FmView& v, FmwView& w)
+{
+    if (h[FMH_VERSION] != FMW_VERSION) return fail(CAPS_SA_EINVAL, "wide FM-index of another format version");
+    const uint64_t ib = h[FMH_IDX_BYTES], n = h[FMH_N], s = h[FMH_S], sigma = h[FMH_SIGMA];
+    if (ib != 4 && ib != 8) return fail(CAPS_SA_EINVAL, "FM-index header: bad index width");
+    if (ib == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "FM-index header: n does not fit its index width");
+    if (n >= 1 && h[FMH_PRIMARY] >= n) return fail(CAPS_SA_EINVAL, "FM-index header: primary >= n");
+    if (s && !fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "FM-index header: bad sample distance");
+    if (sigma > 256 || sigma > n || (n >= 1 && sigma == 0)) return fail(CAPS_SA_EINVAL, "FM-index header: bad alphabet size");
+    const FmwLayout l = fmw_layout(n, sigma, (uint32_t)s, (int)ib);
+    if (h[FMWH_LV] != l.Lv) return fail(CAPS_SA_EINVAL, "FM-index header: the number of levels does not fit the alphabet size");
+    if (h[FMH_NBLOCKS] != l.n_blocks || h[FMWH_OFF_TAB] != l.off_tab || h[FMH_OFF_OCC] != l.off_lev0 || h[FMWH_LEVEL_BYTES] != l.level_bytes ||
+        h[FMH_OFF_MRANK] != l.off_mrank || h[FMH_OFF_SAMPLES] != l.off_samples || h[FMH_TOTAL] != l.total || h[FMH_NSAMPLES] != l.n_samples)
+        return fail(CAPS_SA_EINVAL, "FM-index header: section offsets do not fit n, the alphabet, the index width and the sample distance");
+    if (l.total > index_bytes) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than the FM-index (truncated blob)");
+    const uint8_t* letters = reinterpret_cast<const uint8_t*>(tab) + FMW_TAB_LETTERS;
+    const uint8_t* code_of = reinterpret_cast<const uint8_t*>(tab) + FMW_TAB_CODE;
+    const uint64_t *C = tab + FMW_TAB_C / 8, *zone = tab + FMW_TAB_ZONE / 8, *Z = tab + FMW_TAB_Z / 8;
+    {
+        uint32_t present[8] = {};
+        for (uint64_t c = 0; c < 256; ++c) {
+            if (c >= sigma) { if (letters[c]) return fail(CAPS_SA_EINVAL, "FM-index table: bad letters"); continue; }
+            if (c && (letters[c] ^ 0x80u) <= (letters[c - 1] ^ 0x80u)) return fail(CAPS_SA_EINVAL, "FM-index table: bad letters");
+            present[letters[c] / 32] |= 1u << (letters[c] % 32);
+        }
+        FmwTable t;
+        if (n) fmw_alphabet(present, t);
+        if (std::memcmp(t.code_of(), code_of, 256) != 0) return fail(CAPS_SA_EINVAL, "FM-index table: code_of[] does not fit the letters");
+    }
+    if (C[0] != 1 || C[256] != n + 1) return fail(CAPS_SA_EINVAL, "FM-index table: bad C[]");
+    for (uint32_t c = 0; c < 256; ++c)
+        if (C[c] > C[c + 1] || (c >= sigma && C[c] != n + 1)) return fail(CAPS_SA_EINVAL, "FM-index table: bad C[]");
+    {
+        uint64_t zn[256], Zn[4 * FMW_MAX_LV];
+        fmw_zones(n ? sigma : 0, l.Lv, C, zn, Zn);
+        if (std::memcmp(zn, zone, sizeof zn) != 0) return fail(CAPS_SA_EINVAL, "FM-index table: zone[] does not fit C[]");
+        if (std::memcmp(Zn, Z, sizeof Zn) != 0) return fail(CAPS_SA_EINVAL, "FM-index table: Z[][] does not fit C[]");
+    }
+    const char* base = static_cast<const char*>(dIndex);
+    v = FmView{};
+    v.n = n;
+    v.primary = h[FMH_PRIMARY];
+    v.n_blocks = l.n_blocks;
+    v.n_samples = l.n_samples;
+    v.s = (uint32_t)s;
+    w.n = n;
+    w.primary = h[FMH_PRIMARY];
+    w.n_blocks = l.n_blocks;
+    w.n_samples = l.n_samples;
+    w.lev_words = l.level_bytes / 4;
+    w.lev0 = reinterpret_cast<const uint32_t*>(base + l.off_lev0);
+    w.mrank = base + l.off_mrank;
+    w.samples = base + l.off_samples;
+    w.tab = reinterpret_cast<const uint64_t*>(base + l.off_tab);
+    w.sigma = (uint32_t)sigma;
+    w.Lv = l.Lv;
+    w.s = (uint32_t)s;
+    return CAPS_SA_OK;
+}
+constexpr const char* FMW_NOT_BUILT = "this is a wide FM-index (\"CAPSFMW1\"): text samples and extract are not built for the wide format";
+
+// any blob at dIndex (device memory) whose header h has been read: a narrow one fills v (w.Lv = 0), a wide one has its table
+// section read back and checked and fills both
+inline int fm_check_any(Backend& be, const uint64_t* h, uint64_t index_bytes, const void* dIndex, FmView& v, FmwView& w)
+{
+    w = FmwView{};
+    if (h[FMH_MAGIC] != FMW_MAGIC) return fm_check_header(h, index_bytes, dIndex, v);
+    if (index_bytes < FM_HDR_WORDS * sizeof(uint64_t) + FMW_TAB_BYTES) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than the FM-index (truncated blob)");
+    FmwTable t;
+    be.d2h(t.w, static_cast<const char*>(dIndex) + FM_HDR_WORDS * sizeof(uint64_t), FMW_TAB_BYTES);
+    be.sync();
+    return fmw_check(h, t.w, index_bytes, dIndex, v, w);
+}
+
+template <typename idx_t>
+int fmw_check_build(const void* B, uint64_t n, uint64_t primary, const void* SA, uint64_t s, const void* index, uint64_t index_bytes)
+{
+    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
+    if (SA && !fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be a power of two in 1 .. 1024");
+    if (!index) return fail(CAPS_SA_EINVAL, "null index");
+    if (n && !B) return fail(CAPS_SA_EINVAL, "null BWT");
+    if (n && primary >= n) return fail(CAPS_SA_EINVAL, "primary >= n");
+    // (the alphabet is not known yet: room for the smallest index is asked for here, for the actual one once the letters are counted)
+    if (index_bytes < fmw_layout(n, std::min<uint64_t>(n, 1), SA ? (uint32_t)s : 0u, (int)sizeof(idx_t)).total)
+        return fail(CAPS_SA_EINVAL, "index_bytes too small (caps_sa_hip_fm_wide_index_bytes)");
+    return CAPS_SA_OK;
+}
+
+// the workspace: present words | tile counts (FM_KEYS columns) | 256 totals | the code histogram (256 columns of FMW_HIST_WGS) |
+// two code buffers of n + 1 bytes (each up to a multiple of 64); every part 256-byte aligned.  No array of n index entries.
+constexpr uint32_t FMW_HIST_WGS = 1024;
+struct FmwPlan { size_t off_present, off_cnt, off_total, off_hist, off_a, off_b, bytes; uint64_t n_tiles, cap; uint32_t hist_wgs; };
+template <typename idx_t> FmwPlan fmw_plan(uint64_t n)
+{
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    FmwPlan p;
+    const uint64_t n_blocks = (n + 1) / FmGeom<idx_t>::ROWS + 1;
+    p.n_tiles = (n_blocks * FmGeom<idx_t>::ROWS + FM_TILE - 1) / FM_TILE;
+    p.cap = (n + 1 + 63) & ~uint64_t(63);
+    p.hist_wgs = (uint32_t)std::min<uint64_t>((n / FM_WROWS + 1 + FM_NT - 1) / FM_NT, FMW_HIST_WGS);
+    p.off_present = 0;
+    p.off_cnt = up(8 * sizeof(uint32_t));
+    p.off_total = p.off_cnt + up(FM_KEYS * p.n_tiles * sizeof(uint64_t));
+    p.off_hist = p.off_total + up(256 * sizeof(uint64_t));
+    p.off_a = p.off_hist + up(256ull * p.hist_wgs * sizeof(uint64_t));
+    p.off_b = p.off_a + up(p.cap);
+    p.bytes = p.off_b + up(p.cap) + 256;          // (+ the slack that aligns a caller's pointer)
+    return p;
+}
+inline int fmw_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
+{
+    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    *bytes = idx_bytes == 4 ? fmw_plan<uint32_t>(n).bytes : fmw_plan<uint64_t>(n).bytes;
+    return CAPS_SA_OK;
+}
+
+// the build on be's stream, workspace at base (256-byte aligned); synchronises.  capacity: the bytes at dIndex.
+template <typename idx_t>
+int run_fmw_build(Backend& be, const uint8_t* dB, uint64_t n, uint64_t primary, const idx_t* dSA, uint32_t s, char* dIndex, uint64_t capacity,
+                  char* base, const FmwPlan& p, uint64_t* total_out)
+{
+    if (!dSA) s = 0;
+    uint64_t h[FM_HDR_WORDS];
+    std::memset(h, 0, sizeof h);
+    FmwTable t;
+    uint64_t sigma = 0;
+    uint32_t* present = reinterpret_cast<uint32_t*>(base + p.off_present);
+    uint64_t* cnt = reinterpret_cast<uint64_t*>(base + p.off_cnt);
+    uint64_t* total = reinterpret_cast<uint64_t*>(base + p.off_total);
+    uint64_t* hist = reinterpret_cast<uint64_t*>(base + p.off_hist);
+    uint8_t* cur = reinterpret_cast<uint8_t*>(base + p.off_a);
+    uint8_t* nxt = reinterpret_cast<uint8_t*>(base + p.off_b);
+    if (n) {
+        be.memset(present, 0, 8 * sizeof(uint32_t));
+        CAPS_LAUNCH(fm_probe_kernel, capped_grid(std::min<uint64_t>((n + 16ull * FM_NT - 1) / (16ull * FM_NT), 4096), FM_NT), FM_NT, be, dB, n, present);
+        uint32_t pm[8];
+        be.d2h(pm, present, sizeof pm);
+        be.sync();
+        sigma = fmw_alphabet(pm, t);
+    }
+    const FmwLayout l = fmw_layout(n, sigma, s, (int)sizeof(idx_t));
+    if (capacity < l.total)
+        return fail(CAPS_SA_EINVAL, ("index_bytes too small: the BWT has " + std::to_string(sigma) + " distinct bytes (caps_sa_hip_fm_wide_index_bytes)").c_str());
+    h[FMH_MAGIC] = FMW_MAGIC; h[FMH_VERSION] = FMW_VERSION; h[FMH_N] = n; h[FMH_PRIMARY] = n ? primary : 0; h[FMH_IDX_BYTES] = sizeof(idx_t);
+    h[FMH_SIGMA] = sigma; h[FMWH_LV] = l.Lv; h[FMWH_OFF_TAB] = l.off_tab; h[FMWH_LEVEL_BYTES] = l.level_bytes;
+    h[FMH_S] = s; h[FMH_NSAMPLES] = l.n_samples; h[FMH_NBLOCKS] = l.n_blocks; h[FMH_OFF_OCC] = l.off_lev0; h[FMH_OFF_MRANK] = l.off_mrank;
+    h[FMH_OFF_SAMPLES] = l.off_samples; h[FMH_TOTAL] = l.total;
+    uint64_t* C = t.C();
+    C[0] = 1;
+    for (uint32_t c = 1; c <= 256; ++c) C[c] = n + 1;
+    if (n == 0) {
+        be.memset(dIndex + l.off_lev0, 0, l.total - l.off_lev0);
+    } else {
+        // the letters' table is read by the code kernel from its place in the blob
+        be.h2d(dIndex + l.off_tab, t.w, FMW_TAB_BYTES);
+        CAPS_LAUNCH(fmw_code_kernel, p.hist_wgs, FM_NT, be, dB, n, primary, reinterpret_cast<const uint8_t*>(dIndex + l.off_tab + FMW_TAB_CODE), cur, hist);
+        CAPS_LAUNCH(fm_scan_kernel, 256, FM_NT, be, hist, (uint64_t)p.hist_wgs, 0u, 256u, total);
+        uint64_t K[256];
+        be.d2h(K, total, sizeof K);
+        be.sync();
+        uint64_t sum = 0;
+        for (uint32_t c = 0; c < 256; ++c) sum += K[c];
+        if (K[0] == 0 || sum != n + 1) throw HipError("fm wide build: the symbol counts do not add up to n");
+        K[0] -= 1;                                           // (the '$' row)
+        for (uint32_t c = 0; c < 256; ++c) C[c + 1] = C[c] + K[c];
+        fmw_zones(sigma, l.Lv, C, t.zone(), t.Z());
+        const uint32_t tg = capped_grid(std::min<uint64_t>(p.n_tiles, 16384), FM_NT);
+        for (uint32_t lev = 0; lev < l.Lv; ++lev) {
+            const uint32_t shift = 2 * (l.Lv - 1 - lev);
+            uint32_t* occ = reinterpret_cast<uint32_t*>(dIndex + l.off_lev0 + lev * l.level_bytes);
+            CAPS_LAUNCH(fmw_count_kernel, tg, FM_NT, be, (const uint8_t*)cur, n, p.n_tiles, shift, cnt);
+            CAPS_LAUNCH(fm_scan_kernel, 4, FM_NT, be, cnt, p.n_tiles, 0u, 4u, total);
+            CAPS_LAUNCH((fmw_pack_kernel<idx_t>), tg, FM_NT, be, (const uint8_t*)cur, n, p.n_tiles, l.n_blocks, shift, (const uint64_t*)cnt, occ);
+            if (lev + 1 < l.Lv) {
+                const uint64_t* Z = t.Z() + 4 * lev;
+                CAPS_LAUNCH(fmw_scatter_kernel, tg, FM_NT, be, (const uint8_t*)cur, nxt, n, p.cap, p.n_tiles, shift, (const uint64_t*)cnt, Z[1], Z[2], Z[3]);
+                std::swap(cur, nxt);
+            }
+        }
+        uint64_t marked = 0;
+        if (s) {
+            const uint64_t mrank_end = l.off_mrank + l.n_blocks * sizeof(idx_t), samples_end = l.off_samples + l.n_samples * sizeof(idx_t);
+            if (l.off_samples > mrank_end) be.memset(dIndex + mrank_end, 0, l.off_samples - mrank_end);
+            if (l.total > samples_end) be.memset(dIndex + samples_end, 0, l.total - samples_end);
+            uint32_t* occ = reinterpret_cast<uint32_t*>(dIndex + l.off_lev0);
+            idx_t* mrank = reinterpret_cast<idx_t*>(dIndex + l.off_mrank);
+            idx_t* samples = reinterpret_cast<idx_t*>(dIndex + l.off_samples);
+            CAPS_LAUNCH((fm_mark_kernel<idx_t>), tg, FM_NT, be, dSA, n, p.n_tiles, l.n_blocks, s, occ, mrank, cnt);
+            CAPS_LAUNCH(fm_scan_kernel, 1, FM_NT, be, cnt, p.n_tiles, 4u, 1u, total);
+            CAPS_LAUNCH((fm_sample_kernel<idx_t>), tg, FM_NT, be, dSA, n, p.n_tiles, l.n_blocks, s, (const uint32_t*)occ, mrank, (const uint64_t*)cnt, samples,
+                        l.n_samples);
+            be.d2h(&marked, total + 4, sizeof(uint64_t));
+        }
+        be.sync();
+        if (s && marked != l.n_samples)
+            return fail(CAPS_SA_EINVAL, ("SA is not the suffix array of a text of n symbols: it holds " + std::to_string(marked) + " multiples of sa_sample, a suffix array " +
+                                         std::to_string(l.n_samples)).c_str());
+    }
+    be.h2d(dIndex + l.off_tab, t.w, FMW_TAB_BYTES);
+    be.h2d(dIndex, h, sizeof h);
+    be.sync();
+    if (total_out) *total_out = l.total;
+    return CAPS_SA_OK;
+}
+
+template <typename idx_t>
+int fmw_build_device(const void* dB, uint64_t n, uint64_t primary, const void* dSA, uint64_t s, void* dIndex, uint64_t index_bytes, void* workspace,
+                     uint64_t workspace_bytes, void* stream)
+{
+    if (int rc = fmw_check_build<idx_t>(dB, n, primary, dSA, s, dIndex, index_bytes)) return rc;
+    const FmwPlan p = fmw_plan<idx_t>(n);
+    if (workspace && workspace_bytes < p.bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_fm_wide_workspace_bytes)");
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);                                    // a null workspace: allocated here, freed on return
+        if (!workspace) workspace = da.get<char>(p.bytes);
+        char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+        return run_fmw_build<idx_t>(be, static_cast<const uint8_t*>(dB), n, primary, static_cast<const idx_t*>(dSA), (uint32_t)s,
+                                    static_cast<char*>(dIndex), index_bytes, base, p, nullptr);
+    });
+}
+
+// host buffers: BWT and SA up, the index built at the head of the host-path block and downloaded; it stays there for the host queries
+template <typename idx_t>
+int fmw_build_host(const uint8_t* B, uint64_t n, uint64_t primary, const idx_t* SA, uint64_t s, void* index, uint64_t index_bytes, int device)
+{
+    if (int rc = fmw_check_build<idx_t>(B, n, primary, SA, s, index, index_bytes)) return rc;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        hc.fm_host = nullptr;
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const FmwPlan p = fmw_plan<idx_t>(n);
+        const uint64_t room = std::min<uint64_t>(index_bytes, fmw_layout(n, 256, SA ? (uint32_t)s : 0u, (int)sizeof(idx_t)).total);
+        const size_t off_B = up(room), off_SA = off_B + up(n ? n : 1), off_ws = off_SA + (SA ? up(n * sizeof(idx_t)) : 0), total = off_ws + p.bytes;
+        fm_host_block(hc, be, device, total);
+        uint8_t* dB = reinterpret_cast<uint8_t*>(hc.base + off_B);
+        idx_t* dSA = SA ? reinterpret_cast<idx_t*>(hc.base + off_SA) : nullptr;
+        be.h2d(dB, B, n);
+        if (SA) be.h2d(dSA, SA, n * sizeof(idx_t));
+        uint64_t made = 0;
+        if (int rc = run_fmw_build<idx_t>(be, dB, n, primary, dSA, (uint32_t)s, hc.base, room, hc.base + off_ws, p, &made)) return rc;
+        be.d2h(index, hc.base, made);
+        be.sync();
+        fm_mark_resident(hc, index, made);
+        return CAPS_SA_OK;
+    });
+}
+
 // count on device arrays; `hdr`: the header when the caller has read it already (the host forms), else it is read back here
 inline int run_fm_count(Backend& be, const void* dIndex, uint64_t index_bytes, const uint64_t* hdr, const void* dPat, const void* dPatOff, uint64_t q,
                         void* dFirst, void* dCount)
@@ -1633,7 +1979,8 @@ inline int run_fm_count(Backend& be, const void* dIndex, uint64_t index_bytes, c
     if (hdr) std::memcpy(h, hdr, sizeof h);
     else { be.d2h(h, dIndex, sizeof h); be.sync(); }
     FmView v;
-    if (int rc = fm_check_header(h, index_bytes, dIndex, v)) return rc;
+    FmwView w;
+    if (int rc = fm_check_any(be, h, index_bytes, dIndex, v, w)) return rc;
     if (q == 0) return CAPS_SA_OK;
     uint64_t* words = fm_words(be);
     uint32_t* flags = reinterpret_cast<uint32_t*>(words);
@@ -1647,6 +1994,13 @@ inline int run_fm_count(Backend& be, const void* dIndex, uint64_t index_bytes, c
     if (v.n == 0) {
         be.memset(dFirst, 0, q * sizeof(uint64_t));
         be.memset(dCount, 0, q * sizeof(uint64_t));
+    } else if (w.Lv) {
+        if (h[FMH_IDX_BYTES] == 4)
+            CAPS_LAUNCH((fmw_count_q_kernel<uint32_t>), g, FM_NT, be, w, static_cast<const uint8_t*>(dPat), static_cast<const uint64_t*>(dPatOff), q,
+                        static_cast<uint64_t*>(dFirst), static_cast<uint64_t*>(dCount));
+        else
+            CAPS_LAUNCH((fmw_count_q_kernel<uint64_t>), g, FM_NT, be, w, static_cast<const uint8_t*>(dPat), static_cast<const uint64_t*>(dPatOff), q,
+                        static_cast<uint64_t*>(dFirst), static_cast<uint64_t*>(dCount));
     } else if (h[FMH_IDX_BYTES] == 4) {
         CAPS_LAUNCH((fm_count_kernel<uint32_t>), g, FM_NT, be, v, static_cast<const uint8_t*>(dPat), static_cast<const uint64_t*>(dPatOff), q,
                     static_cast<uint64_t*>(dFirst), static_cast<uint64_t*>(dCount));
@@ -1677,7 +2031,8 @@ inline int run_fm_locate(Backend& be, const void* dIndex, uint64_t index_bytes, 
     if (hdr) std::memcpy(h, hdr, sizeof h);
     else { be.d2h(h, dIndex, sizeof h); be.sync(); }
     FmView v;
-    if (int rc = fm_check_header(h, index_bytes, dIndex, v)) return rc;
+    FmwView w;
+    if (int rc = fm_check_any(be, h, index_bytes, dIndex, v, w)) return rc;
     if (v.s == 0 && v.n) return fail(CAPS_SA_EUNSUPPORTED, "this FM-index was built without SA samples: it can count, not locate");
     if (q == 0) return CAPS_SA_OK;
     uint64_t* words = fm_words(be);
@@ -1697,7 +2052,13 @@ inline int run_fm_locate(Backend& be, const void* dIndex, uint64_t index_bytes, 
     if (o_end == o_begin || v.n == 0) return CAPS_SA_OK;
     if (!dPos) return fail(CAPS_SA_EINVAL, "null pointer");
     const uint32_t lg = capped_grid(std::min<uint64_t>((o_end - o_begin + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
-    if (h[FMH_IDX_BYTES] == 4)
+    if (w.Lv && h[FMH_IDX_BYTES] == 4)
+        CAPS_LAUNCH((fmw_locate_kernel<uint32_t>), lg, FM_NT, be, w, static_cast<const uint64_t*>(dFirst), static_cast<const uint64_t*>(dCount),
+                    static_cast<const uint64_t*>(dOutOff), q, o_begin, o_end, static_cast<uint64_t*>(dPos), flags);
+    else if (w.Lv)
+        CAPS_LAUNCH((fmw_locate_kernel<uint64_t>), lg, FM_NT, be, w, static_cast<const uint64_t*>(dFirst), static_cast<const uint64_t*>(dCount),
+                    static_cast<const uint64_t*>(dOutOff), q, o_begin, o_end, static_cast<uint64_t*>(dPos), flags);
+    else if (h[FMH_IDX_BYTES] == 4)
         CAPS_LAUNCH((fm_locate_kernel<uint32_t>), lg, FM_NT, be, v, static_cast<const uint64_t*>(dFirst), static_cast<const uint64_t*>(dCount),
                     static_cast<const uint64_t*>(dOutOff), q, o_begin, o_end, static_cast<uint64_t*>(dPos), flags);
     else
@@ -1734,11 +2095,20 @@ inline void fm_upload(HostPathCache& hc, Backend& be, int device, const void* in
     be.sync();
     fm_mark_resident(hc, index, blob);
 }
-inline int fm_host_header(const void* index, uint64_t index_bytes, uint64_t* h, FmView& v)
+// w: a call that answers wide blobs passes it (w->Lv = 0 for a narrow blob); without it a wide blob is CAPS_SA_EUNSUPPORTED
+inline int fm_host_header(const void* index, uint64_t index_bytes, uint64_t* h, FmView& v, FmwView* w = nullptr)
 {
     if (!index) return fail(CAPS_SA_EINVAL, "null index");
     if (index_bytes < FM_HDR_WORDS * sizeof(uint64_t)) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than an FM-index header");
     std::memcpy(h, index, FM_HDR_WORDS * sizeof(uint64_t));
+    if (w) *w = FmwView{};
+    if (h[FMH_MAGIC] == FMW_MAGIC) {
+        if (!w) return fail(CAPS_SA_EUNSUPPORTED, FMW_NOT_BUILT);
+        if (index_bytes < FM_HDR_WORDS * sizeof(uint64_t) + FMW_TAB_BYTES) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than the FM-index (truncated blob)");
+        FmwTable t;
+        std::memcpy(t.w, static_cast<const char*>(index) + FM_HDR_WORDS * sizeof(uint64_t), FMW_TAB_BYTES);
+        return fmw_check(h, t.w, index_bytes, index, v, *w);
+    }
     return fm_check_header(h, index_bytes, index, v);
 }
 
@@ -1747,7 +2117,8 @@ inline int fm_count_host(const void* index, uint64_t index_bytes, const uint8_t*
 {
     uint64_t h[FM_HDR_WORDS];
     FmView v;
-    if (int rc = fm_host_header(index, index_bytes, h, v)) return rc;
+    FmwView w;
+    if (int rc = fm_host_header(index, index_bytes, h, v, &w)) return rc;
     if (q == 0) return CAPS_SA_OK;
     if (!patoff || !first || !count) return fail(CAPS_SA_EINVAL, "null pointer");
     for (uint64_t j = 0; j < q; ++j)
@@ -1779,7 +2150,8 @@ inline int fm_locate_host(const void* index, uint64_t index_bytes, const uint64_
 {
     uint64_t h[FM_HDR_WORDS];
     FmView v;
-    if (int rc = fm_host_header(index, index_bytes, h, v)) return rc;
+    FmwView w;
+    if (int rc = fm_host_header(index, index_bytes, h, v, &w)) return rc;
     if (v.s == 0 && v.n) return fail(CAPS_SA_EUNSUPPORTED, "this FM-index was built without SA samples: it can count, not locate");
     if (q == 0) return CAPS_SA_OK;
     if (!outoff || !first || !count) return fail(CAPS_SA_EINVAL, "null pointer");
@@ -1819,6 +2191,7 @@ inline int run_fm_add_text_samples(Backend& be, char* dIndex, uint64_t capacity,
     if (hdr) std::memcpy(h, hdr, sizeof h);
     else { be.d2h(h, dIndex, sizeof h); be.sync(); }
     FmView v;
+    if (h[FMH_MAGIC] == FMW_MAGIC) return fail(CAPS_SA_EUNSUPPORTED, FMW_NOT_BUILT);
     if (int rc = fm_check_header(h, capacity, dIndex, v)) return rc;
     if (v.s == 0) return fail(CAPS_SA_EUNSUPPORTED, "this FM-index was built without SA samples: text samples are taken from them");
     if (t < v.s) return fail(CAPS_SA_EINVAL, "text_sample must be a power of two in sa_sample .. 1024");
@@ -1928,6 +2301,7 @@ inline int run_fm_extract(Backend& be, const void* dIndex, uint64_t index_bytes,
     if (hdr) std::memcpy(h, hdr, sizeof h);
     else { be.d2h(h, dIndex, sizeof h); be.sync(); }
     FmView v;
+    if (h[FMH_MAGIC] == FMW_MAGIC) return fail(CAPS_SA_EUNSUPPORTED, FMW_NOT_BUILT);
     if (int rc = fm_check_header(h, index_bytes, dIndex, v)) return rc;
     if (h[FMH_VERSION] != FM_VERSION_TEXT)
         return fail(CAPS_SA_EUNSUPPORTED, "this FM-index has no text-position samples (format version 1): caps_sa_hip_fm_add_text_samples first");
@@ -2048,7 +2422,7 @@ inline int fm_match_offsets(Backend& be, const void* dPatOff, uint64_t q, uint64
 }
 
 // the match kernel over [o_begin, o_end) (not empty); n = 0: every length 0
-inline void launch_fm_match(Backend& be, const FmView& v, int W, const void* dPat, const void* dPatOff, uint64_t q, uint64_t o_begin, uint64_t o_end,
+inline void launch_fm_match(Backend& be, const FmView& v, const FmwView& w, int W, const void* dPat, const void* dPatOff, uint64_t q, uint64_t o_begin, uint64_t o_end,
                             uint32_t max_len, uint32_t* len, uint64_t* first, uint64_t* count)
 {
     const uint64_t total = o_end - o_begin;
@@ -2059,7 +2433,13 @@ inline void launch_fm_match(Backend& be, const FmView& v, int W, const void* dPa
         return;
     }
     const uint32_t g = capped_grid(std::min<uint64_t>((total + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
-    if (W == 4)
+    if (w.Lv && W == 4)
+        CAPS_LAUNCH((fmw_match_kernel<uint32_t>), g, FM_NT, be, w, static_cast<const uint8_t*>(dPat), static_cast<const uint64_t*>(dPatOff), q, o_begin,
+                    o_end, max_len, len, first, count);
+    else if (w.Lv)
+        CAPS_LAUNCH((fmw_match_kernel<uint64_t>), g, FM_NT, be, w, static_cast<const uint8_t*>(dPat), static_cast<const uint64_t*>(dPatOff), q, o_begin,
+                    o_end, max_len, len, first, count);
+    else if (W == 4)
         CAPS_LAUNCH((fm_match_kernel<uint32_t>), g, FM_NT, be, v, static_cast<const uint8_t*>(dPat), static_cast<const uint64_t*>(dPatOff), q, o_begin,
                     o_end, max_len, len, first, count);
     else
@@ -2075,13 +2455,14 @@ inline int run_fm_match(Backend& be, const void* dIndex, uint64_t index_bytes, c
     if (hdr) std::memcpy(h, hdr, sizeof h);
     else { be.d2h(h, dIndex, sizeof h); be.sync(); }
     FmView v;
-    if (int rc = fm_check_header(h, index_bytes, dIndex, v)) return rc;
+    FmwView w;
+    if (int rc = fm_check_any(be, h, index_bytes, dIndex, v, w)) return rc;
     if (q == 0) return CAPS_SA_OK;
     uint64_t o_begin = 0, o_end = 0;
     if (int rc = fm_match_offsets(be, dPatOff, q, v.n, o_begin, o_end)) return rc;
     if (o_end == o_begin) return CAPS_SA_OK;
     if (!dPat || !dLen) return fail(CAPS_SA_EINVAL, "null pointer");
-    launch_fm_match(be, v, (int)h[FMH_IDX_BYTES], dPat, dPatOff, q, o_begin, o_end, max_len, static_cast<uint32_t*>(dLen),
+    launch_fm_match(be, v, w, (int)h[FMH_IDX_BYTES], dPat, dPatOff, q, o_begin, o_end, max_len, static_cast<uint32_t*>(dLen),
                     static_cast<uint64_t*>(dFirst), static_cast<uint64_t*>(dCount));
     be.sync();
     return CAPS_SA_OK;
@@ -2116,7 +2497,8 @@ inline int fm_match_host(const void* index, uint64_t index_bytes, const uint8_t*
 {
     uint64_t h[FM_HDR_WORDS];
     FmView v;
-    if (int rc = fm_host_header(index, index_bytes, h, v)) return rc;
+    FmwView w;
+    if (int rc = fm_host_header(index, index_bytes, h, v, &w)) return rc;
     if (q == 0) return CAPS_SA_OK;
     if (!len) return fail(CAPS_SA_EINVAL, "null pointer");
     if (int rc = fm_match_host_check(pat, patoff, q)) return rc;
@@ -2184,7 +2566,8 @@ inline int run_fm_mems(Backend& be, DevAllocs& da, const void* dIndex, uint64_t 
     if (hdr) std::memcpy(h, hdr, sizeof h);
     else { be.d2h(h, dIndex, sizeof h); be.sync(); }
     FmView v;
-    if (int rc = fm_check_header(h, index_bytes, dIndex, v)) return rc;
+    FmwView w;
+    if (int rc = fm_check_any(be, h, index_bytes, dIndex, v, w)) return rc;
     if (q == 0) {
         if (dMemOff) { be.memset(dMemOff, 0, sizeof(uint64_t)); be.sync(); }
         if (offsets_written) *offsets_written = dMemOff != nullptr;
@@ -2210,7 +2593,7 @@ inline int run_fm_mems(Backend& be, DevAllocs& da, const void* dIndex, uint64_t 
     uint64_t* colbase = reinterpret_cast<uint64_t*>(ws + p.off_base);
     uint64_t* words = fm_words(be);
     const uint64_t* off = static_cast<const uint64_t*>(dPatOff);
-    launch_fm_match(be, v, (int)h[FMH_IDX_BYTES], dPat, dPatOff, q, o_begin, o_end, 0u, len, dMems ? first : nullptr, dMems ? count : nullptr);
+    launch_fm_match(be, v, w, (int)h[FMH_IDX_BYTES], dPat, dPatOff, q, o_begin, o_end, 0u, len, dMems ? first : nullptr, dMems ? count : nullptr);
     const uint32_t g = capped_grid(std::min<uint64_t>((p.padded + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
     const uint32_t qg = capped_grid(std::min<uint64_t>((q + 1 + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
     CAPS_LAUNCH(fm_mem_flag_kernel, g, FM_NT, be, (const uint32_t*)len, off, q, total, p.padded, std::max<uint32_t>(min_len, 1u), slot);
@@ -2257,7 +2640,8 @@ inline int fm_mems_host(const void* index, uint64_t index_bytes, const uint8_t* 
 {
     uint64_t h[FM_HDR_WORDS];
     FmView v;
-    if (int rc = fm_host_header(index, index_bytes, h, v)) return rc;
+    FmwView w;
+    if (int rc = fm_host_header(index, index_bytes, h, v, &w)) return rc;
     if (!memoff) return fail(CAPS_SA_EINVAL, "null pointer");
     if (q == 0) { memoff[0] = 0; return CAPS_SA_OK; }
     if (int rc = fm_match_host_check(pat, patoff, q)) return rc;
@@ -2710,6 +3094,19 @@ int CAPS_API(fm_index_bytes)(uint64_t n, uint32_t sa_sample, int idx_bytes, uint
     { return caps::fm_build_host<IDX>(BWT, n, primary, SA, sa_sample, index, index_bytes, device); }
 CAPS_DEFINE_FM(u32, uint32_t)
 CAPS_DEFINE_FM(u64, uint64_t)
+int CAPS_API(fm_wide_index_bytes)(uint64_t n, uint32_t sigma, uint32_t sa_sample, int idx_bytes, uint64_t* bytes)
+{ return caps::fmw_index_bytes(n, sigma, sa_sample, idx_bytes, bytes); }
+int CAPS_API(fm_wide_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::fmw_workspace_bytes(n, idx_bytes, bytes); }
+#define CAPS_DEFINE_FM_WIDE(SFX, IDX)                                                                                                \
+    int CAPS_API(fm_build_wide_device_##SFX)(const void* dBWT, uint64_t n, uint64_t primary, const void* dSA, uint32_t sa_sample,   \
+                                             void* dIndex, uint64_t index_capacity, void* workspace, uint64_t workspace_bytes, void* stream) \
+    { return caps::fmw_build_device<IDX>(dBWT, n, primary, dSA, sa_sample, dIndex, index_capacity, workspace, workspace_bytes, stream); } \
+    int CAPS_API(fm_build_wide_##SFX)(const uint8_t* BWT, uint64_t n, uint64_t primary, const IDX* SA, uint32_t sa_sample,          \
+                                      void* index, uint64_t index_capacity, int device)                                             \
+    { return caps::fmw_build_host<IDX>(BWT, n, primary, SA, sa_sample, index, index_capacity, device); }
+CAPS_DEFINE_FM_WIDE(u32, uint32_t)
+CAPS_DEFINE_FM_WIDE(u64, uint64_t)
+#undef CAPS_DEFINE_FM_WIDE
 int CAPS_API(fm_from_bwt_workspace_bytes)(uint64_t n, uint32_t sa_sample, int idx_bytes, uint64_t* bytes)
 { return caps::fm_from_bwt_workspace_bytes(n, sa_sample, idx_bytes, bytes); }
 #define CAPS_FM_FROM_BWT(SFX, IDX)                                                                                                  \

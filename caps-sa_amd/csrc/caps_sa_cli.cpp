@@ -4,11 +4,18 @@
 //     caps_sa <input_path> <output_path> [subproblem-count] [bounded-context] [--pretty-print] [--gpus N] [--bwt PATH]
 //     caps_sa --inverse-bwt IN.bwt OUT
 //     caps_sa <input_path> <output_path> [subproblem-count] --fm-index PATH [--fm-sample S] [--fm-text-sample T]
+//     caps_sa <input_path> <output_path> [subproblem-count] --raw [--bwt PATH] [--fm-index PATH [--fm-sample S]]
 //     caps_sa --fm-search INDEX PATTERNS [--locate K]
 //     caps_sa --fm-mems INDEX PATTERNS [--min-len L]
 //     caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S] [--fm-text-sample T]
 //     caps_sa --fm-extract INDEX RANGES
 //
+// * --raw (not in the reference; on the build line only): the text as given, no remap to {A,C,G,T} -- SA, LCP and --bwt are those of
+//   the file's own bytes, and --fm-index PATH writes the wide format (include/caps_sa_hip.h "FM-index: the wide format") for 1 .. 256
+//   distinct bytes.  --fm-search and --fm-mems tell a wide index by its magic and take the pattern lines as bytes, unremapped (a
+//   line still ends at '\n' or "\r\n").  The wide format has no text samples and no extract: --raw with --fm-text-sample, and
+//   --fm-extract on a wide index, are refused with a message that names the format, before anything is written.  Without --raw
+//   nothing changes;
 // * --fm-mems INDEX PATTERNS [--min-len L] (not in the reference): one pattern per line of PATTERNS, remapped like the text; per
 //   line the number of its maximal exact matches of at least L (default 1) bytes against the text (include/caps_sa_hip.h "FM-index:
 //   matching statistics"), then "start:length:count" for each by increasing end: start within the pattern, count = its occurrences
@@ -84,7 +91,7 @@ static bool parse_count(const std::string& s, size_t& out)
 
 template <typename idx_t>
 static int run(const std::string& text, const std::string& out_path, size_t p, size_t ctx, bool pretty, const std::vector<int>& devices,
-               const std::string& bwt_path, const std::string& fm_path = std::string(), uint32_t fm_sample = 32, uint32_t fm_text_sample = 0)
+               const std::string& bwt_path, const std::string& fm_path = std::string(), uint32_t fm_sample = 32, uint32_t fm_text_sample = 0, bool raw = false)
 {
     if (p > std::numeric_limits<idx_t>::max()) { std::cerr << "subproblem-count does not fit the index type\n"; return EXIT_FAILURE; }
     // the bounded-context mode replays the reference's merge history, one GPU thread per merge node -- the top levels
@@ -120,14 +127,36 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
         if (!bwt) return EXIT_FAILURE;
     }
     if (!fm_path.empty()) {
-        CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::build<idx_t>(suf_arr.BWT(), suf_arr.n(), suf_arr.primary(), suf_arr.SA(), fm_sample);
+        CaPS_SA::FM_Index fm = raw ? CaPS_SA::FM_Index::build_wide<idx_t>(suf_arr.BWT(), suf_arr.n(), suf_arr.primary(), suf_arr.SA(), fm_sample)
+                                   : CaPS_SA::FM_Index::build<idx_t>(suf_arr.BWT(), suf_arr.n(), suf_arr.primary(), suf_arr.SA(), fm_sample);
         if (fm_text_sample) fm.add_text_samples(fm_text_sample);
         fm.save(fm_path);
-        std::cerr << "FM-index: " << fm.size() << " bytes, SA samples every " << fm_sample << " positions";
+        std::cerr << "FM-index: " << fm.size() << " bytes";
+        if (raw) std::cerr << " (wide format, " << fm.sigma() << " letters)";
+        std::cerr << ", SA samples every " << fm_sample << " positions";
         if (fm_text_sample) std::cerr << ", text samples every " << fm_text_sample;
         std::cerr << ".\n";
     }
     return 0;
+}
+
+// the lines of a PATTERNS file, concatenated: remapped like the text for an index of the remapped text, as bytes for a wide index
+// (which --raw wrote over the text's own bytes)
+static void read_patterns(const std::string& lines, bool as_bytes, std::string& pats, std::vector<uint64_t>& off)
+{
+    static const char lookup[4] = {'A', 'C', 'T', 'G'};
+    off.assign(1, 0);
+    for (size_t a = 0; a < lines.size();) {
+        size_t b = lines.find('\n', a);
+        if (b == std::string::npos) b = lines.size();
+        size_t e = b;
+        if (e > a && lines[e - 1] == '\r') --e;
+        if (as_bytes) pats.append(lines, a, e - a);
+        else
+            for (size_t j = a; j < e; ++j) pats.push_back(lookup[(std::toupper(static_cast<unsigned char>(lines[j])) & 0x6) >> 1]);
+        off.push_back(pats.size());
+        a = b + 1;
+    }
 }
 
 // caps_sa --fm-search INDEX PATTERNS [--locate K]: args = everything after the program name
@@ -143,18 +172,9 @@ static int fm_search_main(const std::vector<std::string>& args)
     if (!read_input(args[2], lines)) return EXIT_FAILURE;
     try {
         const CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::load(args[1]);
-        static const char lookup[4] = {'A', 'C', 'T', 'G'};
         std::string pats;
-        std::vector<uint64_t> off(1, 0);
-        for (size_t a = 0; a < lines.size();) {
-            size_t b = lines.find('\n', a);
-            if (b == std::string::npos) b = lines.size();
-            size_t e = b;
-            if (e > a && lines[e - 1] == '\r') --e;
-            for (size_t j = a; j < e; ++j) pats.push_back(lookup[(std::toupper(static_cast<unsigned char>(lines[j])) & 0x6) >> 1]);
-            off.push_back(pats.size());
-            a = b + 1;
-        }
+        std::vector<uint64_t> off;
+        read_patterns(lines, fm.wide(), pats, off);
         std::vector<uint64_t> first, cnt, out_off, pos;
         fm.count(pats, off, first, cnt);
         if (locate) fm.locate(first, cnt, k, out_off, pos);
@@ -186,18 +206,9 @@ static int fm_mems_main(const std::vector<std::string>& args)
     if (!read_input(args[2], lines)) return EXIT_FAILURE;
     try {
         const CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::load(args[1]);
-        static const char lookup[4] = {'A', 'C', 'T', 'G'};
         std::string pats;
-        std::vector<uint64_t> off(1, 0);
-        for (size_t a = 0; a < lines.size();) {
-            size_t b = lines.find('\n', a);
-            if (b == std::string::npos) b = lines.size();
-            size_t e = b;
-            if (e > a && lines[e - 1] == '\r') --e;
-            for (size_t j = a; j < e; ++j) pats.push_back(lookup[(std::toupper(static_cast<unsigned char>(lines[j])) & 0x6) >> 1]);
-            off.push_back(pats.size());
-            a = b + 1;
-        }
+        std::vector<uint64_t> off;
+        read_patterns(lines, fm.wide(), pats, off);
         std::vector<uint64_t> mem_off;
         std::vector<CaPS_SA::FM_Index::Mem> mems;
         fm.mems(pats, off, static_cast<uint32_t>(min_len), mem_off, mems);
@@ -318,6 +329,10 @@ static int fm_extract_main(const std::vector<std::string>& args)
     }
     try {
         const CaPS_SA::FM_Index fm = CaPS_SA::FM_Index::load(args[1]);
+        if (fm.wide()) {
+            std::cerr << "--fm-extract: " << args[1] << " is a wide FM-index (\"CAPSFMW1\", written by --raw --fm-index): extract is not built for the wide format\n";
+            return EXIT_FAILURE;
+        }
         if (fm.size() < 256 || std::memcmp(fm.data(), "CAPSFMI1", 8) != 0) {
             std::cerr << "--fm-extract: " << args[1] << " is not an FM-index of this library\n";
             return EXIT_FAILURE;
@@ -382,11 +397,12 @@ int main(int argc, char* argv[])
     for (int i = 1; i < argc; ++i)
         if (std::strcmp(argv[i], "--fm-extract") == 0) return fm_extract_main(std::vector<std::string>(argv + 1, argv + argc));
     std::vector<std::string> pos;
-    bool pretty = false, bwt = false, fm = false, fm_sample_given = false, fm_text_given = false;
+    bool pretty = false, bwt = false, fm = false, fm_sample_given = false, fm_text_given = false, raw = false;
     size_t gpus = 1, fm_sample = 32, fm_text_sample = 0;
     std::string bwt_path, fm_path;
     for (int i = 1; i < argc; ++i) {
         if (std::strcmp(argv[i], "--pretty-print") == 0) pretty = true;
+        else if (std::strcmp(argv[i], "--raw") == 0) raw = true;
         else if (std::strcmp(argv[i], "--bwt") == 0) {
             bwt = true;
             if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) bwt_path = argv[++i];
@@ -419,7 +435,7 @@ int main(int argc, char* argv[])
     if (pos.size() < 2) {
         std::cerr << "Usage: caps_sa <input_path> <output_path> <(optional)-subproblem-count> "
                      "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH> "
-                     "<(optional)--fm-index PATH [--fm-sample S] [--fm-text-sample T]>\n"
+                     "<(optional)--fm-index PATH [--fm-sample S] [--fm-text-sample T]> <(optional)--raw>\n"
                      "       caps_sa --inverse-bwt IN.bwt OUT\n"
                      "       caps_sa --fm-search INDEX PATTERNS [--locate K]\n"
                      "       caps_sa --fm-mems INDEX PATTERNS [--min-len L]\n"
@@ -447,6 +463,10 @@ int main(int argc, char* argv[])
         std::cerr << "--fm-text-sample: a power of two in the --fm-sample distance .. 1024, please (--fm-sample is " << fm_sample << ")\n";
         return EXIT_FAILURE;
     }
+    if (raw && fm_text_given) {
+        std::cerr << "--fm-text-sample: --raw --fm-index writes a wide FM-index (\"CAPSFMW1\"): text samples are not built for the wide format\n";
+        return EXIT_FAILURE;
+    }
     if (fm) {
         if (fm_path.empty()) { std::cerr << "--fm-index: missing output path (--fm-index PATH)\n"; return EXIT_FAILURE; }
         if (gpus > 1) { std::cerr << "--fm-index: the index is built on one GPU; --gpus " << gpus << " has no BWT to build it from\n"; return EXIT_FAILURE; }
@@ -459,8 +479,8 @@ int main(int argc, char* argv[])
 
     std::string text;
     if (!read_input(pos[0], text)) return EXIT_FAILURE;
-    // the byte remap of main.cpp:61-70, on all host threads like the reference's parallel_for
-    {
+    // the byte remap of main.cpp:61-70, on all host threads like the reference's parallel_for (--raw: the text as given)
+    if (!raw) {
         static const char lookup[4] = {'A', 'C', 'T', 'G'};
         const size_t n = text.size();
         const size_t nt = std::max<size_t>(1, std::min<size_t>(std::thread::hardware_concurrency(), n / (1u << 20) + 1));
@@ -478,8 +498,8 @@ int main(int argc, char* argv[])
 
     std::cerr << "Text length: " << text.size() << ".\n";
     try {
-        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample);
-        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample);
+        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw);
+        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw);
     } catch (const std::exception& e) {
         std::cerr << e.what() << "\n";
         return EXIT_FAILURE;

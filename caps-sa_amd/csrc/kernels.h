@@ -5777,6 +5777,431 @@ GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_mem_write_kernel(KCTX const uint32_t* __restri
     }
 }
 
+// ---- wide FM-index: 1 .. 256 letters (capi_impl.h fmw_*; include/caps_sa_hip.h "FM-index: the wide format") -------------------------
+// A 4-ary wavelet matrix over the letter codes, every level an Occ section of the blocks above.  A code has Lv base-4 digits, digit 0
+// the most significant; level 0 is the code sequence in row order ('$' row and the rows behind n: code 0), level l + 1 is level l
+// stably partitioned by its level-l digit.  With Z[l][d] = the rows of level l with a digit below d and zone[c] = where code c gets
+// from position 0:   p = r;  for l < Lv: d = digit_l(c), p = Z[l][d] + Occ_l(d, p);   LF(c, r) = C[c] + p - zone[c] - ['$' below r]
+// -- one line per level, the narrow step exactly when Lv = 1.  The table section (letters, code_of, C, zone, Z: FMW_TAB_BYTES from
+// FmwView::tab, checked on the host) is copied to LDS by every query workgroup; lanes index LDS, never a register array.  Every
+// position is kept inside 0 .. n + 1 and every block inside its level at every level, whatever the tables and the body hold.
+constexpr uint32_t FMW_MAX_LV = 4;
+constexpr uint32_t FMW_TAB_LETTERS = 0, FMW_TAB_CODE = 256, FMW_TAB_C = 512, FMW_TAB_ZONE = FMW_TAB_C + 257 * 8,
+                   FMW_TAB_Z = FMW_TAB_ZONE + 256 * 8, FMW_TAB_USED = FMW_TAB_Z + 4 * FMW_MAX_LV * 8;     // 4,744 bytes
+constexpr uint32_t FMW_TAB_WORDS = FMW_TAB_USED / 8;          // 593 words of 64 bits
+constexpr uint32_t FMW_TAB_BYTES = (FMW_TAB_USED + 63) / 64 * 64;                                         // 4,800 in the blob
+struct FmwView {
+    uint64_t n, primary;
+    uint64_t n_blocks, n_samples;
+    uint64_t lev_words;                        // 32-bit words of one level section
+    const uint32_t* lev0;                      // level l at lev0 + l * lev_words
+    const void* mrank;
+    const void* samples;
+    const uint64_t* tab;                       // the table section (device memory)
+    uint32_t sigma, Lv, s;                     // Lv = 0: not a wide blob
+};
+// views into the LDS copy of the table section
+HD const uint8_t* fmw_letters(const uint64_t* t) { return reinterpret_cast<const uint8_t*>(t) + FMW_TAB_LETTERS; }
+HD const uint8_t* fmw_codes(const uint64_t* t) { return reinterpret_cast<const uint8_t*>(t) + FMW_TAB_CODE; }
+HD const uint64_t* fmw_C(const uint64_t* t) { return t + FMW_TAB_C / 8; }
+HD const uint64_t* fmw_zone(const uint64_t* t) { return t + FMW_TAB_ZONE / 8; }
+HD const uint64_t* fmw_Z(const uint64_t* t) { return t + FMW_TAB_Z / 8; }
+#define FMW_LOAD_TABLE(tab, w)                                                                    \
+    SHARED_ARRAY(uint64_t, tab, FMW_TAB_WORDS);                                                   \
+    PAR(tid) { for (uint32_t k = tid; k < FMW_TAB_WORDS; k += FM_NT) tab[k] = (w).tab[k]; }       \
+    SYNC()
+
+// the block of position p of level l, inside the level whatever p is
+template <typename idx_t>
+HD const uint32_t* fmw_block_of(const FmwView& w, uint32_t l, uint64_t p)
+{
+    using G = FmGeom<idx_t>;
+    uint64_t b = p / G::ROWS;
+    if (b >= w.n_blocks) b = w.n_blocks - 1;
+    return w.lev0 + (uint64_t)l * w.lev_words + b * G::BW;
+}
+// the end of an LF step: position p of the last level -> the row, inside 0 .. n + 1
+HD uint64_t fmw_row(const FmwView& w, const uint64_t* tab, uint32_t c, uint64_t p, bool past_dollar)
+{
+    const uint64_t z = fmw_zone(tab)[c];
+    uint64_t k = p > z ? p - z : 0;
+    if (c == 0 && past_dollar && k) --k;
+    const uint64_t x = fmw_C(tab)[c] + k;
+    return x <= w.n + 1 ? x : w.n + 1;
+}
+// LF(c, lo) and LF(c, hi): both positions go down together, their two lines of a level are issued together
+template <typename idx_t>
+HD void fmw_lf2(const FmwView& w, const uint64_t* tab, uint32_t c, uint64_t& lo, uint64_t& hi)
+{
+    using G = FmGeom<idx_t>;
+    uint64_t pl = lo, ph = hi;
+    for (uint32_t l = 0; l < w.Lv; ++l) {
+        const uint32_t d = (c >> (2u * (w.Lv - 1u - l))) & 3u;
+        const uint64_t z = fmw_Z(tab)[4 * l + d];
+        const uint64_t a = fm_block_occ<idx_t>(fmw_block_of<idx_t>(w, l, pl), d, (uint32_t)(pl % G::ROWS), false);
+        const uint64_t b = fm_block_occ<idx_t>(fmw_block_of<idx_t>(w, l, ph), d, (uint32_t)(ph % G::ROWS), false);
+        pl = z + a <= w.n + 1 ? z + a : w.n + 1;
+        ph = z + b <= w.n + 1 ? z + b : w.n + 1;
+    }
+    lo = fmw_row(w, tab, c, pl, lo > w.primary + 1);
+    hi = fmw_row(w, tab, c, ph, hi > w.primary + 1);
+}
+
+// ---- the build ----
+// the codes of rows 0 .. n in row order (level 0), one byte each ('$' row: 0; the bytes up to the next multiple of 16: 0), and the
+// rows of every code: hist[code * K_GRID_DIM + workgroup] (fm_scan_kernel sums the columns).  code_of: the table in device memory.
+// The histogram has 8 copies in LDS, one per lane mod 8: with a few letters every lane of a wave would hit the same few words.
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fmw_code_kernel(KCTX const uint8_t* __restrict__ B, uint64_t n, uint64_t primary, const uint8_t* __restrict__ code_of,
+                                                uint8_t* __restrict__ codes, uint64_t* __restrict__ hist)
+{
+    static_assert(FM_NT == 256, "one thread per entry of lut[] and of every histogram copy");
+    SHARED_ARRAY(uint32_t, lut, 256);
+    SHARED_ARRAY(uint32_t, h, 8 * 256);
+    PAR(tid) {
+        lut[tid] = code_of[tid];
+        for (uint32_t k = 0; k < 8; ++k) h[k * 256 + tid] = 0;
+    }
+    SYNC();
+    const uint64_t chunks = n / FM_WROWS + 1, stride = (uint64_t)K_GRID_DIM * FM_NT;         // rows 0 .. n
+    for (uint64_t c0 = (uint64_t)K_BLOCK_IDX * FM_NT; c0 < chunks; c0 += stride) {           // block-uniform
+        PAR(tid) {
+            const uint64_t ch = c0 + tid;
+            if (ch < chunks) {
+                const uint64_t r0 = ch * FM_WROWS;
+                uint32_t out[4] = {0, 0, 0, 0};
+                uint32_t* hh = h + (tid & 7u) * 256;
+                if (r0 >= FM_WROWS && r0 + FM_WROWS <= n && !(primary + 1 >= r0 && primary + 1 < r0 + FM_WROWS)) {
+                    uint32_t x[4];
+                    UNROLL
+                    for (uint32_t k = 0; k < 4; ++k) x[k] = STREAM_LOAD(reinterpret_cast<const u32_any_align*>(B + r0) + k);
+                    uint32_t prev = B[r0 - 1];
+                    UNROLL
+                    for (uint32_t j = 0; j < FM_WROWS; ++j) {
+                        const uint32_t c = lut[prev];
+                        out[j / 4] |= c << (8u * (j % 4));
+                        FETCH_ADD_U32(&hh[c], 1u);
+                        prev = (x[j / 4] >> (8u * (j % 4))) & 0xFFu;
+                    }
+                } else {
+                    for (uint32_t j = 0; j < FM_WROWS; ++j) {
+                        const uint64_t r = r0 + j;
+                        if (r > n) continue;
+                        const uint32_t c = r == primary + 1 ? 0u : lut[B[r ? r - 1 : primary]];
+                        out[j / 4] |= c << (8u * (j % 4));
+                        FETCH_ADD_U32(&hh[c], 1u);
+                    }
+                }
+                UNROLL
+                for (uint32_t k = 0; k < 4; ++k) reinterpret_cast<uint32_t*>(codes + r0)[k] = out[k];
+            }
+        }
+    }
+    SYNC();
+    PAR(tid) {
+        uint64_t s = 0;
+        for (uint32_t k = 0; k < 8; ++k) s += h[k * 256 + tid];
+        hist[(uint64_t)tid * K_GRID_DIM + K_BLOCK_IDX] = s;
+    }
+}
+
+// the digit word of rows r0 .. r0 + 15 of a level (r0 a multiple of 16): digit = (code >> shift) & 3; rows behind n: 0
+HD uint32_t fmw_digit_word(const uint8_t* __restrict__ codes, uint64_t n, uint64_t r0, uint32_t shift)
+{
+    uint32_t w = 0;
+    if (r0 + FM_WROWS <= n + 1) {
+        uint32_t x[4];
+        UNROLL
+        for (uint32_t k = 0; k < 4; ++k) x[k] = reinterpret_cast<const uint32_t*>(codes + r0)[k];
+        UNROLL
+        for (uint32_t j = 0; j < FM_WROWS; ++j) w |= (((x[j / 4] >> (8u * (j % 4))) >> shift) & 3u) << (2u * j);
+    } else {
+        for (uint32_t j = 0; j < FM_WROWS; ++j)
+            if (r0 + j <= n) w |= (((uint32_t)codes[r0 + j] >> shift) & 3u) << (2u * j);
+    }
+    return w;
+}
+
+// fm_tile_count_kernel on a level's codes: per tile the rows of each digit -> cnt[digit * n_tiles + tile]
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fmw_count_kernel(KCTX const uint8_t* __restrict__ codes, uint64_t n, uint64_t n_tiles, uint32_t shift,
+                                                 uint64_t* __restrict__ cnt)
+{
+    SHARED_ARRAY(uint32_t, h, 4);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        PAR(tid) { if (tid < 4) h[tid] = 0; }
+        SYNC();
+        PAR(tid) {
+            uint32_t c[4] = {0, 0, 0, 0};
+            for (uint32_t j = 0; j < FM_ROUNDS; ++j) {
+                const uint64_t r0 = tile * FM_TILE + ((uint64_t)j * FM_NT + tid) * FM_WROWS;
+                const uint32_t w = fmw_digit_word(codes, n, r0, shift);
+                UNROLL
+                for (uint32_t k = 0; k < 4; ++k) c[k] += fm_word_rank(w, k, FM_WROWS);
+            }
+            for (uint32_t k = 0; k < 4; ++k) if (c[k]) FETCH_ADD_U32(&h[k], c[k]);
+        }
+        SYNC();
+        PAR(tid) { if (tid < 4) cnt[(uint64_t)tid * n_tiles + tile] = h[tid]; }
+        SYNC();
+    }
+}
+
+// fm_pack_kernel on a level's codes: the blocks of the level, mark words zero
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fmw_pack_kernel(KCTX const uint8_t* __restrict__ codes, uint64_t n, uint64_t n_tiles, uint64_t n_blocks, uint32_t shift,
+                                                const uint64_t* __restrict__ pre, uint32_t* __restrict__ occ)
+{
+    using G = FmGeom<idx_t>;
+    constexpr uint32_t BPR = FM_NT / G::CWN;      // blocks of a round
+    SHARED_ARRAY(uint32_t, tc, 4 * FM_NT);        // [digit][thread]
+    SHARED_ARRAY(uint64_t, bc, 4 * BPR);          // [digit][block of the round]: the sum, then the absolute count before the block
+    SHARED_ARRAY(uint64_t, run, 4);
+    TL_DECL(uint32_t, wd, 1);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        PAR(tid) { if (tid < 4) run[tid] = pre[(uint64_t)tid * n_tiles + tile]; }
+        SYNC();
+        for (uint32_t j = 0; j < FM_ROUNDS; ++j) {
+            const uint64_t w0 = (tile * FM_ROUNDS + j) * FM_NT;                     // first digit word of the round
+            PAR(tid) {
+                const uint32_t w = fmw_digit_word(codes, n, (w0 + tid) * FM_WROWS, shift);
+                TL(wd, tid, 0) = w;
+                UNROLL
+                for (uint32_t k = 0; k < 4; ++k) tc[k * FM_NT + tid] = fm_word_rank(w, k, FM_WROWS);
+            }
+            SYNC();
+            PAR(tid) {
+                if (tid % G::CWN == 0) {
+                    for (uint32_t k = 0; k < 4; ++k) {
+                        uint32_t s = 0;
+                        for (uint32_t i = 0; i < G::CWN; ++i) s += tc[k * FM_NT + tid + i];
+                        bc[k * BPR + tid / G::CWN] = s;
+                    }
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                if (tid < 4) {
+                    uint64_t s = run[tid];
+                    for (uint32_t i = 0; i < BPR; ++i) { const uint64_t v = bc[tid * BPR + i]; bc[tid * BPR + i] = s; s += v; }
+                    run[tid] = s;
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                const uint64_t blk = (w0 + tid) / G::CWN;
+                if (blk < n_blocks) {
+                    uint32_t* p = occ + blk * G::BW;
+                    p[G::CW0 + tid % G::CWN] = TL(wd, tid, 0);
+                    if (tid % G::CWN == 0) {
+                        for (uint32_t k = 0; k < 4; ++k) reinterpret_cast<idx_t*>(p)[k] = (idx_t)bc[k * BPR + tid / G::CWN];
+                        for (uint32_t k = 0; k < G::MWN; ++k) p[G::MW0 + k] = 0;
+                    }
+                }
+            }
+            SYNC();
+        }
+    }
+}
+
+// the stable partition of a level by its digit: row r of digit d goes to  zd + pre[d][tile] + (rows of digit d before r in the tile),
+// zd = the rows of the level with a digit below d.  A thread owns FMW_SROWS consecutive rows; the threads' 4 counts, 16 bits each in one
+// word (a tile has 16,384 rows), are scanned over the workgroup; the tile is laid out in LDS digit by digit and leaves as 4 contiguous
+// runs: aligned words, single bytes only at a run's two ends.  Rows behind n are neither counted nor moved.  cap: the bytes of `out`.
+constexpr uint32_t FMW_SROWS = (uint32_t)(FM_TILE / FM_NT);   // 64
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fmw_scatter_kernel(KCTX const uint8_t* __restrict__ codes, uint8_t* __restrict__ out, uint64_t n, uint64_t cap,
+                                                   uint64_t n_tiles, uint32_t shift, const uint64_t* __restrict__ pre, uint64_t z1, uint64_t z2,
+                                                   uint64_t z3)
+{
+    SHARED_ARRAY(uint64_t, sa, FM_NT);
+    SHARED_ARRAY(uint64_t, sb, FM_NT);
+    SHARED_ARRAY(uint8_t, stage, FM_TILE);
+    TL_DECL(uint32_t, cw, FMW_SROWS / 4);
+    TL_DECL(uint64_t, own, 1);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        PAR(tid) {
+            const uint64_t r0 = tile * FM_TILE + (uint64_t)tid * FMW_SROWS;
+            const uint32_t rows = r0 > n ? 0u : (uint32_t)std::min<uint64_t>(FMW_SROWS, n + 1 - r0);
+            uint64_t c = 0;
+            for (uint32_t k = 0; k < FMW_SROWS / 4; ++k) {
+                uint32_t x = 0;
+                if (4 * k < rows) x = reinterpret_cast<const uint32_t*>(codes + r0)[k];           // (the buffer ends at a multiple of 64)
+                TL(cw, tid, k) = x;
+                for (uint32_t j = 0; j < 4; ++j)
+                    if (4 * k + j < rows) c += 1ull << (16u * (((x >> (8u * j)) >> shift) & 3u));
+            }
+            TL(own, tid, 0) = c;
+            sa[tid] = c;
+        }
+        SYNC();
+        // inclusive scan over the threads, ping-pong between sa and sb: after the 8 steps the result is in sa again
+        for (uint32_t d = 1; d < FM_NT; d *= 4) {
+            PAR(tid) { sb[tid] = sa[tid] + (tid >= d ? sa[tid - d] : 0); }
+            SYNC();
+            PAR(tid) { sa[tid] = sb[tid] + (tid >= 2 * d ? sb[tid - 2 * d] : 0); }
+            SYNC();
+        }
+        PAR(tid) {
+            const uint64_t tot = sa[FM_NT - 1], own = TL(own, tid, 0), ex = sa[tid] - own;
+            uint32_t at[4];
+            uint32_t base = 0;
+            UNROLL
+            for (uint32_t d = 0; d < 4; ++d) { at[d] = base + (uint32_t)((ex >> (16u * d)) & 0xFFFFu); base += (uint32_t)((tot >> (16u * d)) & 0xFFFFu); }
+            const uint32_t rows = (uint32_t)(((own >> 0) & 0xFFFFu) + ((own >> 16) & 0xFFFFu) + ((own >> 32) & 0xFFFFu) + ((own >> 48) & 0xFFFFu));
+            for (uint32_t k = 0; k < FMW_SROWS / 4; ++k) {
+                const uint32_t x = TL(cw, tid, k);
+                for (uint32_t j = 0; j < 4; ++j) {
+                    if (4 * k + j >= rows) break;
+                    const uint32_t b = (x >> (8u * j)) & 0xFFu, d = (b >> shift) & 3u;
+                    // (no indexed register array: the cursor of digit d by selects)
+                    const uint32_t p = d == 0 ? at[0] : d == 1 ? at[1] : d == 2 ? at[2] : at[3];
+                    if (p < FM_TILE) stage[p] = (uint8_t)b;
+                    at[0] += d == 0; at[1] += d == 1; at[2] += d == 2; at[3] += d == 3;
+                }
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            const uint64_t tot = sa[FM_NT - 1];
+            uint32_t s0 = 0;                                                         // the run's first byte in stage
+            for (uint32_t d = 0; d < 4; ++d) {
+                const uint32_t len = (uint32_t)((tot >> (16u * d)) & 0xFFFFu);
+                const uint64_t D = (d == 0 ? 0 : d == 1 ? z1 : d == 2 ? z2 : z3) + pre[(uint64_t)d * n_tiles + tile];
+                const uint32_t head = std::min<uint32_t>(len, (uint32_t)((4u - (D & 3u)) & 3u)), nw = (len - head) / 4, tail0 = head + 4 * nw;
+                if (tid < head && D + tid < cap) out[D + tid] = stage[s0 + tid];
+                for (uint32_t w = tid; w < nw; w += FM_NT) {
+                    const uint32_t k = s0 + head + 4 * w;
+                    const uint32_t v = (uint32_t)stage[k] | ((uint32_t)stage[k + 1] << 8) | ((uint32_t)stage[k + 2] << 16) | ((uint32_t)stage[k + 3] << 24);
+                    if (D + head + 4ull * w + 4 <= cap) *reinterpret_cast<uint32_t*>(out + D + head + 4ull * w) = v;
+                }
+                if (tid < len - tail0 && D + tail0 + tid < cap) out[D + tail0 + tid] = stage[s0 + tail0 + tid];
+                s0 += len;
+            }
+        }
+        SYNC();
+    }
+}
+
+// ---- the queries: the narrow kernels' loops, the LF step above ----
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fmw_count_q_kernel(KCTX FmwView v, const uint8_t* __restrict__ pat, const uint64_t* __restrict__ patoff, uint64_t q,
+                                                   uint64_t* __restrict__ first, uint64_t* __restrict__ count)
+{
+    FMW_LOAD_TABLE(tab, v);
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t j0 = (uint64_t)K_BLOCK_IDX * FM_NT; j0 < q; j0 += stride) {       // block-uniform
+        PAR(tid) {
+            const uint64_t j = j0 + tid;
+            if (j < q) {
+                const uint64_t a = patoff[j], b = patoff[j + 1], m = b > a ? b - a : 0;
+                uint64_t lo = m ? 0 : 1, hi = v.n + 1;                             // every row; without the '$' row for the empty pattern
+                if (m > v.n) hi = lo;
+                for (uint64_t i = m; i > 0 && lo < hi; --i) {
+                    const uint32_t byte = pat[a + i - 1], c = fmw_codes(tab)[byte];
+                    if (!(c < v.sigma && fmw_letters(tab)[c] == byte)) { hi = lo; break; }
+                    fmw_lf2<idx_t>(v, tab, c, lo, hi);
+                }
+                first[j] = lo < hi ? lo - 1 : 0;
+                count[j] = lo < hi ? hi - lo : 0;
+            }
+        }
+    }
+}
+
+// locate: fm_locate_kernel; the code of a row comes from the descent itself (the digit at the position instead of the pattern's)
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fmw_locate_kernel(KCTX FmwView v, const uint64_t* __restrict__ first, const uint64_t* __restrict__ count,
+                                                  const uint64_t* __restrict__ off, uint64_t q, uint64_t o_begin, uint64_t o_end,
+                                                  uint64_t* __restrict__ pos, uint32_t* __restrict__ flags)
+{
+    using G = FmGeom<idx_t>;
+    FMW_LOAD_TABLE(tab, v);
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t o0 = o_begin + (uint64_t)K_BLOCK_IDX * FM_NT; o0 < o_end; o0 += stride) {     // block-uniform
+        PAR(tid) {
+            const uint64_t o = o0 + tid;
+            if (o < o_end) {
+                uint64_t a = 0, b = q;                                              // the last j with off[j] <= o
+                while (b - a > 1) { const uint64_t mid = a + (b - a) / 2; if (off[mid] <= o) a = mid; else b = mid; }
+                const uint64_t t = o - off[a];
+                if (off[a] <= o && t < count[a] && first[a] + t < v.n) {
+                    uint64_t r = first[a] + t + 1, res = ~0ull;
+                    bool done = false;
+                    for (uint32_t steps = 0; steps <= v.s; ++steps) {
+                        if (r == v.primary + 1) { res = steps; done = true; break; }
+                        const uint32_t* p = fmw_block_of<idx_t>(v, 0, r);
+                        uint32_t k = (uint32_t)(r % G::ROWS);
+                        uint32_t mw[G::MWN];
+                        UNROLL
+                        for (uint32_t i = 0; i < G::MWN; ++i) mw[i] = p[G::MW0 + i];
+                        uint32_t below = 0, marked = 0;                             // marks below row k in the block; row k's own
+                        UNROLL
+                        for (uint32_t i = 0; i < G::MWN; ++i) {
+                            const uint32_t rows = k > 32 * i ? (k - 32 * i < 32 ? k - 32 * i : 32) : 0u;
+                            below += (uint32_t)__builtin_popcount(rows < 32 ? mw[i] & ((1u << rows) - 1u) : mw[i]);
+                            if (k / 32 == i) marked = (mw[i] >> (k % 32)) & 1u;
+                        }
+                        if (marked) {
+                            const uint64_t blk = r / G::ROWS;
+                            const uint64_t si = (uint64_t)static_cast<const idx_t*>(v.mrank)[blk < v.n_blocks ? blk : v.n_blocks - 1] + below;
+                            if (si < v.n_samples) { res = (uint64_t)static_cast<const idx_t*>(v.samples)[si] + steps; done = true; }
+                            break;
+                        }
+                        uint32_t c = 0;
+                        uint64_t x = r;
+                        for (uint32_t l = 0; l < v.Lv; ++l) {
+                            if (l) { p = fmw_block_of<idx_t>(v, l, x); k = (uint32_t)(x % G::ROWS); }
+                            const uint32_t d = (p[G::CW0 + k / FM_WROWS] >> (2u * (k % FM_WROWS))) & 3u;
+                            c = 4 * c + d;
+                            x = fmw_Z(tab)[4 * l + d] + fm_block_occ<idx_t>(p, d, k, false);
+                            if (x > v.n + 1) x = v.n + 1;
+                        }
+                        x = fmw_row(v, tab, c, x, r > v.primary + 1);
+                        r = x <= v.n ? (x ? x : 1) : v.n;                            // (a row of the index: 1 .. n)
+                    }
+                    if (!done) { ATOMIC_OR_U32(flags, 4u); res = (uint64_t)(idx_t)~(idx_t)0; }
+                    pos[o] = res;
+                }
+            }
+        }
+    }
+}
+
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fmw_match_kernel(KCTX FmwView v, const uint8_t* __restrict__ pat, const uint64_t* __restrict__ patoff, uint64_t q,
+                                                 uint64_t o_begin, uint64_t o_end, uint32_t max_len, uint32_t* __restrict__ len,
+                                                 uint64_t* __restrict__ first, uint64_t* __restrict__ count)
+{
+    FMW_LOAD_TABLE(tab, v);
+    const uint64_t stride = (uint64_t)K_GRID_DIM * FM_NT;
+    for (uint64_t o0 = o_begin + (uint64_t)K_BLOCK_IDX * FM_NT; o0 < o_end; o0 += stride) {     // block-uniform
+        PAR(tid) {
+            const uint64_t o = o0 + tid;
+            if (o < o_end) {
+                uint64_t a = 0, b = q;                                              // the last j with patoff[j] <= o
+                while (b - a > 1) { const uint64_t mid = a + (b - a) / 2; if (patoff[mid] <= o) a = mid; else b = mid; }
+                const uint64_t p0 = patoff[a];
+                uint64_t steps = p0 <= o ? o - p0 + 1 : 0;                          // e: the bytes at and left of o in its pattern
+                if (max_len && steps > max_len) steps = max_len;
+                uint64_t lo = 0, hi = v.n + 1;
+                uint32_t l = 0;
+                for (uint64_t i = 0; i < steps; ++i) {
+                    const uint32_t byte = pat[o - i], c = fmw_codes(tab)[byte];
+                    if (!(c < v.sigma && fmw_letters(tab)[c] == byte)) break;
+                    uint64_t l2 = lo, h2 = hi;
+                    fmw_lf2<idx_t>(v, tab, c, l2, h2);
+                    if (l2 >= h2) break;
+                    lo = l2;
+                    hi = h2;
+                    ++l;
+                }
+                const bool hit = l != 0 && lo != 0;                                 // (lo >= C[0] = 1 after a step)
+                len[o - o_begin] = hit ? l : 0u;
+                if (first) first[o - o_begin] = hit ? lo - 1 : 0;
+                if (count) count[o - o_begin] = hit ? hi - lo : 0;
+            }
+        }
+    }
+}
+
 // ---- SA samples from the BWT alone (capi_impl.h fm_from_bwt_*; include/caps_sa_hip.h "FM-index from the BWT alone") -------------
 // LF^k(0), k = 1 .. n, is the row of text position n - k (k = n: the '$' row, position 0; k = n + 1: row 0 again), so a row's offset
 // on the cycle of row 0 is its SA value: neither T nor the SA is read.  LF comes from the finished Occ section, one block per step

@@ -34,7 +34,8 @@ extern "C" {
 #define CAPS_SA_ENOMEM (-4)       /* device or host allocation failed */
 #define CAPS_SA_ENODEVICE (-5)    /* no usable GPU */
 #define CAPS_SA_EALPHABET (-6)    /* the workspace was sized for a 2-bit text (caps_sa_hip_workspace_bytes_ex), the text has more than 4 bytes;
-                                     caps_sa_hip_fm_build_*: the BWT has more than 4 distinct bytes */
+                                     caps_sa_hip_fm_build_*: the BWT has more than 4 distinct bytes
+                                     (caps_sa_hip_fm_build_wide_* takes 1 .. 256) */
 
 /* Per-build record; replaces the per-phase stderr lines of construct()
  * (src/Suffix_Array.cpp:469-493).  Times are HIP-event milliseconds on the build's stream. */
@@ -309,7 +310,8 @@ int caps_sa_hip_inverse_bwt_u64(const uint8_t* BWT, uint64_t n, uint64_t primary
  *
  * Alphabet: at most 4 distinct byte values in the BWT (any bytes, >= 0x80 included), coded 0 .. sigma - 1 in signed-char order --
  * the condition under which the build packs the text to 2 bits. More than 4: CAPS_SA_EALPHABET, decided on the device, nothing
- * written. (A wider alphabet needs another rank structure -- a wavelet tree over the codes -- and is out of scope.)
+ * written. (A wider alphabet, 1 .. 256 distinct bytes: the wide format below, "FM-index: the wide format", built by
+ * caps_sa_hip_fm_build_wide_* and answered by the same count, locate, match and mems calls.)
  *
  * The index is ONE relocatable blob without pointers: copy it device <-> host or write it to a file as it is.
  *   header    256 bytes: magic, format version, n, primary, index width, sigma and the byte values, C[0 .. 4], sa_sample, number of
@@ -539,6 +541,86 @@ int caps_sa_hip_fm_mems_device(const void* dIndex, uint64_t index_bytes, const v
                                uint64_t workspace_bytes, void* hip_stream);
 int caps_sa_hip_fm_mems(const void* index, uint64_t index_bytes, const uint8_t* patterns, const uint64_t* pat_off, uint64_t q,
                         uint32_t min_len, uint64_t* mem_off, void* mems, uint64_t mem_capacity, int device);
+
+/* ---- FM-index: the wide format -- count, locate and MEMs over any bytes -----------------
+ *
+ * A second blob format for a BWT of 1 .. 256 distinct bytes (a genome with N, IUPAC DNA, protein, any text), built from
+ * (BWT, primary[, SA]) by caps_sa_hip_fm_build_wide_* and answered by caps_sa_hip_fm_count*, _locate*, _match* and _mems* above, which
+ * tell the two formats apart by the magic; their contracts are unchanged. caps_sa_hip_fm_add_text_samples*, _extract* and
+ * caps_sa_hip_fm_build_from_bwt* are not built for it: the first two answer a wide blob with CAPS_SA_EUNSUPPORTED and write nothing.
+ *
+ * The rank structure is a 4-ary wavelet matrix made of version 1's Occ blocks. Letters are coded 0 .. sigma - 1 in signed-char
+ * order; a code is written with Lv = max(1, ceil(log4 sigma)) base-4 digits, digit 0 the most significant (Lv = 2 for ACGTN and
+ * IUPAC, 3 for protein, 4 for all bytes). Rows are version 1's: rows 0 .. n, row 0 carries BWT[primary], row r in 1 .. n BWT[r - 1],
+ * the '$' row primary + 1 is STORED AS CODE 0. Level 0 is the code sequence in row order; level l + 1 is level l stably partitioned
+ * by its level-l digit (all rows with digit 0 first, then 1, 2, 3). With
+ *   Occ_l(d, p)  the rows below position p of level l whose digit is d
+ *   Z[l][d]      the rows 0 .. n of level l with a digit below d
+ *   zone[c]      the position that code c reaches from p = 0
+ * the LF step is
+ *   p = r;  for l in 0 .. Lv - 1:  d = digit_l(c);  p = Z[l][d] + Occ_l(d, p)
+ *   LF(c, r) = C[c] + p - zone[c] - [c == 0 and r > primary + 1]
+ * and the code of a row (locate) comes from the same descent with the digit AT p in the place of digit_l(c): one aligned block
+ * per level and step. sigma <= 4 gives Lv = 1, and the level-0 section is then byte for byte the Occ section of version 1.
+ *
+ * The blob, byte by byte (wide format version 1; little-endian; W, ROWS as in version 1). The header is 32 64-bit words:
+ *   word  0        magic: the 8 bytes "CAPSFMW1" (0x31574D4653504143)
+ *   word  1        format version = 1
+ *   words 2 .. 4   n, primary (0 when n = 0), W                                          -- version 1's words
+ *   word  5        sigma: the number of distinct bytes of the BWT, 0 .. 256 (0 when n = 0)
+ *   word  6        Lv
+ *   word  7        offset of the table section = 256
+ *   word  8        bytes of one level section = n_blocks * ROWS / 2
+ *   words 9 .. 11  zero
+ *   words 12 .. 14 sa_sample (0: no samples), number of samples, n_blocks              -- version 1's words and rules
+ *   word  15       offset of level 0 = 256 + 4800; level l stands at word 15 + l * word 8
+ *   word  16       offset of the mark ranks = word 15 + Lv * word 8
+ *   word  17       offset of the samples = word 16 + n_blocks * W rounded up to a multiple of 64 (= word 16 when sa_sample = 0)
+ *   word  18       total = word 17 + (number of samples) * W rounded up to a multiple of 64 (= word 17 when sa_sample = 0)
+ *   words 19 .. 31 zero
+ * Table section, 4800 bytes at offset 256 (offsets within the section):
+ *   0     letters u8[256]: letters[c] = the byte of code c for c < sigma, else 0
+ *   256   code_of u8[256]: code_of[b] = the number of letters below byte b in signed-char order. b is a letter iff
+ *         code_of[b] < sigma and letters[code_of[b]] == b: there is no sentinel value
+ *   512   C u64[257]: C[0] = 1, C[c + 1] = C[c] + the number of bytes of the BWT with code c, so C[c] = n + 1 for c >= sigma
+ *   2568  zone u64[256] (0 for c >= sigma)
+ *   4616  Z u64[4][4]: Z[l][d] at 4616 + 8 (4 l + d); rows l >= Lv are 0
+ *   4744  56 zero bytes
+ *   (n = 0: every C[c] = 1, everything else in the section 0.)
+ * Level sections: each is an Occ section in version 1's block layout -- per block 4 counts of W bytes (the rows of the level
+ * before the block whose digit is 0, 1, 2, 3), ROWS / 16 words of 2-bit digits, ROWS / 32 mark words. Only level 0 carries marks
+ * (version 1's: row r is marked iff SA[r - 1] is a multiple of sa_sample); the mark words of the other levels are 0. Positions
+ * behind n store digit 0 and are in no count. Mark ranks and samples: as in version 1, present only with an SA. All padding is 0:
+ * equal inputs give equal blobs. Size: Lv * 0.5 n + 0.16 n bytes at sa_sample = 32, W = 4.
+ *
+ * Build: dSA NULL builds an index that counts (sa_sample ignored). The alphabet is found on the device, so the blob's size is known
+ * only afterwards: it is header word 18. index_capacity must hold it -- caps_sa_hip_fm_wide_index_bytes(n, sigma, ..), sigma = 0
+ * for "unknown" (sized for 256 letters). Workspace: caps_sa_hip_fm_wide_workspace_bytes(n, W) = two code buffers of n + 1 bytes and
+ * 40 bytes per 16,384 rows (+ 2.1 MB): no array of n index entries; NULL is allocated and freed by the call.
+ * Errors, CAPS_SA_EINVAL and checked before any allocation: a null pointer (dBWT may be null for n = 0), primary >= n for n >= 1,
+ * n > UINT32_MAX with _u32, sa_sample no power of two in 1 .. 1024 with an SA, a workspace that is too small, an index_capacity
+ * below the smallest index of n symbols; a capacity below the blob of the alphabet found is CAPS_SA_EINVAL too, with nothing
+ * written. An SA whose multiples of sa_sample are not (n - 1) / sa_sample + 1: CAPS_SA_EINVAL. n = 0
+ * builds, and counts 0.
+ *
+ * Queries: header AND table section are read back and checked on the host before a kernel reads the body -- the letters ascending,
+ * code_of, C monotone from 1 to n + 1, zone and Z recomputed from C, every offset recomputed, total <= index_bytes: anything wrong
+ * is CAPS_SA_EINVAL. The kernels keep every position inside 0 .. n + 1 and every block inside its level at every level, and every
+ * loop is bounded as in version 1: for any body they read inside the blob and terminate.
+ */
+int caps_sa_hip_fm_wide_index_bytes(uint64_t n, uint32_t sigma, uint32_t sa_sample, int idx_bytes, uint64_t* bytes);
+int caps_sa_hip_fm_wide_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes);
+/* dBWT (n bytes), dSA (NULL or the whole suffix array), dIndex (index_capacity bytes, 64-byte aligned, written) and workspace (or
+ * NULL) are device pointers on the current device; the work runs on hip_stream and has completed on return. */
+int caps_sa_hip_fm_build_wide_device_u32(const void* dBWT, uint64_t n, uint64_t primary, const void* dSA, uint32_t sa_sample,
+                                         void* dIndex, uint64_t index_capacity, void* workspace, uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_fm_build_wide_device_u64(const void* dBWT, uint64_t n, uint64_t primary, const void* dSA, uint32_t sa_sample,
+                                         void* dIndex, uint64_t index_capacity, void* workspace, uint64_t workspace_bytes, void* hip_stream);
+/* Host buffers, on the device block of the host-buffer builds as caps_sa_hip_fm_build_*: header word 18 bytes of `index` are written. */
+int caps_sa_hip_fm_build_wide_u32(const uint8_t* BWT, uint64_t n, uint64_t primary, const uint32_t* SA, uint32_t sa_sample,
+                                  void* index, uint64_t index_capacity, int device);
+int caps_sa_hip_fm_build_wide_u64(const uint8_t* BWT, uint64_t n, uint64_t primary, const uint64_t* SA, uint32_t sa_sample,
+                                  void* index, uint64_t index_capacity, int device);
 
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
