@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from ._binding import CapsLib, CapsSaError, Stats, Shard, ShardInfo, EXPORTS, MEM_DTYPE  # noqa: F401
+from ._binding import CapsLib, CapsSaError, Stats, Shard, ShardInfo, EXPORTS, MEM_DTYPE, KMER_DTYPE  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CAPS_SA_LIB selects a tuning variant built by `make variant` (benchmarking only).
@@ -49,6 +49,25 @@ def inverse_bwt(BWT, primary: int, device: int = 0) -> np.ndarray:
     ``SuffixArray(T, bwt=True)``'s ``BWT()`` and ``primary()`` -> np.uint8 array.  The index width follows n.  An input that is
     not the BWT of any text raises CapsSaError (code -1)."""
     return lib().inverse_bwt(BWT, primary, device=device)
+
+
+def kmers(SA, LCP, k: int, min_count: int = 1, max_count: int = 0, device: int = 0, _lib: CapsLib | None = None) -> np.ndarray:
+    """The k-mer table of the text whose full-context SA and LCP these are (include/caps_sa_hip.h "k-mers from SA and LCP"), e.g.
+    arrays read from a dump: a structured array (KMER_DTYPE: first, count, pos) of the distinct k-mers with min_count <= count
+    (<= max_count unless that is 0), in the library's byte order.  K-mer j is T[pos : pos + k] and occurs at
+    SA[first : first + count].  The index width is SA's dtype."""
+    return (_lib or lib()).kmers(SA, LCP, k, min_count, max_count, device=device)
+
+
+def kmer_spectrum(SA, LCP, k: int, bins: int = 1024, device: int = 0, _lib: CapsLib | None = None) -> np.ndarray:
+    """np.uint64[bins + 1]: hist[c] = the distinct k-mers that occur c times, hist[bins] = bins times or more, hist[0] = 0."""
+    return (_lib or lib()).kmer_spectrum(SA, LCP, k, bins, device=device)
+
+
+def kmer_census(SA, LCP, max_k: int, device: int = 0, _lib: CapsLib | None = None):
+    """(distinct, unique), np.uint64[max_k + 1] each: for every k in 1 .. max_k the number of distinct k-mers and of those that
+    occur once, from one pass."""
+    return (_lib or lib()).kmer_census(SA, LCP, max_k, device=device)
 
 
 class SuffixArray:
@@ -119,6 +138,27 @@ class SuffixArray:
         if self._primary is None:
             raise RuntimeError("construct() has not been called")
         return self._primary
+
+    def _kmer_arrays(self):
+        if self._ctx:
+            raise ValueError("k-mers need a full-context suffix array: this one was built with max_context set")
+        return self.SA(), self.LCP()
+
+    def kmers(self, k: int, min_count: int = 1, max_count: int = 0) -> np.ndarray:
+        """The distinct k-mers with min_count <= count (<= max_count unless that is 0) as a structured array (KMER_DTYPE: first, count,
+        pos) in the library's byte order: k-mer j is T()[pos : pos + k] and occurs at SA()[first : first + count]."""
+        SA, LCP = self._kmer_arrays()
+        return lib().kmers(SA, LCP, k, min_count, max_count, self._bits, self._device)
+
+    def kmer_spectrum(self, k: int, bins: int = 1024) -> np.ndarray:
+        """np.uint64[bins + 1]: hist[c] = the distinct k-mers that occur c times, hist[bins] = bins times or more."""
+        SA, LCP = self._kmer_arrays()
+        return lib().kmer_spectrum(SA, LCP, k, bins, self._bits, self._device)
+
+    def kmer_census(self, max_k: int):
+        """(distinct, unique), np.uint64[max_k + 1] each: the number of distinct k-mers and of those that occur once, k = 1 .. max_k."""
+        SA, LCP = self._kmer_arrays()
+        return lib().kmer_census(SA, LCP, max_k, self._bits, self._device)
 
     def dump(self, path: str) -> None:
         """Suffix_Array::dump format (src/Suffix_Array.cpp:497-509): u64 n, SA, LCP."""

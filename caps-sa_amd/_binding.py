@@ -125,17 +125,21 @@ EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_b
            "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_from_bwt_workspace_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device",
            "fm_index_bytes_ex", "fm_add_text_samples", "fm_add_text_samples_device", "fm_extract_workspace_bytes", "fm_extract", "fm_extract_device",
            "fm_match", "fm_match_device", "fm_mems_workspace_bytes", "fm_mems", "fm_mems_device", "fm_wide_index_bytes",
-           "fm_wide_workspace_bytes"] + SHARD_EXPORTS + [
+           "fm_wide_workspace_bytes", "kmer_workspace_bytes"] + SHARD_EXPORTS + [
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
     for name in ("build", "build_multi", "build_device", "verify_device", "verify_slice_device", "sort_suffixes", "sort_segments", "merge",
                  "upper_bound", "lcp", "build_bwt", "bwt_device", "inverse_bwt", "inverse_bwt_device", "fm_build", "fm_build_device",
-                 "fm_build_from_bwt", "fm_build_from_bwt_device", "fm_build_wide", "fm_build_wide_device")
+                 "fm_build_from_bwt", "fm_build_from_bwt_device", "fm_build_wide", "fm_build_wide_device",
+                 "kmers", "kmers_device", "kmer_spectrum", "kmer_spectrum_device", "kmer_census", "kmer_census_device")
 ]
 
 
 # a MEM record of fm_mems (include/caps_sa_hip.h "FM-index: matching statistics"): 32 bytes, little-endian
 MEM_DTYPE = np.dtype([("pattern", "<u8"), ("start", "<u4"), ("length", "<u4"), ("first", "<u8"), ("count", "<u8")])
+
+# a record of kmers (include/caps_sa_hip.h "k-mers from SA and LCP"): 24 bytes, little-endian
+KMER_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("pos", "<u8")])
 
 
 class CapsSaError(RuntimeError):
@@ -218,7 +222,21 @@ class CapsLib:
         f("fm_wide_index_bytes").argtypes = [_u64, ctypes.c_uint32, ctypes.c_uint32, _ci, ctypes.POINTER(_u64)]
         f("fm_wide_workspace_bytes").restype = _ci
         f("fm_wide_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
+        f("kmer_workspace_bytes").restype = _ci
+        f("kmer_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
         for sfx in ("u32", "u64"):
+            f(f"kmers_{sfx}").restype = _ci
+            f(f"kmers_{sfx}").argtypes = [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _u64, ctypes.POINTER(_u64), _ci]
+            f(f"kmers_device_{sfx}").restype = _ci
+            f(f"kmers_device_{sfx}").argtypes = [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64, _vp]
+            f(f"kmer_spectrum_{sfx}").restype = _ci
+            f(f"kmer_spectrum_{sfx}").argtypes = [_vp, _vp, _u64, _u64, ctypes.c_uint32, _vp, _ci]
+            f(f"kmer_spectrum_device_{sfx}").restype = _ci
+            f(f"kmer_spectrum_device_{sfx}").argtypes = [_vp, _vp, _u64, _u64, ctypes.c_uint32, _vp, _vp, _u64, _vp]
+            f(f"kmer_census_{sfx}").restype = _ci
+            f(f"kmer_census_{sfx}").argtypes = [_vp, _vp, _u64, ctypes.c_uint32, _vp, _vp, _ci]
+            f(f"kmer_census_device_{sfx}").restype = _ci
+            f(f"kmer_census_device_{sfx}").argtypes = [_vp, _vp, _u64, ctypes.c_uint32, _vp, _vp, _vp, _u64, _vp]
             f(f"fm_build_wide_{sfx}").restype = _ci
             f(f"fm_build_wide_{sfx}").argtypes = [_vp, _u64, _u64, _vp, ctypes.c_uint32, _vp, _u64, _ci]
             f(f"fm_build_wide_device_{sfx}").restype = _ci
@@ -696,6 +714,86 @@ class CapsLib:
         ws_bytes (fm_mems_workspace_bytes), or 0: allocated and freed by the call."""
         self._check(self._f("fm_mems_device")(dIndex_ptr or None, index_bytes, dPat_ptr or None, dPatOff_ptr or None, q, min_len,
                                               dMemOff_ptr or None, dMems_ptr or None, mem_capacity, dWS_ptr or None, ws_bytes, stream or None))
+
+    # ------------------------------------------------------------------ k-mers (include/caps_sa_hip.h "k-mers from SA and LCP")
+    @staticmethod
+    def _sa_lcp(SA, LCP, idx_bits):
+        """(SA, LCP, n, suffix): both contiguous in one index dtype -- SA's own unless idx_bits is given."""
+        SA = np.asarray(SA)
+        if idx_bits is None:
+            idx_bits = 64 if SA.dtype.itemsize == 8 else 32
+        sfx, dt = _sfx(idx_bits)
+        SA = np.ascontiguousarray(SA, dtype=dt)
+        LCP = np.ascontiguousarray(LCP, dtype=dt)
+        if SA.ndim != 1 or SA.shape != LCP.shape:
+            raise ValueError("SA and LCP: two 1-d arrays of one size")
+        return SA, LCP, int(SA.size), sfx
+
+    def kmer_workspace_bytes(self, n: int, idx_bits: int = 32) -> int:
+        out = _u64(0)
+        self._check(self._f("kmer_workspace_bytes")(n, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    def kmers(self, SA, LCP, k: int, min_count: int = 1, max_count: int = 0, idx_bits: int | None = None, device: int = 0) -> np.ndarray:
+        """The distinct k-mers with min_count <= count (<= max_count unless that is 0) as a structured array (KMER_DTYPE: first,
+        count, pos) in the library's byte order: k-mer j is T[pos : pos + k] and occurs at SA[first : first + count].  The counting
+        call, then the writing call."""
+        SA, LCP, n, sfx = self._sa_lcp(SA, LCP, idx_bits)
+        found = _u64(0)
+        args = (SA.ctypes.data if n else None, LCP.ctypes.data if n else None, n, k, min_count, max_count)
+        self._check(self._f(f"kmers_{sfx}")(*args, None, 0, ctypes.byref(found), device))
+        rec = np.zeros(found.value, dtype=KMER_DTYPE)
+        if rec.size:
+            self._check(self._f(f"kmers_{sfx}")(*args, rec.ctypes.data, rec.size, ctypes.byref(found), device))
+        return rec
+
+    def kmer_spectrum(self, SA, LCP, k: int, bins: int = 1024, idx_bits: int | None = None, device: int = 0) -> np.ndarray:
+        """np.uint64[bins + 1]: hist[c] = the distinct k-mers that occur c times, hist[bins] = bins times or more, hist[0] = 0."""
+        SA, LCP, n, sfx = self._sa_lcp(SA, LCP, idx_bits)
+        hist = np.zeros(max(int(bins), 0) + 1, dtype=np.uint64)
+        self._check(self._f(f"kmer_spectrum_{sfx}")(SA.ctypes.data if n else None, LCP.ctypes.data if n else None, n, k, bins,
+                                                    hist.ctypes.data, device))
+        return hist
+
+    def kmer_census(self, SA, LCP, max_k: int, idx_bits: int | None = None, device: int = 0):
+        """(distinct, unique), np.uint64[max_k + 1] each: the number of distinct k-mers and of those that occur once, k = 1 .. max_k."""
+        SA, LCP, n, sfx = self._sa_lcp(SA, LCP, idx_bits)
+        distinct = np.zeros(max(int(max_k), 0) + 1, dtype=np.uint64)
+        unique = np.zeros_like(distinct)
+        self._check(self._f(f"kmer_census_{sfx}")(SA.ctypes.data if n else None, LCP.ctypes.data if n else None, n, max_k,
+                                                  distinct.ctypes.data, unique.ctypes.data, device))
+        return distinct, unique
+
+    def kmers_device(self, dSA_ptr: int, dLCP_ptr: int, n: int, k: int, min_count: int = 1, max_count: int = 0, dRecords_ptr: int = 0,
+                     capacity: int = 0, dWS_ptr: int = 0, ws_bytes: int = 0, idx_bits: int = 32, stream: int = 0) -> int:
+        """Device arrays -> the number of records; dRecords_ptr 0: the counting call, else `capacity` 24-byte records are written
+        there.  More records than capacity: CapsSaError (code -1) whose n_records attribute holds their number."""
+        sfx, _ = _sfx(idx_bits)
+        found = _u64(0)
+        rc = self._f(f"kmers_device_{sfx}")(dSA_ptr or None, dLCP_ptr or None, n, k, min_count, max_count, dRecords_ptr or None, capacity,
+                                            ctypes.byref(found), dWS_ptr or None, ws_bytes, stream or None)
+        if rc != 0:
+            err = CapsSaError(rc, self._f("last_error")().decode(errors="replace"))
+            err.n_records = found.value
+            raise err
+        return found.value
+
+    def kmer_spectrum_device(self, dSA_ptr: int, dLCP_ptr: int, n: int, k: int, bins: int = 1024, dWS_ptr: int = 0, ws_bytes: int = 0,
+                             idx_bits: int = 32, stream: int = 0) -> np.ndarray:
+        sfx, _ = _sfx(idx_bits)
+        hist = np.zeros(max(int(bins), 0) + 1, dtype=np.uint64)
+        self._check(self._f(f"kmer_spectrum_device_{sfx}")(dSA_ptr or None, dLCP_ptr or None, n, k, bins, hist.ctypes.data, dWS_ptr or None,
+                                                           ws_bytes, stream or None))
+        return hist
+
+    def kmer_census_device(self, dSA_ptr: int, dLCP_ptr: int, n: int, max_k: int, dWS_ptr: int = 0, ws_bytes: int = 0, idx_bits: int = 32,
+                           stream: int = 0):
+        sfx, _ = _sfx(idx_bits)
+        distinct = np.zeros(max(int(max_k), 0) + 1, dtype=np.uint64)
+        unique = np.zeros_like(distinct)
+        self._check(self._f(f"kmer_census_device_{sfx}")(dSA_ptr or None, dLCP_ptr or None, n, max_k, distinct.ctypes.data,
+                                                         unique.ctypes.data, dWS_ptr or None, ws_bytes, stream or None))
+        return distinct, unique
 
     # ------------------------------------------------------------------ kernel-level entry points
     def sort_suffixes(self, T, idx, idx_bits: int = 32, device: int = 0):

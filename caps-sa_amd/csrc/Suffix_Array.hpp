@@ -18,6 +18,8 @@
 //  * an optional list of devices: construct() then shards the build over them (caps_sa_hip_build_multi_*);
 //  * construct_bwt() (not in the reference): construct() plus the Burrows-Wheeler transform (include/caps_sa_hip.h), one device;
 //    its n-byte buffer is allocated by the first construct_bwt(), so construct() callers pay nothing for it.
+//  * kmers() / kmer_spectrum() / kmer_census() (not in the reference): the k-mer table, spectrum and census of the text from SA() and LCP()
+//    after a full-context construct() (include/caps_sa_hip.h "k-mers from SA and LCP").
 //  * the free function inverse_bwt() (not in the reference): the text back from (BWT, primary).
 //  * the class FM_Index (not in the reference either): count, locate, matching statistics, MEMs and extract over (BWT, primary) and a sample of the SA.
 #ifndef CAPS_SA_AMD_SUFFIX_ARRAY_HPP
@@ -129,6 +131,43 @@ public:
     const uint8_t* BWT() const { return BWT_; }                 // null before the first construct_bwt()
     uint64_t primary() const { return primary_; }
 
+    // ---- k-mers from SA and LCP (include/caps_sa_hip.h; not in the reference).  After a full-context construct() / construct_bwt():
+    // with max_context set the arrays are no suffix array and these throw std::invalid_argument.  On devices()[0].
+    struct Kmer { uint64_t first, count, pos; };               // the ABI's 24-byte record: the k-mer is T()[pos .. pos + k), at SA()[first .. first + count)
+    // the distinct k-mers with min_count <= count (<= max_count unless that is 0), in the library's byte order
+    std::vector<Kmer> kmers(uint64_t k, uint64_t min_count = 1, uint64_t max_count = 0) const
+    {
+        kmer_arrays_ok("kmers");
+        static_assert(sizeof(Kmer) == 24, "the ABI's record");
+        uint64_t found = 0;
+        kmers_call(k, min_count, max_count, nullptr, 0, &found);                 // the counting call
+        std::vector<Kmer> out(static_cast<std::size_t>(found));
+        if (found) kmers_call(k, min_count, max_count, out.data(), found, &found);
+        return out;
+    }
+    // hist[c] = the distinct k-mers that occur c times (1 <= c < bins), hist[bins] = bins times or more, hist[0] = 0
+    std::vector<uint64_t> kmer_spectrum(uint64_t k, uint32_t bins = 1024) const
+    {
+        kmer_arrays_ok("kmer_spectrum");
+        std::vector<uint64_t> hist(static_cast<std::size_t>(bins) + 1, 0);
+        const int rc = std::is_same<idx_t, uint32_t>::value
+            ? caps_sa_hip_kmer_spectrum_u32(reinterpret_cast<const uint32_t*>(SA_), reinterpret_cast<const uint32_t*>(LCP_), n_, k, bins, hist.data(), devices_[0])
+            : caps_sa_hip_kmer_spectrum_u64(reinterpret_cast<const uint64_t*>(SA_), reinterpret_cast<const uint64_t*>(LCP_), n_, k, bins, hist.data(), devices_[0]);
+        if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_kmer_spectrum: ") + caps_sa_hip_last_error());
+        return hist;
+    }
+    // distinct[k] / unique[k], k = 1 .. max_k: the number of distinct k-mers and of those that occur once (index 0 is 0)
+    void kmer_census(uint32_t max_k, std::vector<uint64_t>& distinct, std::vector<uint64_t>& unique) const
+    {
+        kmer_arrays_ok("kmer_census");
+        distinct.assign(static_cast<std::size_t>(max_k) + 1, 0);
+        unique.assign(static_cast<std::size_t>(max_k) + 1, 0);
+        const int rc = std::is_same<idx_t, uint32_t>::value
+            ? caps_sa_hip_kmer_census_u32(reinterpret_cast<const uint32_t*>(SA_), reinterpret_cast<const uint32_t*>(LCP_), n_, max_k, distinct.data(), unique.data(), devices_[0])
+            : caps_sa_hip_kmer_census_u64(reinterpret_cast<const uint64_t*>(SA_), reinterpret_cast<const uint64_t*>(LCP_), n_, max_k, distinct.data(), unique.data(), devices_[0]);
+        if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_kmer_census: ") + caps_sa_hip_last_error());
+    }
+
     // Reference: src/Suffix_Array.cpp:497-509 -- u64 n, then SA, then LCP, native endianness.
     void dump(std::ofstream& output)
     {
@@ -142,6 +181,19 @@ public:
     const caps_sa_stats& stats() const { return stats_; }
 
 private:
+    void kmer_arrays_ok(const char* what) const
+    {
+        if (max_context_ != 0 && max_context_ < n_)
+            throw std::invalid_argument(std::string("Suffix_Array::") + what + ": k-mers need a full-context suffix array (max_context is set)");
+    }
+    void kmers_call(uint64_t k, uint64_t min_count, uint64_t max_count, void* records, uint64_t capacity, uint64_t* found) const
+    {
+        const int rc = std::is_same<idx_t, uint32_t>::value
+            ? caps_sa_hip_kmers_u32(reinterpret_cast<const uint32_t*>(SA_), reinterpret_cast<const uint32_t*>(LCP_), n_, k, min_count, max_count, records, capacity, found, devices_[0])
+            : caps_sa_hip_kmers_u64(reinterpret_cast<const uint64_t*>(SA_), reinterpret_cast<const uint64_t*>(LCP_), n_, k, min_count, max_count, records, capacity, found, devices_[0]);
+        if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_kmers: ") + caps_sa_hip_last_error());
+    }
+
     const char* const T_;
     const idx_t n_;
     idx_t* SA_;

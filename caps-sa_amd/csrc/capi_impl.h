@@ -2676,6 +2676,284 @@ inline int fm_mems_host(const void* index, uint64_t index_bytes, const uint8_t* 
     });
 }
 
+// ---- k-mers from SA and LCP (include/caps_sa_hip.h "k-mers from SA and LCP"; kernels.h kmer_*) --------------------------------------
+// Workspace: next[n_tiles + 1] | cnt[n_tiles] | totals[2 * KMER_KEYS] | per-workgroup histogram columns[2 * KMER_KEYS][grid], 64-bit words.
+struct KmerPlan {
+    uint64_t n_tiles = 0;
+    uint32_t grid = 1;                         // workgroups of the histogram kernels (= the length of a column)
+    size_t off_next = 0, off_cnt = 0, off_tot = 0, off_hist = 0, bytes = 0;
+};
+inline KmerPlan kmer_plan(uint64_t n)
+{
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    KmerPlan p;
+    p.n_tiles = (n + KMER_TILE - 1) / KMER_TILE;
+    // a workgroup's LDS bins are 32 bits wide: at most 2^16 tiles (2^30 ranks) each
+    p.grid = capped_grid(std::max<uint64_t>(std::min<uint64_t>(p.n_tiles, 1024), (p.n_tiles + 65535) / 65536), FM_NT);
+    p.off_next = 0;
+    p.off_cnt = p.off_next + up((p.n_tiles + 1) * 8);
+    p.off_tot = p.off_cnt + up((p.n_tiles + 1) * 8);
+    p.off_hist = p.off_tot + up(2 * KMER_KEYS * 8);
+    p.bytes = p.off_hist + up((size_t)2 * KMER_KEYS * p.grid * 8);
+    return p;
+}
+inline int kmer_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
+{
+    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
+    *bytes = kmer_plan(n).bytes + 256;
+    return CAPS_SA_OK;
+}
+
+// the workspace of one call: the caller's (aligned up, checked by kmer_check_ws before) or one of the call's own
+struct KmerWs {
+    char* base = nullptr;
+    KmerPlan p;
+    uint64_t* next() const { return reinterpret_cast<uint64_t*>(base + p.off_next); }
+    uint64_t* cnt() const { return reinterpret_cast<uint64_t*>(base + p.off_cnt); }
+    uint64_t* tot() const { return reinterpret_cast<uint64_t*>(base + p.off_tot); }
+    uint64_t* hist() const { return reinterpret_cast<uint64_t*>(base + p.off_hist); }
+};
+inline char* kmer_align_ws(void* workspace, uint64_t workspace_bytes, uint64_t& usable)
+{
+    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+    const uint64_t slack = (uint64_t)(ws - static_cast<char*>(workspace));
+    usable = workspace_bytes > slack ? workspace_bytes - slack : 0;
+    return ws;
+}
+template <typename idx_t> int kmer_check_arrays(const void* SA, const void* LCP, uint64_t n)
+{
+    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
+    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
+    if (n && (!SA || !LCP)) return fail(CAPS_SA_EINVAL, "null pointer");
+    return CAPS_SA_OK;
+}
+inline int kmer_check_ws(void* workspace, uint64_t workspace_bytes, uint64_t n)
+{
+    if (!workspace) return CAPS_SA_OK;
+    uint64_t usable = 0;
+    kmer_align_ws(workspace, workspace_bytes, usable);
+    if (usable < kmer_plan(n).bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_kmer_workspace_bytes)");
+    return CAPS_SA_OK;
+}
+inline KmerWs kmer_ws(Backend& be, DevAllocs& da, void* workspace, uint64_t workspace_bytes, uint64_t n)
+{
+    KmerWs w;
+    w.p = kmer_plan(n);
+    uint64_t usable = 0;
+    if (workspace) w.base = kmer_align_ws(workspace, workspace_bytes, usable);
+    else w.base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(da.get<char>(w.p.bytes + 256)) + 255) & ~uintptr_t(255));
+    return w;
+}
+inline int kmer_check_counts(uint64_t k, uint64_t min_count, uint64_t max_count)
+{
+    if (k == 0) return fail(CAPS_SA_EINVAL, "k must be at least 1");
+    if (max_count && min_count > max_count) return fail(CAPS_SA_EINVAL, "min_count > max_count");
+    return CAPS_SA_OK;
+}
+
+// next[t] = the first head at or after tile t (1 <= k <= n, n >= 1)
+template <typename idx_t>
+void run_kmer_heads(Backend& be, const idx_t* dLCP, uint64_t n, uint64_t k, const KmerWs& w)
+{
+    const uint32_t tg = capped_grid(std::min<uint64_t>(w.p.n_tiles, 1u << 20), FM_NT);
+    CAPS_LAUNCH((kmer_head_kernel<idx_t>), tg, FM_NT, be, dLCP, n, k, w.p.n_tiles, w.next());
+    CAPS_LAUNCH(kmer_next_kernel, 1, FM_NT, be, w.next(), w.p.n_tiles, n);
+}
+
+// the table: counts, and with dRec the records; *found is written whenever the call gets as far as counting
+template <typename idx_t>
+int run_kmers(Backend& be, const idx_t* dSA, const idx_t* dLCP, uint64_t n, uint64_t k, uint64_t min_count, uint64_t max_count, void* dRec,
+              uint64_t capacity, uint64_t* found, const KmerWs& w)
+{
+    *found = 0;
+    if (n == 0 || k > n) return CAPS_SA_OK;
+    if (min_count == 0) min_count = 1;
+    run_kmer_heads<idx_t>(be, dLCP, n, k, w);
+    const uint32_t tg = capped_grid(std::min<uint64_t>(w.p.n_tiles, 1u << 20), FM_NT);
+    CAPS_LAUNCH((kmer_run_kernel<idx_t, KMER_COUNT>), tg, FM_NT, be, dSA, dLCP, n, k, w.p.n_tiles, (const uint64_t*)w.next(), min_count, max_count,
+                w.cnt(), (uint64_t*)nullptr, (uint64_t)0, 0u, (uint64_t*)nullptr);
+    CAPS_LAUNCH(fm_scan_kernel, 1, FM_NT, be, w.cnt(), w.p.n_tiles, 0u, 1u, w.tot());
+    be.d2h(found, w.tot(), sizeof(uint64_t));
+    be.sync();
+    if (!dRec) return CAPS_SA_OK;
+    if (*found > capacity) return fail(CAPS_SA_EINVAL, "capacity is smaller than the number of k-mers (*n_records; a call with dRecords = NULL counts them)");
+    if (*found) {
+        CAPS_LAUNCH((kmer_run_kernel<idx_t, KMER_WRITE>), tg, FM_NT, be, dSA, dLCP, n, k, w.p.n_tiles, (const uint64_t*)w.next(), min_count, max_count,
+                    w.cnt(), static_cast<uint64_t*>(dRec), capacity, 0u, (uint64_t*)nullptr);
+        be.sync();
+    }
+    return CAPS_SA_OK;
+}
+
+template <typename idx_t>
+int run_kmer_spectrum(Backend& be, const idx_t* dSA, const idx_t* dLCP, uint64_t n, uint64_t k, uint32_t bins, uint64_t* hist, const KmerWs& w)
+{
+    std::memset(hist, 0, ((size_t)bins + 1) * sizeof(uint64_t));
+    if (n == 0 || k > n) return CAPS_SA_OK;
+    run_kmer_heads<idx_t>(be, dLCP, n, k, w);
+    CAPS_LAUNCH((kmer_run_kernel<idx_t, KMER_SPECTRUM>), w.p.grid, FM_NT, be, dSA, dLCP, n, k, w.p.n_tiles, (const uint64_t*)w.next(), (uint64_t)1,
+                (uint64_t)0, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, bins, w.hist());
+    CAPS_LAUNCH(fm_scan_kernel, bins + 1, FM_NT, be, w.hist(), (uint64_t)w.p.grid, 0u, bins + 1, w.tot());
+    be.d2h(hist, w.tot(), ((size_t)bins + 1) * sizeof(uint64_t));
+    be.sync();
+    return CAPS_SA_OK;
+}
+
+template <typename idx_t>
+int run_kmer_census(Backend& be, const idx_t* dSA, const idx_t* dLCP, uint64_t n, uint32_t max_k, uint64_t* distinct, uint64_t* unique, const KmerWs& w)
+{
+    std::memset(distinct, 0, ((size_t)max_k + 1) * sizeof(uint64_t));
+    std::memset(unique, 0, ((size_t)max_k + 1) * sizeof(uint64_t));
+    if (n == 0) return CAPS_SA_OK;
+    CAPS_LAUNCH((kmer_census_kernel<idx_t>), w.p.grid, FM_NT, be, dSA, dLCP, n, max_k, w.p.n_tiles, w.hist());
+    CAPS_LAUNCH(fm_scan_kernel, max_k + 1, FM_NT, be, w.hist(), (uint64_t)w.p.grid, 0u, max_k + 1, w.tot());
+    CAPS_LAUNCH(fm_scan_kernel, max_k + 1, FM_NT, be, w.hist(), (uint64_t)w.p.grid, KMER_KEYS, max_k + 1, w.tot());
+    std::vector<uint64_t> t(2 * KMER_KEYS);
+    be.d2h(t.data(), w.tot(), t.size() * sizeof(uint64_t));
+    be.sync();
+    int64_t d = 0, u = 0;                                   // the differences summed from the left
+    for (uint32_t k = 1; k <= max_k; ++k) {
+        d += (int64_t)t[k];
+        u += (int64_t)t[KMER_KEYS + k];
+        distinct[k] = (uint64_t)d;
+        unique[k] = (uint64_t)u;
+    }
+    return CAPS_SA_OK;
+}
+
+template <typename idx_t>
+int kmers_device(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, uint64_t min_count, uint64_t max_count, void* dRec, uint64_t capacity,
+                 uint64_t* n_records, void* workspace, uint64_t workspace_bytes, void* stream)
+{
+    if (int rc = kmer_check_arrays<idx_t>(dSA, dLCP, n)) return rc;
+    if (!n_records) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (int rc = kmer_check_counts(k, min_count, max_count)) return rc;
+    if (reinterpret_cast<uintptr_t>(dRec) & 7u) return fail(CAPS_SA_EINVAL, "dRecords must be 8-byte aligned");
+    if (int rc = kmer_check_ws(workspace, workspace_bytes, n)) return rc;
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);
+        KmerWs w;
+        if (n && k <= n) w = kmer_ws(be, da, workspace, workspace_bytes, n);
+        return run_kmers<idx_t>(be, static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), n, k, min_count, max_count, dRec, capacity,
+                                n_records, w);
+    });
+}
+template <typename idx_t>
+int kmer_spectrum_device(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, uint32_t bins, uint64_t* hist, void* workspace,
+                         uint64_t workspace_bytes, void* stream)
+{
+    if (int rc = kmer_check_arrays<idx_t>(dSA, dLCP, n)) return rc;
+    if (!hist) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (k == 0) return fail(CAPS_SA_EINVAL, "k must be at least 1");
+    if (bins < 1 || bins > KMER_MAX_BINS) return fail(CAPS_SA_EINVAL, "bins must be in 1 .. 1024");
+    if (int rc = kmer_check_ws(workspace, workspace_bytes, n)) return rc;
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);
+        KmerWs w;
+        if (n && k <= n) w = kmer_ws(be, da, workspace, workspace_bytes, n);
+        return run_kmer_spectrum<idx_t>(be, static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), n, k, bins, hist, w);
+    });
+}
+template <typename idx_t>
+int kmer_census_device(const void* dSA, const void* dLCP, uint64_t n, uint32_t max_k, uint64_t* distinct, uint64_t* unique, void* workspace,
+                       uint64_t workspace_bytes, void* stream)
+{
+    if (int rc = kmer_check_arrays<idx_t>(dSA, dLCP, n)) return rc;
+    if (!distinct || !unique) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (max_k < 1 || max_k > KMER_MAX_BINS) return fail(CAPS_SA_EINVAL, "max_k must be in 1 .. 1024");
+    if (int rc = kmer_check_ws(workspace, workspace_bytes, n)) return rc;
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);
+        KmerWs w;
+        if (n) w = kmer_ws(be, da, workspace, workspace_bytes, n);
+        return run_kmer_census<idx_t>(be, static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), n, max_k, distinct, unique, w);
+    });
+}
+
+// host SA / LCP: both up into buffers of the call's own, the device form on them, the records down
+template <typename idx_t> struct KmerHostArrays {
+    idx_t* sa = nullptr;
+    idx_t* lcp = nullptr;
+    KmerHostArrays(Backend& be, DevAllocs& da, const idx_t* SA, const idx_t* LCP, uint64_t n)
+    {
+        if (!n) return;
+        sa = da.get<idx_t>(n);
+        lcp = da.get<idx_t>(n);
+        be.h2d(sa, SA, n * sizeof(idx_t));
+        be.h2d(lcp, LCP, n * sizeof(idx_t));
+    }
+};
+template <typename idx_t>
+int kmers_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint64_t k, uint64_t min_count, uint64_t max_count, void* records, uint64_t capacity,
+               uint64_t* n_records, int device)
+{
+    if (int rc = kmer_check_arrays<idx_t>(SA, LCP, n)) return rc;
+    if (!n_records) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (int rc = kmer_check_counts(k, min_count, max_count)) return rc;
+    if (reinterpret_cast<uintptr_t>(records) & 7u) return fail(CAPS_SA_EINVAL, "records must be 8-byte aligned");
+    if (n == 0 || k > n) { *n_records = 0; return CAPS_SA_OK; }
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        Backend be(nullptr);
+        DevAllocs da(be);
+        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
+        const KmerWs w = kmer_ws(be, da, nullptr, 0, n);
+        if (int rc = run_kmers<idx_t>(be, a.sa, a.lcp, n, k, min_count, max_count, nullptr, 0, n_records, w)) return rc;
+        if (!records) return CAPS_SA_OK;
+        if (*n_records > capacity) return fail(CAPS_SA_EINVAL, "capacity is smaller than the number of k-mers (*n_records; a call with records = NULL counts them)");
+        if (*n_records == 0) return CAPS_SA_OK;
+        const uint64_t found = *n_records;
+        uint64_t* dRec = da.get<uint64_t>(3 * found);
+        if (int rc = run_kmers<idx_t>(be, a.sa, a.lcp, n, k, min_count, max_count, dRec, found, n_records, w)) return rc;
+        be.d2h(records, dRec, found * 24);
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+template <typename idx_t>
+int kmer_spectrum_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint64_t k, uint32_t bins, uint64_t* hist, int device)
+{
+    if (int rc = kmer_check_arrays<idx_t>(SA, LCP, n)) return rc;
+    if (!hist) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (k == 0) return fail(CAPS_SA_EINVAL, "k must be at least 1");
+    if (bins < 1 || bins > KMER_MAX_BINS) return fail(CAPS_SA_EINVAL, "bins must be in 1 .. 1024");
+    if (n == 0 || k > n) { std::memset(hist, 0, ((size_t)bins + 1) * sizeof(uint64_t)); return CAPS_SA_OK; }
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        Backend be(nullptr);
+        DevAllocs da(be);
+        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
+        return run_kmer_spectrum<idx_t>(be, a.sa, a.lcp, n, k, bins, hist, kmer_ws(be, da, nullptr, 0, n));
+    });
+}
+template <typename idx_t>
+int kmer_census_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint32_t max_k, uint64_t* distinct, uint64_t* unique, int device)
+{
+    if (int rc = kmer_check_arrays<idx_t>(SA, LCP, n)) return rc;
+    if (!distinct || !unique) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (max_k < 1 || max_k > KMER_MAX_BINS) return fail(CAPS_SA_EINVAL, "max_k must be in 1 .. 1024");
+    if (n == 0) {
+        std::memset(distinct, 0, ((size_t)max_k + 1) * sizeof(uint64_t));
+        std::memset(unique, 0, ((size_t)max_k + 1) * sizeof(uint64_t));
+        return CAPS_SA_OK;
+    }
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        Backend be(nullptr);
+        DevAllocs da(be);
+        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
+        return run_kmer_census<idx_t>(be, a.sa, a.lcp, n, max_k, distinct, unique, kmer_ws(be, da, nullptr, 0, n));
+    });
+}
+
 // Text on the device for the kernel-level entry points.
 struct DevText {
     uint8_t* raw = nullptr;
@@ -3150,6 +3428,31 @@ int CAPS_API(fm_match_device)(const void* dIndex, uint64_t index_bytes, const vo
 int CAPS_API(fm_match)(const void* index, uint64_t index_bytes, const uint8_t* patterns, const uint64_t* pat_off, uint64_t q, uint32_t max_len,
                        uint32_t* len, uint64_t* first, uint64_t* count, int device)
 { return caps::fm_match_host(index, index_bytes, patterns, pat_off, q, max_len, len, first, count, device); }
+int CAPS_API(kmer_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::kmer_workspace_bytes(n, idx_bytes, bytes); }
+#define CAPS_DEFINE_KMER(SFX, IDX)                                                                                          \
+    int CAPS_API(kmers_device_##SFX)(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, uint64_t min_count,         \
+                                     uint64_t max_count, void* dRecords, uint64_t capacity, uint64_t* n_records, void* ws,  \
+                                     uint64_t ws_bytes, void* stream)                                                       \
+    { return caps::kmers_device<IDX>(dSA, dLCP, n, k, min_count, max_count, dRecords, capacity, n_records, ws, ws_bytes, stream); } \
+    int CAPS_API(kmer_spectrum_device_##SFX)(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, uint32_t bins,      \
+                                             uint64_t* hist, void* ws, uint64_t ws_bytes, void* stream)                     \
+    { return caps::kmer_spectrum_device<IDX>(dSA, dLCP, n, k, bins, hist, ws, ws_bytes, stream); }                          \
+    int CAPS_API(kmer_census_device_##SFX)(const void* dSA, const void* dLCP, uint64_t n, uint32_t max_k, uint64_t* distinct, \
+                                           uint64_t* unique, void* ws, uint64_t ws_bytes, void* stream)                     \
+    { return caps::kmer_census_device<IDX>(dSA, dLCP, n, max_k, distinct, unique, ws, ws_bytes, stream); }                  \
+    int CAPS_API(kmers_##SFX)(const IDX* SA, const IDX* LCP, uint64_t n, uint64_t k, uint64_t min_count, uint64_t max_count, \
+                              void* records, uint64_t capacity, uint64_t* n_records, int device)                            \
+    { return caps::kmers_host<IDX>(SA, LCP, n, k, min_count, max_count, records, capacity, n_records, device); }            \
+    int CAPS_API(kmer_spectrum_##SFX)(const IDX* SA, const IDX* LCP, uint64_t n, uint64_t k, uint32_t bins, uint64_t* hist, \
+                                      int device)                                                                           \
+    { return caps::kmer_spectrum_host<IDX>(SA, LCP, n, k, bins, hist, device); }                                            \
+    int CAPS_API(kmer_census_##SFX)(const IDX* SA, const IDX* LCP, uint64_t n, uint32_t max_k, uint64_t* distinct,          \
+                                    uint64_t* unique, int device)                                                           \
+    { return caps::kmer_census_host<IDX>(SA, LCP, n, max_k, distinct, unique, device); }
+CAPS_DEFINE_KMER(u32, uint32_t)
+CAPS_DEFINE_KMER(u64, uint64_t)
+#undef CAPS_DEFINE_KMER
+
 int CAPS_API(fm_mems_workspace_bytes)(uint64_t total_pattern_bytes, uint64_t q, uint64_t* bytes)
 { return caps::fm_mems_workspace_bytes(total_pattern_bytes, q, bytes); }
 int CAPS_API(fm_mems_device)(const void* dIndex, uint64_t index_bytes, const void* dPatterns, const void* dPatOff, uint64_t q, uint32_t min_len,

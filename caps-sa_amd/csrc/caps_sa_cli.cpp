@@ -2,6 +2,7 @@
 // (reference src/main.cpp:43-93):
 //
 //     caps_sa <input_path> <output_path> [subproblem-count] [bounded-context] [--pretty-print] [--gpus N] [--bwt PATH]
+//     caps_sa <input_path> <output_path> [subproblem-count] [--kmers K PATH [--min-count A] [--max-count B]] [--kmer-spectrum K PATH]
 //     caps_sa --inverse-bwt IN.bwt OUT
 //     caps_sa <input_path> <output_path> [subproblem-count] --fm-index PATH [--fm-sample S] [--fm-text-sample T]
 //     caps_sa <input_path> <output_path> [subproblem-count] --raw [--bwt PATH] [--fm-index PATH [--fm-sample S]]
@@ -10,6 +11,14 @@
 //     caps_sa --fm-from-bwt IN.bwt OUT.fm [--fm-sample S] [--fm-text-sample T]
 //     caps_sa --fm-extract INDEX RANGES
 //
+// * --kmers K PATH [--min-count A] [--max-count B] (not in the reference; on the build line): after the SA / LCP output, the k-mer
+//   table of the (remapped) text to PATH (include/caps_sa_hip.h "k-mers from SA and LCP"): one line "kmer<TAB>count" per distinct
+//   K-mer with A <= count <= B (defaults: every count), in the library's byte order.  Refused with --raw (arbitrary bytes do not
+//   make lines) and with a bounded context (its order is no suffix array), each with a message, before anything is written;
+//   --min-count / --max-count without --kmers are refused;
+// * --kmer-spectrum K PATH (not in the reference; on the build line): the multiplicity spectrum to PATH, one line "c number" for
+//   c = 1 .. 1024: the distinct K-mers that occur c times (the last line: 1024 times or more).  Allowed with --raw; refused with a
+//   bounded context;
 // * --raw (not in the reference; on the build line only): the text as given, no remap to {A,C,G,T} -- SA, LCP and --bwt are those of
 //   the file's own bytes, and --fm-index PATH writes the wide format (include/caps_sa_hip.h "FM-index: the wide format") for 1 .. 256
 //   distinct bytes.  --fm-search and --fm-mems tell a wide index by its magic and take the pattern lines as bytes, unremapped (a
@@ -65,6 +74,12 @@
 
 #include "Suffix_Array.hpp"
 
+// A driver that compiles this file over a renamed C ABI (#define caps_sa_hip_build_multi_u32 ...) and was written before the k-mer
+// entry points existed has no twin for them to link against: it gets the CLI without --kmers / --kmer-spectrum (both refused).
+#if defined(caps_sa_hip_build_multi_u32) && !defined(caps_sa_hip_kmers_u32)
+#define CAPS_CLI_NO_KMERS 1
+#endif
+
 static bool read_input(const std::string& path, std::string& text)
 {
     std::ifstream in(path, std::ios::binary | std::ios::ate);
@@ -89,9 +104,16 @@ static bool parse_count(const std::string& s, size_t& out)
     return true;
 }
 
+// what --kmers / --kmer-spectrum ask for (k = 0: not asked for)
+struct KmerJob {
+    size_t k = 0, min_count = 1, max_count = 0, spectrum_k = 0;
+    std::string path, spectrum_path;
+};
+
 template <typename idx_t>
 static int run(const std::string& text, const std::string& out_path, size_t p, size_t ctx, bool pretty, const std::vector<int>& devices,
-               const std::string& bwt_path, const std::string& fm_path = std::string(), uint32_t fm_sample = 32, uint32_t fm_text_sample = 0, bool raw = false)
+               const std::string& bwt_path, const std::string& fm_path = std::string(), uint32_t fm_sample = 32, uint32_t fm_text_sample = 0, bool raw = false,
+               const KmerJob& km = KmerJob())
 {
     if (p > std::numeric_limits<idx_t>::max()) { std::cerr << "subproblem-count does not fit the index type\n"; return EXIT_FAILURE; }
     // the bounded-context mode replays the reference's merge history, one GPU thread per merge node -- the top levels
@@ -137,6 +159,26 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
         if (fm_text_sample) std::cerr << ", text samples every " << fm_text_sample;
         std::cerr << ".\n";
     }
+#ifndef CAPS_CLI_NO_KMERS
+    if (km.k) {
+        const auto table = suf_arr.kmers(km.k, km.min_count, km.max_count);
+        std::ofstream out(km.path, std::ios::binary);
+        if (!out) { std::cerr << km.path << " : cannot open for writing\n"; return EXIT_FAILURE; }
+        for (const auto& r : table) {
+            out.write(text.data() + r.pos, static_cast<std::streamsize>(km.k));
+            out << '\t' << r.count << '\n';
+        }
+        if (!out) return EXIT_FAILURE;
+        std::cerr << "k-mers: " << table.size() << " distinct " << km.k << "-mers written.\n";
+    }
+    if (km.spectrum_k) {
+        const std::vector<uint64_t> hist = suf_arr.kmer_spectrum(km.spectrum_k, 1024);
+        std::ofstream out(km.spectrum_path, std::ios::binary);
+        if (!out) { std::cerr << km.spectrum_path << " : cannot open for writing\n"; return EXIT_FAILURE; }
+        for (size_t c = 1; c <= 1024; ++c) out << c << ' ' << hist[c] << '\n';
+        if (!out) return EXIT_FAILURE;
+    }
+#endif
     return 0;
 }
 
@@ -400,8 +442,31 @@ int main(int argc, char* argv[])
     bool pretty = false, bwt = false, fm = false, fm_sample_given = false, fm_text_given = false, raw = false;
     size_t gpus = 1, fm_sample = 32, fm_text_sample = 0;
     std::string bwt_path, fm_path;
+    KmerJob km;
+    bool kmers = false, spectrum = false, min_count_given = false, max_count_given = false;
     for (int i = 1; i < argc; ++i) {
         if (std::strcmp(argv[i], "--pretty-print") == 0) pretty = true;
+        else if (std::strcmp(argv[i], "--kmers") == 0 || std::strcmp(argv[i], "--kmer-spectrum") == 0) {
+            const bool table = std::strcmp(argv[i], "--kmers") == 0;
+            const char* opt = argv[i];
+            size_t k = 0;
+            if ((table ? kmers : spectrum)) { std::cerr << opt << ": given twice\n"; return EXIT_FAILURE; }
+            if (i + 2 >= argc || !parse_count(argv[i + 1], k) || k < 1 || std::strncmp(argv[i + 2], "--", 2) == 0) {
+                std::cerr << opt << ": usage: " << opt << " K PATH (K >= 1)\n";
+                return EXIT_FAILURE;
+            }
+            if (table) { kmers = true; km.k = k; km.path = argv[i + 2]; }
+            else { spectrum = true; km.spectrum_k = k; km.spectrum_path = argv[i + 2]; }
+            i += 2;
+        }
+        else if (std::strcmp(argv[i], "--min-count") == 0 || std::strcmp(argv[i], "--max-count") == 0) {
+            const bool lo = std::strcmp(argv[i], "--min-count") == 0;
+            size_t v = 0;
+            if (i + 1 >= argc || !parse_count(argv[i + 1], v) || v < 1) { std::cerr << argv[i] << ": a count of at least 1, please\n"; return EXIT_FAILURE; }
+            (lo ? km.min_count : km.max_count) = v;
+            (lo ? min_count_given : max_count_given) = true;
+            ++i;
+        }
         else if (std::strcmp(argv[i], "--raw") == 0) raw = true;
         else if (std::strcmp(argv[i], "--bwt") == 0) {
             bwt = true;
@@ -435,7 +500,8 @@ int main(int argc, char* argv[])
     if (pos.size() < 2) {
         std::cerr << "Usage: caps_sa <input_path> <output_path> <(optional)-subproblem-count> "
                      "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH> "
-                     "<(optional)--fm-index PATH [--fm-sample S] [--fm-text-sample T]> <(optional)--raw>\n"
+                     "<(optional)--fm-index PATH [--fm-sample S] [--fm-text-sample T]> <(optional)--raw> "
+                     "<(optional)--kmers K PATH [--min-count A] [--max-count B]> <(optional)--kmer-spectrum K PATH>\n"
                      "       caps_sa --inverse-bwt IN.bwt OUT\n"
                      "       caps_sa --fm-search INDEX PATTERNS [--locate K]\n"
                      "       caps_sa --fm-mems INDEX PATTERNS [--min-len L]\n"
@@ -453,6 +519,22 @@ int main(int argc, char* argv[])
         struct stat sb;                                       // (an input that cannot be stat'ed is reported by read_input below)
         if (ctx != 0 && stat(pos[0].c_str(), &sb) == 0 && ctx < static_cast<size_t>(sb.st_size)) {
             std::cerr << "--bwt: a bounded-context order (bounded-context " << ctx << ") is not a suffix array and has no BWT\n";
+            return EXIT_FAILURE;
+        }
+    }
+    // --kmers / --kmer-spectrum: the same manners
+#ifdef CAPS_CLI_NO_KMERS
+    if (kmers || spectrum) { std::cerr << (kmers ? "--kmers" : "--kmer-spectrum") << ": not built into this driver\n"; return EXIT_FAILURE; }
+#endif
+    if (min_count_given && !kmers) { std::cerr << "--min-count: only with --kmers K PATH\n"; return EXIT_FAILURE; }
+    if (max_count_given && !kmers) { std::cerr << "--max-count: only with --kmers K PATH\n"; return EXIT_FAILURE; }
+    if (kmers && raw) { std::cerr << "--kmers: the table is lines of text, and --raw keeps arbitrary bytes that do not make lines (--kmer-spectrum works with --raw)\n"; return EXIT_FAILURE; }
+    if (kmers && max_count_given && km.min_count > km.max_count) { std::cerr << "--kmers: --min-count " << km.min_count << " is above --max-count " << km.max_count << "\n"; return EXIT_FAILURE; }
+    if (kmers || spectrum) {
+        const char* opt = kmers ? "--kmers" : "--kmer-spectrum";
+        struct stat sb;
+        if (ctx != 0 && stat(pos[0].c_str(), &sb) == 0 && ctx < static_cast<size_t>(sb.st_size)) {
+            std::cerr << opt << ": a bounded-context order (bounded-context " << ctx << ") is not a suffix array and has no k-mer table\n";
             return EXIT_FAILURE;
         }
     }
@@ -498,8 +580,8 @@ int main(int argc, char* argv[])
 
     std::cerr << "Text length: " << text.size() << ".\n";
     try {
-        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw);
-        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw);
+        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km);
+        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km);
     } catch (const std::exception& e) {
         std::cerr << e.what() << "\n";
         return EXIT_FAILURE;

@@ -6461,4 +6461,337 @@ GLOBAL_FN LAUNCH_BOUNDS(FM_NT) fm_extract_kernel(KCTX FmView v, const uint64_t* 
     }
 }
 
+// ---- k-mers from SA and LCP (capi_impl.h kmer_*; include/caps_sa_hip.h "k-mers from SA and LCP") ---------------------------------
+// Rank i is a head iff i == 0 or LCP[i] < k; a run is a head and the ranks up to the next head; a run whose head's suffix has k bytes
+// (SA[h] <= n - k) is a distinct k-mer and its length the k-mer's count.  Tiles of FM_TILE ranks, FM_NT threads, grid-stride:
+//   kmer_head_kernel    per tile the rank of its first head (n: none)
+//   kmer_next_kernel    one workgroup: the suffix minimum over the tiles, next[t] = the first head at or after tile t, next[n_tiles] = n
+//   kmer_run_kernel     per tile: coalesced 16-byte loads of LCP (and of SA where a chunk has a head) leave one byte per chunk in LDS
+//                       -- its head bits and, 4 bits up, "this head's suffix has k bytes"; then a lane owns KMER_LANE consecutive
+//                       ranks as a 64-bit mask, the first head behind the lane comes from a backward scan over the lanes' first
+//                       heads in LDS and behind the tile from next[tile + 1]: no lane walks forward, whatever the run's length
+//   kmer_census_kernel  one pass, every k at once: two difference histograms
+// Nothing is indexed by a value read from SA or LCP except histogram bins, and those are compared with their bound first.
+constexpr uint64_t KMER_TILE = FM_TILE;
+constexpr uint32_t KMER_LANE = (uint32_t)(KMER_TILE / FM_NT);     // 64 ranks per lane: one mask word
+constexpr uint32_t KMER_MAX_BINS = 1024;                          // spectrum bins, census max_k
+constexpr uint32_t KMER_KEYS = KMER_MAX_BINS + 1;                 // columns of a histogram: bins 0 .. 1024
+constexpr uint32_t KMER_CEN_COPIES = 4;                           // copies of the census histograms in LDS, one per lane mod 4
+constexpr uint32_t KMER_GROUP = 16;                               // lanes of a group of the two-step scans over the lanes
+enum { KMER_COUNT = 0, KMER_WRITE = 1, KMER_SPECTRUM = 2 };
+static_assert(KMER_LANE == 64 && FM_NT == KMER_GROUP * KMER_GROUP, "a lane's ranks are one 64-bit mask; 16 groups of 16 lanes");
+template <typename idx_t> struct KmerGeom {
+    static constexpr uint32_t PER = 16u / sizeof(idx_t);                  // ranks of a 16-byte chunk (4 / 2)
+    static constexpr uint32_t CHUNKS = (uint32_t)(KMER_TILE / PER);       // chunks of a tile
+    static constexpr uint32_t ROUNDS = CHUNKS / FM_NT;                    // chunks per thread and tile (16 / 32)
+    static constexpr uint32_t LANE_CHUNKS = KMER_LANE / PER;              // chunks of a lane's ranks
+};
+template <typename idx_t> struct alignas(sizeof(idx_t)) KmerChunk { idx_t v[16u / sizeof(idx_t)]; };
+
+// ranks i0 .. i0 + PER - 1 (i0 < n): the entries of A that exist (the others 0)
+template <typename idx_t>
+HD KmerChunk<idx_t> kmer_load(const idx_t* __restrict__ A, uint64_t n, uint64_t i0)
+{
+    constexpr uint32_t PER = KmerGeom<idx_t>::PER;
+    KmerChunk<idx_t> c;
+    if (i0 + PER <= n) {
+        c = *reinterpret_cast<const KmerChunk<idx_t>*>(A + i0);
+    } else {
+        for (uint32_t j = 0; j < PER; ++j) c.v[j] = i0 + j < n ? A[i0 + j] : (idx_t)0;
+    }
+    return c;
+}
+// the head bits of the chunk at i0 (i0 < n)
+template <typename idx_t>
+HD uint32_t kmer_head_bits(const idx_t* __restrict__ LCP, uint64_t n, uint64_t k, uint64_t i0)
+{
+    constexpr uint32_t PER = KmerGeom<idx_t>::PER;
+    const KmerChunk<idx_t> c = kmer_load<idx_t>(LCP, n, i0);
+    uint32_t hb = 0;
+    UNROLL
+    for (uint32_t j = 0; j < PER; ++j) hb |= (i0 + j < n && (uint64_t)c.v[j] < k ? 1u : 0u) << j;
+    return i0 == 0 ? hb | 1u : hb;
+}
+
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) kmer_head_kernel(KCTX const idx_t* __restrict__ LCP, uint64_t n, uint64_t k, uint64_t n_tiles,
+                                                 uint64_t* __restrict__ head)
+{
+    using G = KmerGeom<idx_t>;
+    SHARED_ARRAY(uint32_t, first, 1);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t t0 = tile * KMER_TILE;
+        PAR(tid) { if (tid == 0) first[0] = (uint32_t)KMER_TILE; }
+        SYNC();
+        PAR(tid) {
+            // four chunks in flight, then a look: a lane stops at its first head (where nearly every rank is one, a genome at
+            // k = 31, this pass reads a quarter of LCP; where none is, all of it)
+            uint32_t best = (uint32_t)KMER_TILE;
+            for (uint32_t j0 = 0; j0 < G::ROUNDS && best == (uint32_t)KMER_TILE; j0 += 4) {
+                uint32_t hb[4];
+                UNROLL
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint64_t i0 = t0 + (uint64_t)((j0 + j) * FM_NT + tid) * G::PER;
+                    hb[j] = i0 < n ? kmer_head_bits<idx_t>(LCP, n, k, i0) : 0u;
+                }
+                UNROLL
+                for (uint32_t j = 0; j < 4; ++j)
+                    if (hb[j] && best == (uint32_t)KMER_TILE) best = ((j0 + j) * FM_NT + tid) * G::PER + (uint32_t)__builtin_ctz(hb[j]);
+            }
+            if (best < (uint32_t)KMER_TILE) ATOMIC_MIN_U32(&first[0], best);
+        }
+        SYNC();
+        PAR(tid) { if (tid == 0) head[tile] = first[0] < (uint32_t)KMER_TILE ? t0 + first[0] : n; }
+        SYNC();
+    }
+}
+
+// one workgroup, fm_scan_kernel's shape with min from the right: head[t] = the first head at or after tile t; head[n_tiles] = n
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) kmer_next_kernel(KCTX uint64_t* __restrict__ head, uint64_t n_tiles, uint64_t n)
+{
+    SHARED_ARRAY(uint64_t, part, FM_NT);
+    const uint64_t per = (n_tiles + FM_NT - 1) / FM_NT;
+    PAR(tid) {
+        const uint64_t a = std::min<uint64_t>(n_tiles, tid * per), b = std::min<uint64_t>(n_tiles, a + per);
+        uint64_t m = n;
+        for (uint64_t t = a; t < b; ++t) m = std::min<uint64_t>(m, head[t]);
+        part[tid] = m;
+    }
+    SYNC();
+    PAR(tid) {
+        if (tid == 0) {
+            uint64_t m = n;
+            for (uint32_t t = FM_NT; t-- > 0;) { const uint64_t v = part[t]; part[t] = m; m = std::min<uint64_t>(m, v); }
+            head[n_tiles] = n;
+        }
+    }
+    SYNC();
+    PAR(tid) {
+        const uint64_t a = std::min<uint64_t>(n_tiles, tid * per), b = std::min<uint64_t>(n_tiles, a + per);
+        uint64_t m = part[tid];
+        for (uint64_t t = b; t-- > a;) { m = std::min<uint64_t>(m, head[t]); head[t] = m; }
+    }
+}
+
+// the runs whose heads are the bits of m (rank r0 + bit): f(head rank, length); behind the last one of the lane the run ends at lane_next
+template <typename F>
+DEV_INLINE void kmer_each_run(uint64_t m, uint64_t v, uint64_t r0, uint64_t lane_next, F&& f)
+{
+    while (m) {
+        const uint32_t p = (uint32_t)__builtin_ctzll(m);
+        m &= m - 1;
+        const uint64_t h = r0 + p, e = m ? r0 + (uint32_t)__builtin_ctzll(m) : lane_next;
+        if ((v >> p) & 1u) f(h, e - h);
+    }
+}
+
+// MODE KMER_COUNT: cnt[tile] = the k-mers of the tile's heads with min_count <= count (<= max_count unless that is 0).
+// MODE KMER_WRITE: cnt[] scanned (fm_scan_kernel); the same k-mers as records (first | count | pos) at cnt[tile] + their number in the
+//                  tile, three 8-byte stores each; a slot at or beyond cap is not written.
+// MODE KMER_SPECTRUM: every k-mer adds 1 to bin min(count, bins) of the workgroup's histogram; hist[bin * K_GRID_DIM + workgroup].
+//                  Bin 1 (nearly every k-mer of a genome at k = 31) is counted in a register and added once per thread: no LDS
+//                  atomic on the common path, and one copy of the histogram (4 KB) instead of eight.
+template <typename idx_t, int MODE>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) kmer_run_kernel(KCTX const idx_t* __restrict__ SA, const idx_t* __restrict__ LCP, uint64_t n, uint64_t k,
+                                                uint64_t n_tiles, const uint64_t* __restrict__ next, uint64_t min_count, uint64_t max_count,
+                                                uint64_t* __restrict__ cnt, uint64_t* __restrict__ rec, uint64_t cap, uint32_t bins,
+                                                uint64_t* __restrict__ hist)
+{
+    using G = KmerGeom<idx_t>;
+    SHARED_ARRAY(uint8_t, bits, G::CHUNKS);                // per chunk: head bits | valid bits << 4
+    SHARED_ARRAY(uint32_t, lane, FM_NT);                   // per lane: its first head (tile-relative; KMER_TILE: none), then its records
+    SHARED_ARRAY(uint32_t, scan, FM_NT);                   // the scan of lane[] inside its group of 16, exclusive
+    SHARED_ARRAY(uint32_t, grp, 2 * KMER_GROUP);           // per group: its min / sum, and the exclusive scan over the groups
+    SHARED_ARRAY(uint32_t, h, MODE == KMER_SPECTRUM ? KMER_KEYS : 1);
+    TL_DECL(uint64_t, st, 3);                              // a lane's head mask, valid mask, the first head behind its ranks
+    TL_DECL(uint32_t, ones, 1);
+    const uint64_t last_valid = k <= n ? n - k : 0;        // (k > n: no suffix has k bytes; the host never launches then)
+    auto passes = [&](uint64_t c) { return c >= min_count && (max_count == 0 || c <= max_count); };
+    PAR(tid) {
+        TL(ones, tid, 0) = 0;
+        if (MODE == KMER_SPECTRUM) for (uint32_t b = tid; b < KMER_KEYS; b += FM_NT) h[b] = 0;
+    }
+    SYNC();
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t t0 = tile * KMER_TILE;
+        PAR(tid) {
+            if (tid == 0 && MODE == KMER_COUNT) h[0] = 0;
+            UNROLL
+            for (uint32_t j0 = 0; j0 < G::ROUNDS; j0 += 4) {
+                uint32_t hb[4];
+                UNROLL
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint64_t i0 = t0 + (uint64_t)((j0 + j) * FM_NT + tid) * G::PER;
+                    hb[j] = i0 < n ? kmer_head_bits<idx_t>(LCP, n, k, i0) : 0u;
+                }
+                UNROLL
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint32_t c = (j0 + j) * FM_NT + tid;
+                    uint32_t vb = 0;
+                    if (hb[j] && k <= n) {
+                        const uint64_t i0 = t0 + (uint64_t)c * G::PER;
+                        const KmerChunk<idx_t> s = kmer_load<idx_t>(SA, n, i0);
+                        UNROLL
+                        for (uint32_t e = 0; e < G::PER; ++e) vb |= ((uint64_t)s.v[e] <= last_valid ? 1u : 0u) << e;
+                        vb &= hb[j];
+                    }
+                    bits[c] = (uint8_t)(hb[j] | (vb << 4));
+                }
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            uint64_t m = 0, v = 0;
+            UNROLL
+            for (uint32_t b = 0; b < G::LANE_CHUNKS; ++b) {
+                const uint32_t x = bits[tid * G::LANE_CHUNKS + b];
+                m |= (uint64_t)(x & 15u) << (b * G::PER);
+                v |= (uint64_t)(x >> 4) << (b * G::PER);
+            }
+            TL(st, tid, 0) = m;
+            TL(st, tid, 1) = v;
+            lane[tid] = m ? tid * KMER_LANE + (uint32_t)__builtin_ctzll(m) : (uint32_t)KMER_TILE;
+        }
+        SYNC();
+        PAR(tid) {                                          // backward: the first head behind every lane, inside its group
+            if (tid < KMER_GROUP) {
+                uint32_t run = (uint32_t)KMER_TILE;
+                for (uint32_t j = KMER_GROUP; j-- > 0;) {
+                    const uint32_t at = tid * KMER_GROUP + j, x = lane[at];
+                    scan[at] = run;
+                    run = std::min(run, x);
+                }
+                grp[tid] = run;
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            if (tid == 0) {
+                uint32_t run = (uint32_t)KMER_TILE;
+                for (uint32_t g = KMER_GROUP; g-- > 0;) { const uint32_t x = grp[g]; grp[KMER_GROUP + g] = run; run = std::min(run, x); }
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            const uint32_t nx = std::min(scan[tid], grp[KMER_GROUP + tid / KMER_GROUP]);
+            const uint64_t lane_next = nx < (uint32_t)KMER_TILE ? t0 + nx : next[tile + 1];
+            TL(st, tid, 2) = lane_next;
+            const uint64_t r0 = t0 + (uint64_t)tid * KMER_LANE;
+            if (MODE == KMER_SPECTRUM) {
+                uint32_t one = 0;
+                kmer_each_run(TL(st, tid, 0), TL(st, tid, 1), r0, lane_next, [&](uint64_t, uint64_t c) {
+                    if (c == 1 || bins == 1) ++one;
+                    else FETCH_ADD_U32(&h[c < bins ? (uint32_t)c : bins], 1u);
+                });
+                TL(ones, tid, 0) += one;
+            } else {
+                uint32_t mine = 0;
+                kmer_each_run(TL(st, tid, 0), TL(st, tid, 1), r0, lane_next, [&](uint64_t, uint64_t c) { mine += passes(c) ? 1u : 0u; });
+                if (MODE == KMER_COUNT) { if (mine) FETCH_ADD_U32(&h[0], mine); }
+                else lane[tid] = mine;
+            }
+        }
+        SYNC();
+        if (MODE == KMER_COUNT) {
+            PAR(tid) { if (tid == 0) cnt[tile] = h[0]; }
+            SYNC();
+        }
+        if (MODE == KMER_WRITE) {
+            PAR(tid) {                                      // forward: the records of the lanes before every lane
+                if (tid < KMER_GROUP) {
+                    uint32_t run = 0;
+                    for (uint32_t j = 0; j < KMER_GROUP; ++j) {
+                        const uint32_t at = tid * KMER_GROUP + j, x = lane[at];
+                        scan[at] = run;
+                        run += x;
+                    }
+                    grp[tid] = run;
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                if (tid == 0) {
+                    uint32_t run = 0;
+                    for (uint32_t g = 0; g < KMER_GROUP; ++g) { const uint32_t x = grp[g]; grp[KMER_GROUP + g] = run; run += x; }
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                uint64_t at = cnt[tile] + scan[tid] + grp[KMER_GROUP + tid / KMER_GROUP];
+                const uint64_t r0 = t0 + (uint64_t)tid * KMER_LANE;
+                kmer_each_run(TL(st, tid, 0), TL(st, tid, 1), r0, TL(st, tid, 2), [&](uint64_t hd, uint64_t c) {
+                    if (!passes(c)) return;
+                    if (at < cap) {
+                        rec[3 * at] = hd;
+                        rec[3 * at + 1] = c;
+                        rec[3 * at + 2] = (uint64_t)SA[hd];
+                    }
+                    ++at;
+                });
+            }
+            SYNC();
+        }
+    }
+    if (MODE == KMER_SPECTRUM) {
+        PAR(tid) { if (TL(ones, tid, 0)) FETCH_ADD_U32(&h[1], TL(ones, tid, 0)); }
+        SYNC();
+        PAR(tid) { for (uint32_t b = tid; b <= bins; b += FM_NT) hist[(uint64_t)b * K_GRID_DIM + K_BLOCK_IDX] = h[b]; }
+    }
+}
+
+// census: rank i, with a = LCP[i] (0 at rank 0), a' = max(a, LCP[i + 1]) (0 behind the last rank) and b = n - SA[i] (0 for an SA[i] that
+// is no position), adds 1 to distinct[k] for a < k <= b and to unique[k] for a' < k <= b -- as differences: +1 at bin lo + 1, -1 at
+// bin b + 1, summed from the left on the host.  A bin above max_k is never read by that sum, so it is not counted at all (on a genome
+// that is nearly every b + 1).  Two histograms of bins 0 .. max_k, KMER_CEN_COPIES copies each (copy = lane mod 4, bin-major, so the
+// copies of a bin lie in four banks); hist[(which * KMER_KEYS + bin) * K_GRID_DIM + workgroup] = the copies' sum, two's complement.
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) kmer_census_kernel(KCTX const idx_t* __restrict__ SA, const idx_t* __restrict__ LCP, uint64_t n, uint32_t max_k,
+                                                   uint64_t n_tiles, uint64_t* __restrict__ hist)
+{
+    using G = KmerGeom<idx_t>;
+    constexpr uint32_t ONE = KMER_CEN_COPIES * KMER_KEYS;
+    SHARED_ARRAY(uint32_t, d, 2 * ONE);
+    PAR(tid) { for (uint32_t b = tid; b < 2 * ONE; b += FM_NT) d[b] = 0; }
+    SYNC();
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t t0 = tile * KMER_TILE;
+        PAR(tid) {
+            uint32_t* D = d + (tid % KMER_CEN_COPIES);
+            auto add = [&](uint32_t* H, uint64_t a, uint64_t b) {
+                if (a < b && a < max_k) {
+                    FETCH_ADD_U32(&H[((uint32_t)a + 1u) * KMER_CEN_COPIES], 1u);
+                    if (b < max_k) FETCH_ADD_U32(&H[((uint32_t)b + 1u) * KMER_CEN_COPIES], 0xFFFFFFFFu);
+                }
+            };
+            for (uint32_t j = 0; j < G::ROUNDS; ++j) {
+                const uint64_t i0 = t0 + (uint64_t)(j * FM_NT + tid) * G::PER;
+                if (i0 >= n) break;
+                const KmerChunk<idx_t> l = kmer_load<idx_t>(LCP, n, i0), s = kmer_load<idx_t>(SA, n, i0);
+                const uint64_t behind = i0 + G::PER < n ? (uint64_t)LCP[i0 + G::PER] : 0;
+                UNROLL
+                for (uint32_t e = 0; e < G::PER; ++e) {
+                    const uint64_t i = i0 + e;
+                    if (i < n) {
+                        const uint64_t a = i == 0 ? 0 : (uint64_t)l.v[e];
+                        const uint64_t nx = e + 1 < G::PER ? (uint64_t)l.v[e + 1 < G::PER ? e + 1 : e] : behind;     // (0 behind rank n - 1)
+                        const uint64_t b = (uint64_t)s.v[e] < n ? n - (uint64_t)s.v[e] : 0;
+                        add(D, a, b);
+                        add(D + ONE, std::max(a, nx), b);
+                    }
+                }
+            }
+        }
+    }
+    SYNC();
+    PAR(tid) {
+        for (uint32_t b = tid; b <= max_k; b += FM_NT) {
+            for (uint32_t w = 0; w < 2; ++w) {
+                int64_t s = 0;
+                for (uint32_t c = 0; c < KMER_CEN_COPIES; ++c) s += (int32_t)d[w * ONE + b * KMER_CEN_COPIES + c];
+                hist[((uint64_t)w * KMER_KEYS + b) * K_GRID_DIM + K_BLOCK_IDX] = (uint64_t)s;
+            }
+        }
+    }
+}
+
 }  // namespace caps

@@ -622,6 +622,72 @@ int caps_sa_hip_fm_build_wide_u32(const uint8_t* BWT, uint64_t n, uint64_t prima
 int caps_sa_hip_fm_build_wide_u64(const uint8_t* BWT, uint64_t n, uint64_t primary, const uint64_t* SA, uint32_t sa_sample,
                                   void* index, uint64_t index_capacity, int device);
 
+/* ---- k-mers from SA and LCP ---------------------------------------------------------
+ * The k-mer table, the multiplicity spectrum and a census over every k of a text, from the two arrays a full-context construct()
+ * gives and nothing else: the text is not read. T is a text of n bytes, SA its suffix array, LCP[i] the exact common prefix of the
+ * suffixes SA[i - 1] and SA[i]; LCP[0] counts as 0 whatever it holds. k >= 1.
+ *   - Rank i is a HEAD iff i == 0 or LCP[i] < k.
+ *   - The RUN of a head h is the ranks h .. h' - 1, h' the next head, or n if there is none.
+ *   - A run IS A K-MER iff SA[h] <= n - k (computed without overflow; for k > n no run is a k-mer). Its bytes are
+ *     T[SA[h] .. SA[h] + k), its count is h' - h, its occurrences are SA[h .. h').
+ *   - A suffix shorter than k is always a run of its own and is no k-mer.
+ *   - The runs in rank order are the distinct k-mers in the library's byte order (the reference's signed-char order).
+ * The cost does not depend on k, and the table comes out sorted.
+ *
+ * Arrays of a bounded-context build (max_context > 0) are not a suffix array: the result is then unspecified. For arrays that are
+ * not the SA / LCP of any text the calls still terminate, read only SA[0 .. n) and LCP[0 .. n) and write only inside the output
+ * buffers: nothing is indexed by a value read from the arrays except histogram bins, and those are clamped. There is no validation
+ * pass and no error for such inputs.
+ *
+ * kmers: the k-mers with min_count <= count <= max_count (min_count = 0 is treated as 1, max_count = 0 means no upper bound,
+ * min_count > max_count > 0 is CAPS_SA_EINVAL) as records of 24 bytes, little-endian, in rank order:
+ *     u64 first (the head's rank) | u64 count | u64 pos (SA[first])
+ * *n_records (host) is always written. dRecords = NULL is the counting call. A non-null dRecords (8-byte aligned) with
+ * *n_records > capacity is CAPS_SA_EINVAL: *n_records is still valid and no record is written.
+ *
+ * kmer_spectrum: hist (host, u64[bins + 1]): hist[c], 1 <= c < bins, = the distinct k-mers that occur exactly c times,
+ * hist[bins] = those that occur bins times or more, hist[0] = 0. bins in 1 .. 1024.
+ *
+ * kmer_census: every k in 1 .. max_k (max_k in 1 .. 1024) from one pass: distinct[k] = the number of distinct k-mers, unique[k] =
+ * the number that occur once (host, u64[max_k + 1] each; index 0 is 0). Per rank i, with a = (i == 0 ? 0 : LCP[i]),
+ * a' = max(a, i + 1 < n ? LCP[i + 1] : 0) and b = (SA[i] < n ? n - SA[i] : 0): rank i adds 1 to distinct[k] for a < k <= b and to
+ * unique[k] for a' < k <= b.
+ *
+ * Common: k = 0, max_k = 0, a null pointer with n > 0, n > UINT32_MAX with _u32 or a workspace that is too small are
+ * CAPS_SA_EINVAL, checked before any allocation, nothing written. n = 0 succeeds with zeros. The workspace
+ * (caps_sa_hip_kmer_workspace_bytes) is O(n / 16,384) words and a fixed 16.8 MB of histogram columns, no array of n entries; NULL
+ * is allocated and freed by the call. dSA, dLCP, dRecords and workspace are device pointers on the current device; the work runs on
+ * hip_stream and has completed on return. Ranks beyond 2^32 (_u64 with n > UINT32_MAX) are untested.
+ */
+int caps_sa_hip_kmer_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes);
+int caps_sa_hip_kmers_device_u32(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, uint64_t min_count, uint64_t max_count,
+                                 void* dRecords, uint64_t capacity, uint64_t* n_records, void* workspace, uint64_t workspace_bytes,
+                                 void* hip_stream);
+int caps_sa_hip_kmers_device_u64(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, uint64_t min_count, uint64_t max_count,
+                                 void* dRecords, uint64_t capacity, uint64_t* n_records, void* workspace, uint64_t workspace_bytes,
+                                 void* hip_stream);
+int caps_sa_hip_kmer_spectrum_device_u32(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, uint32_t bins, uint64_t* hist,
+                                         void* workspace, uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_kmer_spectrum_device_u64(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, uint32_t bins, uint64_t* hist,
+                                         void* workspace, uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_kmer_census_device_u32(const void* dSA, const void* dLCP, uint64_t n, uint32_t max_k, uint64_t* distinct,
+                                       uint64_t* unique, void* workspace, uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_kmer_census_device_u64(const void* dSA, const void* dLCP, uint64_t n, uint32_t max_k, uint64_t* distinct,
+                                       uint64_t* unique, void* workspace, uint64_t workspace_bytes, void* hip_stream);
+/* Host SA and LCP (and host records): the arrays go up into device buffers of the call's own on `device`, the records come down. */
+int caps_sa_hip_kmers_u32(const uint32_t* SA, const uint32_t* LCP, uint64_t n, uint64_t k, uint64_t min_count, uint64_t max_count,
+                          void* records, uint64_t capacity, uint64_t* n_records, int device);
+int caps_sa_hip_kmers_u64(const uint64_t* SA, const uint64_t* LCP, uint64_t n, uint64_t k, uint64_t min_count, uint64_t max_count,
+                          void* records, uint64_t capacity, uint64_t* n_records, int device);
+int caps_sa_hip_kmer_spectrum_u32(const uint32_t* SA, const uint32_t* LCP, uint64_t n, uint64_t k, uint32_t bins, uint64_t* hist,
+                                  int device);
+int caps_sa_hip_kmer_spectrum_u64(const uint64_t* SA, const uint64_t* LCP, uint64_t n, uint64_t k, uint32_t bins, uint64_t* hist,
+                                  int device);
+int caps_sa_hip_kmer_census_u32(const uint32_t* SA, const uint32_t* LCP, uint64_t n, uint32_t max_k, uint64_t* distinct,
+                                uint64_t* unique, int device);
+int caps_sa_hip_kmer_census_u64(const uint64_t* SA, const uint64_t* LCP, uint64_t n, uint32_t max_k, uint64_t* distinct,
+                                uint64_t* unique, int device);
+
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
 /* merge_sort (src/Suffix_Array.cpp:112-129) of an arbitrary list of cnt distinct suffix
