@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from ._binding import CapsLib, CapsSaError, Stats, Shard, ShardInfo, EXPORTS, MEM_DTYPE, KMER_DTYPE  # noqa: F401
+from ._binding import CapsLib, CapsSaError, Stats, Shard, ShardInfo, EXPORTS, MEM_DTYPE, KMER_DTYPE, LZ_DTYPE, LZ_LITERAL  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CAPS_SA_LIB selects a tuning variant built by `make variant` (benchmarking only).
@@ -68,6 +68,19 @@ def kmer_census(SA, LCP, max_k: int, device: int = 0, _lib: CapsLib | None = Non
     """(distinct, unique), np.uint64[max_k + 1] each: for every k in 1 .. max_k the number of distinct k-mers and of those that
     occur once, from one pass."""
     return (_lib or lib()).kmer_census(SA, LCP, max_k, device=device)
+
+
+def lpf(SA, LCP, device: int = 0, _lib: CapsLib | None = None):
+    """(LPF, Prev) of the text whose full-context SA and LCP these are (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP"), e.g.
+    arrays read from a dump, in text order and SA's dtype: LPF[i] = the longest prefix of T[i:] that also starts at some j < i,
+    Prev[i] = such a j (all ones where LPF[i] = 0)."""
+    return (_lib or lib()).lpf(SA, LCP, device=device)
+
+
+def lz77(SA, LCP, device: int = 0, _lib: CapsLib | None = None) -> np.ndarray:
+    """The LZ77 factorization of that text: a structured array (LZ_DTYPE: pos, len, src) in text order; phrase j is
+    T[src : src + len] (the two may overlap), or the one byte T[pos] where src = LZ_LITERAL."""
+    return (_lib or lib()).lz77(SA, LCP, device=device)
 
 
 class SuffixArray:
@@ -139,9 +152,9 @@ class SuffixArray:
             raise RuntimeError("construct() has not been called")
         return self._primary
 
-    def _kmer_arrays(self):
+    def _kmer_arrays(self, what: str = "k-mers"):
         if self._ctx:
-            raise ValueError("k-mers need a full-context suffix array: this one was built with max_context set")
+            raise ValueError(f"{what} need a full-context suffix array: this one was built with max_context set")
         return self.SA(), self.LCP()
 
     def kmers(self, k: int, min_count: int = 1, max_count: int = 0) -> np.ndarray:
@@ -159,6 +172,18 @@ class SuffixArray:
         """(distinct, unique), np.uint64[max_k + 1] each: the number of distinct k-mers and of those that occur once, k = 1 .. max_k."""
         SA, LCP = self._kmer_arrays()
         return lib().kmer_census(SA, LCP, max_k, self._bits, self._device)
+
+    def lpf(self):
+        """(LPF, Prev) in text order: LPF[i] = the longest prefix of T()[i:] that also starts at some j < i, Prev[i] = such a j (all
+        ones where LPF[i] = 0)."""
+        SA, LCP = self._kmer_arrays("LPF and LZ77")
+        return lib().lpf(SA, LCP, self._bits, self._device)
+
+    def lz77(self) -> np.ndarray:
+        """The LZ77 factorization as a structured array (LZ_DTYPE: pos, len, src): phrase j is T()[src : src + len], or the one byte
+        T()[pos] where src = LZ_LITERAL."""
+        SA, LCP = self._kmer_arrays("LPF and LZ77")
+        return lib().lz77(SA, LCP, self._bits, self._device)
 
     def dump(self, path: str) -> None:
         """Suffix_Array::dump format (src/Suffix_Array.cpp:497-509): u64 n, SA, LCP."""

@@ -125,13 +125,14 @@ EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_b
            "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_from_bwt_workspace_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device",
            "fm_index_bytes_ex", "fm_add_text_samples", "fm_add_text_samples_device", "fm_extract_workspace_bytes", "fm_extract", "fm_extract_device",
            "fm_match", "fm_match_device", "fm_mems_workspace_bytes", "fm_mems", "fm_mems_device", "fm_wide_index_bytes",
-           "fm_wide_workspace_bytes", "kmer_workspace_bytes"] + SHARD_EXPORTS + [
+           "fm_wide_workspace_bytes", "kmer_workspace_bytes", "lpf_workspace_bytes", "lz77_workspace_bytes"] + SHARD_EXPORTS + [
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
     for name in ("build", "build_multi", "build_device", "verify_device", "verify_slice_device", "sort_suffixes", "sort_segments", "merge",
                  "upper_bound", "lcp", "build_bwt", "bwt_device", "inverse_bwt", "inverse_bwt_device", "fm_build", "fm_build_device",
                  "fm_build_from_bwt", "fm_build_from_bwt_device", "fm_build_wide", "fm_build_wide_device",
-                 "kmers", "kmers_device", "kmer_spectrum", "kmer_spectrum_device", "kmer_census", "kmer_census_device")
+                 "kmers", "kmers_device", "kmer_spectrum", "kmer_spectrum_device", "kmer_census", "kmer_census_device",
+                 "lpf", "lpf_device", "lz77", "lz77_device")
 ]
 
 
@@ -140,6 +141,10 @@ MEM_DTYPE = np.dtype([("pattern", "<u8"), ("start", "<u4"), ("length", "<u4"), (
 
 # a record of kmers (include/caps_sa_hip.h "k-mers from SA and LCP"): 24 bytes, little-endian
 KMER_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("pos", "<u8")])
+
+# a phrase of lz77 (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP"): 24 bytes, little-endian; src = LZ_LITERAL: one byte
+LZ_DTYPE = np.dtype([("pos", "<u8"), ("len", "<u8"), ("src", "<u8")])
+LZ_LITERAL = 0xFFFFFFFFFFFFFFFF
 
 
 class CapsSaError(RuntimeError):
@@ -224,7 +229,18 @@ class CapsLib:
         f("fm_wide_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
         f("kmer_workspace_bytes").restype = _ci
         f("kmer_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
+        for name in ("lpf_workspace_bytes", "lz77_workspace_bytes"):
+            f(name).restype = _ci
+            f(name).argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
         for sfx in ("u32", "u64"):
+            f(f"lpf_{sfx}").restype = _ci
+            f(f"lpf_{sfx}").argtypes = [_vp, _vp, _u64, _vp, _vp, _ci]
+            f(f"lpf_device_{sfx}").restype = _ci
+            f(f"lpf_device_{sfx}").argtypes = [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp]
+            f(f"lz77_{sfx}").restype = _ci
+            f(f"lz77_{sfx}").argtypes = [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _ci]
+            f(f"lz77_device_{sfx}").restype = _ci
+            f(f"lz77_device_{sfx}").argtypes = [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64, _vp]
             f(f"kmers_{sfx}").restype = _ci
             f(f"kmers_{sfx}").argtypes = [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _u64, ctypes.POINTER(_u64), _ci]
             f(f"kmers_device_{sfx}").restype = _ci
@@ -794,6 +810,65 @@ class CapsLib:
         self._check(self._f(f"kmer_census_device_{sfx}")(dSA_ptr or None, dLCP_ptr or None, n, max_k, distinct.ctypes.data,
                                                          unique.ctypes.data, dWS_ptr or None, ws_bytes, stream or None))
         return distinct, unique
+
+    # ------------------------------------------------------------------ LPF and LZ77 (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP")
+    def lpf_workspace_bytes(self, n: int, idx_bits: int = 32) -> int:
+        out = _u64(0)
+        self._check(self._f("lpf_workspace_bytes")(n, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    def lz77_workspace_bytes(self, n: int, idx_bits: int = 32) -> int:
+        out = _u64(0)
+        self._check(self._f("lz77_workspace_bytes")(n, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    def lpf(self, SA, LCP, idx_bits: int | None = None, device: int = 0):
+        """(LPF, Prev) in text order, in the index dtype: LPF[i] = the longest prefix of T[i:] that also starts at some j < i, Prev[i]
+        = such a j (all ones where LPF[i] = 0)."""
+        SA, LCP, n, sfx = self._sa_lcp(SA, LCP, idx_bits)
+        LPF = np.zeros(n, dtype=SA.dtype)
+        Prev = np.full(n, np.iinfo(SA.dtype).max, dtype=SA.dtype)
+        self._check(self._f(f"lpf_{sfx}")(SA.ctypes.data if n else None, LCP.ctypes.data if n else None, n, LPF.ctypes.data if n else None,
+                                          Prev.ctypes.data if n else None, device))
+        return LPF, Prev
+
+    def lz77(self, SA, LCP, idx_bits: int | None = None, device: int = 0) -> np.ndarray:
+        """The LZ77 factorization as a structured array (LZ_DTYPE: pos, len, src) in text order; src = LZ_LITERAL: a literal of one
+        byte.  One host call (arrays up, lpf, count, write) into a buffer of min(n, n / 8 + 1024) records, which holds the parse of any
+        text whose phrases average 8 bytes or more; only where it does not, a second call with the exact number, which uploads the arrays
+        and runs lpf again (a caller with the arrays on the device uses lpf_device and lz77_device and pays for lpf once)."""
+        SA, LCP, n, sfx = self._sa_lcp(SA, LCP, idx_bits)
+        found = _u64(0)
+        args = (SA.ctypes.data if n else None, LCP.ctypes.data if n else None, n)
+        f = self._f(f"lz77_{sfx}")
+        rec = np.zeros(min(n, n // 8 + 1024), dtype=LZ_DTYPE)
+        rc = f(*args, rec.ctypes.data if rec.size else None, rec.size, ctypes.byref(found), device)
+        if rc != 0 and found.value > rec.size:               # the buffer was too small: the number is valid, nothing was written
+            rec = np.zeros(found.value, dtype=LZ_DTYPE)
+            rc = f(*args, rec.ctypes.data, rec.size, ctypes.byref(found), device)
+        self._check(rc)
+        return rec[:found.value].copy() if found.value < rec.size else rec
+
+    def lpf_device(self, dSA_ptr: int, dLCP_ptr: int, n: int, dLPF_ptr: int = 0, dPrev_ptr: int = 0, dWS_ptr: int = 0, ws_bytes: int = 0,
+                   idx_bits: int = 32, stream: int = 0) -> None:
+        """Device arrays -> LPF and Prev (n entries of the index width each, text order; 0: not written)."""
+        sfx, _ = _sfx(idx_bits)
+        self._check(self._f(f"lpf_device_{sfx}")(dSA_ptr or None, dLCP_ptr or None, n, dLPF_ptr or None, dPrev_ptr or None, dWS_ptr or None,
+                                                 ws_bytes, stream or None))
+
+    def lz77_device(self, dLPF_ptr: int, dPrev_ptr: int, n: int, dRecords_ptr: int = 0, capacity: int = 0, dWS_ptr: int = 0,
+                    ws_bytes: int = 0, idx_bits: int = 32, stream: int = 0) -> int:
+        """Device LPF and Prev -> the number of phrases; dRecords_ptr 0: the counting call, else `capacity` 24-byte records are written
+        there.  More phrases than capacity: CapsSaError (code -1) whose n_phrases attribute holds their number."""
+        sfx, _ = _sfx(idx_bits)
+        found = _u64(0)
+        rc = self._f(f"lz77_device_{sfx}")(dLPF_ptr or None, dPrev_ptr or None, n, dRecords_ptr or None, capacity, ctypes.byref(found),
+                                           dWS_ptr or None, ws_bytes, stream or None)
+        if rc != 0:
+            err = CapsSaError(rc, self._f("last_error")().decode(errors="replace"))
+            err.n_phrases = found.value
+            raise err
+        return found.value
 
     # ------------------------------------------------------------------ kernel-level entry points
     def sort_suffixes(self, T, idx, idx_bits: int = 32, device: int = 0):

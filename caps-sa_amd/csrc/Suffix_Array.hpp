@@ -20,11 +20,14 @@
 //    its n-byte buffer is allocated by the first construct_bwt(), so construct() callers pay nothing for it.
 //  * kmers() / kmer_spectrum() / kmer_census() (not in the reference): the k-mer table, spectrum and census of the text from SA() and LCP()
 //    after a full-context construct() (include/caps_sa_hip.h "k-mers from SA and LCP").
+//  * lpf() / lz77() (not in the reference): the longest-previous-factor array with a previous occurrence for every position, and the LZ77
+//    factorization, from SA() and LCP() after a full-context construct() (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP").
 //  * the free function inverse_bwt() (not in the reference): the text back from (BWT, primary).
 //  * the class FM_Index (not in the reference either): count, locate, matching statistics, MEMs and extract over (BWT, primary) and a sample of the SA.
 #ifndef CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 #define CAPS_SA_AMD_SUFFIX_ARRAY_HPP
 
+#include <algorithm>
 #include <cstdint>
 #include <cstddef>
 #include <cstdlib>
@@ -168,6 +171,38 @@ public:
         if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_kmer_census: ") + caps_sa_hip_last_error());
     }
 
+    // ---- LPF and LZ77 from SA and LCP (include/caps_sa_hip.h; not in the reference).  After a full-context construct() / construct_bwt():
+    // with max_context set these throw std::invalid_argument.  On devices()[0].
+    struct Phrase { uint64_t pos, len, src; };                 // the ABI's 24-byte record: T()[src .. src + len), or the byte T()[pos] where src == literal
+    static constexpr uint64_t literal = ~static_cast<uint64_t>(0);
+    // LPF[i] = the longest prefix of T()[i ..) that also starts at some j < i, Prev[i] = such a j (all ones where LPF[i] = 0), text order
+    void lpf(std::vector<idx_t>& LPF, std::vector<idx_t>& Prev) const
+    {
+        lz_arrays_ok("lpf");
+        LPF.assign(static_cast<std::size_t>(n_), 0);
+        Prev.assign(static_cast<std::size_t>(n_), static_cast<idx_t>(~static_cast<idx_t>(0)));
+        const int rc = std::is_same<idx_t, uint32_t>::value
+            ? caps_sa_hip_lpf_u32(reinterpret_cast<const uint32_t*>(SA_), reinterpret_cast<const uint32_t*>(LCP_), n_, reinterpret_cast<uint32_t*>(LPF.data()), reinterpret_cast<uint32_t*>(Prev.data()), devices_[0])
+            : caps_sa_hip_lpf_u64(reinterpret_cast<const uint64_t*>(SA_), reinterpret_cast<const uint64_t*>(LCP_), n_, reinterpret_cast<uint64_t*>(LPF.data()), reinterpret_cast<uint64_t*>(Prev.data()), devices_[0]);
+        if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_lpf: ") + caps_sa_hip_last_error());
+    }
+    // the phrases in text order.  One call (arrays up, lpf, count, write) into room for min(n, n / 8 + 1024) records, enough wherever the
+    // phrases average 8 bytes or more; only where it is not, a second call with the exact number (which runs lpf again)
+    std::vector<Phrase> lz77() const
+    {
+        lz_arrays_ok("lz77");
+        static_assert(sizeof(Phrase) == 24, "the ABI's record");
+        const uint64_t n = static_cast<uint64_t>(n_);
+        uint64_t z = 0;
+        std::vector<Phrase> out(static_cast<std::size_t>(std::min<uint64_t>(n, n / 8 + 1024)));
+        if (!lz77_call(out.empty() ? nullptr : out.data(), out.size(), &z)) {
+            out.assign(static_cast<std::size_t>(z), Phrase{});
+            if (!lz77_call(out.data(), z, &z)) throw std::runtime_error(std::string("caps_sa_hip_lz77: ") + caps_sa_hip_last_error());
+        }
+        out.resize(static_cast<std::size_t>(z));
+        return out;
+    }
+
     // Reference: src/Suffix_Array.cpp:497-509 -- u64 n, then SA, then LCP, native endianness.
     void dump(std::ofstream& output)
     {
@@ -192,6 +227,22 @@ private:
             ? caps_sa_hip_kmers_u32(reinterpret_cast<const uint32_t*>(SA_), reinterpret_cast<const uint32_t*>(LCP_), n_, k, min_count, max_count, records, capacity, found, devices_[0])
             : caps_sa_hip_kmers_u64(reinterpret_cast<const uint64_t*>(SA_), reinterpret_cast<const uint64_t*>(LCP_), n_, k, min_count, max_count, records, capacity, found, devices_[0]);
         if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_kmers: ") + caps_sa_hip_last_error());
+    }
+
+    void lz_arrays_ok(const char* what) const
+    {
+        if (max_context_ != 0 && max_context_ < n_)
+            throw std::invalid_argument(std::string("Suffix_Array::") + what + ": LPF and LZ77 need a full-context suffix array (max_context is set)");
+    }
+    // false: the buffer was too small and *z says how many records there are; any other failure throws
+    bool lz77_call(void* records, uint64_t capacity, uint64_t* z) const
+    {
+        const int rc = std::is_same<idx_t, uint32_t>::value
+            ? caps_sa_hip_lz77_u32(reinterpret_cast<const uint32_t*>(SA_), reinterpret_cast<const uint32_t*>(LCP_), n_, records, capacity, z, devices_[0])
+            : caps_sa_hip_lz77_u64(reinterpret_cast<const uint64_t*>(SA_), reinterpret_cast<const uint64_t*>(LCP_), n_, records, capacity, z, devices_[0]);
+        if (rc != CAPS_SA_OK && records && *z > capacity) return false;
+        if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_lz77: ") + caps_sa_hip_last_error());
+        return true;
     }
 
     const char* const T_;

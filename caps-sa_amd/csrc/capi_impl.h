@@ -2954,6 +2954,249 @@ int kmer_census_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint32_t max
     });
 }
 
+// ---- LPF and LZ77 from SA and LCP (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP"; kernels.h lpf_* / lz_*) ------------------------
+// lpf workspace: tab[2 * LPF_MAX_LEVELS + 2] (offset, nodes of every level) | bad | sumSA[nodes] | sumLCP[nodes], nodes = all levels.
+struct LpfPlan {
+    uint64_t n_tiles = 0, nodes = 0;
+    uint32_t top = 0;                                      // the level that is one node
+    uint64_t tab[2 * LPF_MAX_LEVELS + 2] = {};
+    size_t off_tab = 0, off_bad = 0, off_sa = 0, off_lcp = 0, bytes = 0;
+};
+inline LpfPlan lpf_plan(uint64_t n, size_t w)
+{
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    LpfPlan p;
+    p.n_tiles = (n + LPF_TILE - 1) / LPF_TILE;
+    uint64_t cnt = n;
+    do {
+        cnt = (cnt + LPF_F - 1) / LPF_F;
+        ++p.top;
+        p.tab[2 * p.top] = p.nodes;
+        p.tab[2 * p.top + 1] = cnt;
+        p.nodes += cnt;
+    } while (cnt > 1 && p.top + 1 < LPF_MAX_LEVELS);
+    p.off_tab = 0;
+    p.off_bad = up(sizeof(p.tab));
+    p.off_sa = p.off_bad + 256;
+    p.off_lcp = p.off_sa + up(p.nodes * w);
+    p.bytes = p.off_lcp + up(p.nodes * w);
+    return p;
+}
+// lz77 workspace: ex[n] | gx[n_groups * LZ_SPEC] (index width) | gentry[n_groups] | entry[n_tiles] | cnt[n_tiles + 1] | total, 64-bit words
+struct LzPlan {
+    uint64_t n_tiles = 0, n_groups = 0;
+    size_t off_ex = 0, off_gx = 0, off_gentry = 0, off_entry = 0, off_cnt = 0, off_tot = 0, bytes = 0;
+};
+inline LzPlan lz_plan(uint64_t n, size_t w)
+{
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    LzPlan p;
+    p.n_tiles = (n + LZ_TILE - 1) / LZ_TILE;
+    p.n_groups = (n + LZ_GPOS - 1) / LZ_GPOS;
+    p.off_ex = 0;
+    p.off_gx = up(n * w);
+    p.off_gentry = p.off_gx + up(p.n_groups * LZ_SPEC * w);
+    p.off_entry = p.off_gentry + up(p.n_groups * 8);
+    p.off_cnt = p.off_entry + up(p.n_tiles * 8);
+    p.off_tot = p.off_cnt + up((p.n_tiles + 1) * 8);
+    p.bytes = p.off_tot + 256;
+    return p;
+}
+inline int lz_ws_args(uint64_t n, int idx_bytes, uint64_t* bytes)
+{
+    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
+    return CAPS_SA_OK;
+}
+inline int lpf_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
+{
+    if (int rc = lz_ws_args(n, idx_bytes, bytes)) return rc;
+    *bytes = lpf_plan(n, (size_t)idx_bytes).bytes + 256;
+    return CAPS_SA_OK;
+}
+inline int lz77_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
+{
+    if (int rc = lz_ws_args(n, idx_bytes, bytes)) return rc;
+    *bytes = lz_plan(n, (size_t)idx_bytes).bytes + 256;
+    return CAPS_SA_OK;
+}
+// the caller's workspace aligned up (null: one of the call's own); `need` was checked by lz_check_ws before
+inline int lz_check_ws(void* workspace, uint64_t workspace_bytes, size_t need, const char* which)
+{
+    if (!workspace) return CAPS_SA_OK;
+    uint64_t usable = 0;
+    kmer_align_ws(workspace, workspace_bytes, usable);
+    if (usable < need) return fail(CAPS_SA_EINVAL, which);
+    return CAPS_SA_OK;
+}
+inline char* lz_ws(DevAllocs& da, void* workspace, uint64_t workspace_bytes, size_t need)
+{
+    uint64_t usable = 0;
+    if (workspace) return kmer_align_ws(workspace, workspace_bytes, usable);
+    return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(da.get<char>(need + 256)) + 255) & ~uintptr_t(255));
+}
+
+// kmer_check_arrays' checks with messages that name this call's arrays
+template <typename idx_t> int lz_check_arrays(const void* a, const void* b, uint64_t n, const char* null_msg)
+{
+    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
+    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
+    if (n && (!a || !b)) return fail(CAPS_SA_EINVAL, null_msg);
+    return CAPS_SA_OK;
+}
+
+// n >= 1, dLPF or dPrev non-null
+template <typename idx_t>
+int run_lpf(Backend& be, const idx_t* dSA, const idx_t* dLCP, uint64_t n, idx_t* dLPF, idx_t* dPrev, char* ws)
+{
+    const LpfPlan p = lpf_plan(n, sizeof(idx_t));
+    uint64_t* tab = reinterpret_cast<uint64_t*>(ws + p.off_tab);
+    uint32_t* bad = reinterpret_cast<uint32_t*>(ws + p.off_bad);
+    idx_t* sumSA = reinterpret_cast<idx_t*>(ws + p.off_sa);
+    idx_t* sumLCP = reinterpret_cast<idx_t*>(ws + p.off_lcp);
+    be.h2d(tab, p.tab, sizeof(p.tab));
+    be.memset(bad, 0, sizeof(uint32_t));
+    const uint32_t tg = capped_grid(std::min<uint64_t>(p.n_tiles, 1u << 20), FM_NT);
+    CAPS_LAUNCH((lpf_block_kernel<idx_t>), tg, FM_NT, be, dSA, dLCP, n, p.n_tiles, p.tab[3], sumSA, sumLCP);
+    for (uint32_t lev = 2; lev <= p.top; ++lev) {
+        const uint64_t n_par = p.tab[2 * lev + 1];
+        const uint32_t g = capped_grid(std::min<uint64_t>((n_par + FM_NT - 1) / FM_NT, 1u << 16), FM_NT);
+        CAPS_LAUNCH((lpf_up_kernel<idx_t>), g, FM_NT, be, sumSA, sumLCP, p.tab[2 * lev - 2], p.tab[2 * lev - 1], p.tab[2 * lev], n_par);
+    }
+    CAPS_LAUNCH((lpf_tile_kernel<idx_t>), tg, FM_NT, be, dSA, dLCP, n, p.n_tiles, p.tab[3], (const idx_t*)sumSA, (const idx_t*)sumLCP,
+                (const uint64_t*)tab, p.top, dLPF, dPrev, bad);
+    uint32_t is_bad = 0;
+    be.d2h(&is_bad, bad, sizeof(uint32_t));
+    be.sync();
+    if (is_bad) return fail(CAPS_SA_EINVAL, "not a suffix array: a value of SA is n or more");
+    return CAPS_SA_OK;
+}
+
+// the parse of (dLPF, dPrev): *found always; with dRec the records.  counted: the workspace still holds entry[] and the scanned
+// cnt[] of a counting call on the same arrays (the host form's second call), and *found its result.
+template <typename idx_t>
+int run_lz77(Backend& be, const idx_t* dLPF, const idx_t* dPrev, uint64_t n, void* dRec, uint64_t capacity, uint64_t* found, char* ws,
+             bool counted = false)
+{
+    if (!counted) *found = 0;
+    if (n == 0) return CAPS_SA_OK;
+    const LzPlan p = lz_plan(n, sizeof(idx_t));
+    idx_t* ex = reinterpret_cast<idx_t*>(ws + p.off_ex);
+    idx_t* gx = reinterpret_cast<idx_t*>(ws + p.off_gx);
+    uint64_t* gentry = reinterpret_cast<uint64_t*>(ws + p.off_gentry);
+    uint64_t* entry = reinterpret_cast<uint64_t*>(ws + p.off_entry);
+    uint64_t* cnt = reinterpret_cast<uint64_t*>(ws + p.off_cnt);
+    uint64_t* tot = reinterpret_cast<uint64_t*>(ws + p.off_tot);
+    const uint32_t tg = capped_grid(std::min<uint64_t>(p.n_tiles, 1u << 20), FM_NT);
+    if (!counted) {
+        CAPS_LAUNCH((lz_exit_kernel<idx_t>), tg, FM_NT, be, dLPF, n, p.n_tiles, ex);
+        const uint32_t gg = capped_grid(std::min<uint64_t>((p.n_groups * LZ_SPEC + FM_NT - 1) / FM_NT, 1u << 16), FM_NT);
+        CAPS_LAUNCH((lz_group_kernel<idx_t>), gg, FM_NT, be, (const idx_t*)ex, n, p.n_groups, gx);
+        CAPS_LAUNCH((lz_hop_kernel<idx_t>), 1, FM_NT, be, (const idx_t*)ex, (const idx_t*)gx, n, p.n_groups, gentry);
+        const uint32_t eg = capped_grid(std::min<uint64_t>((p.n_groups + FM_NT - 1) / FM_NT, 1u << 16), FM_NT);
+        CAPS_LAUNCH((lz_entry_kernel<idx_t>), eg, FM_NT, be, (const idx_t*)ex, n, p.n_tiles, p.n_groups, (const uint64_t*)gentry, entry);
+        CAPS_LAUNCH((lz_walk_kernel<idx_t, LZ_COUNT>), tg, FM_NT, be, dLPF, dPrev, n, p.n_tiles, (const uint64_t*)entry, cnt, (uint64_t*)nullptr,
+                    (uint64_t)0);
+        CAPS_LAUNCH(fm_scan_kernel, 1, FM_NT, be, cnt, p.n_tiles, 0u, 1u, tot);
+        be.d2h(found, tot, sizeof(uint64_t));
+        be.sync();
+    }
+    if (!dRec) return CAPS_SA_OK;
+    if (*found > capacity) return fail(CAPS_SA_EINVAL, "capacity is smaller than the number of phrases (*n_phrases; a call with dRecords = NULL counts them)");
+    CAPS_LAUNCH((lz_walk_kernel<idx_t, LZ_WRITE>), tg, FM_NT, be, dLPF, dPrev, n, p.n_tiles, (const uint64_t*)entry, cnt,
+                static_cast<uint64_t*>(dRec), capacity);
+    be.sync();
+    return CAPS_SA_OK;
+}
+
+template <typename idx_t>
+int lpf_device(const void* dSA, const void* dLCP, uint64_t n, void* dLPF, void* dPrev, void* workspace, uint64_t workspace_bytes, void* stream)
+{
+    if (int rc = lz_check_arrays<idx_t>(dSA, dLCP, n, "dSA or dLCP is null")) return rc;
+    if (n && !dLPF && !dPrev) return fail(CAPS_SA_EINVAL, "dLPF and dPrev are both null");
+    if (int rc = lz_check_ws(workspace, workspace_bytes, lpf_plan(n, sizeof(idx_t)).bytes, "workspace too small (caps_sa_hip_lpf_workspace_bytes)")) return rc;
+    if (n == 0) return CAPS_SA_OK;
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);
+        char* ws = lz_ws(da, workspace, workspace_bytes, lpf_plan(n, sizeof(idx_t)).bytes);
+        return run_lpf<idx_t>(be, static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), n, static_cast<idx_t*>(dLPF),
+                              static_cast<idx_t*>(dPrev), ws);
+    });
+}
+template <typename idx_t>
+int lz77_device(const void* dLPF, const void* dPrev, uint64_t n, void* dRec, uint64_t capacity, uint64_t* n_phrases, void* workspace,
+                uint64_t workspace_bytes, void* stream)
+{
+    if (int rc = lz_check_arrays<idx_t>(dLPF, dPrev, n, "dLPF or dPrev is null")) return rc;
+    if (!n_phrases) return fail(CAPS_SA_EINVAL, "n_phrases is null");
+    if (reinterpret_cast<uintptr_t>(dRec) & 7u) return fail(CAPS_SA_EINVAL, "dRecords must be 8-byte aligned");
+    if (int rc = lz_check_ws(workspace, workspace_bytes, lz_plan(n, sizeof(idx_t)).bytes, "workspace too small (caps_sa_hip_lz77_workspace_bytes)")) return rc;
+    if (n == 0) { *n_phrases = 0; return CAPS_SA_OK; }
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);
+        char* ws = lz_ws(da, workspace, workspace_bytes, lz_plan(n, sizeof(idx_t)).bytes);
+        return run_lz77<idx_t>(be, static_cast<const idx_t*>(dLPF), static_cast<const idx_t*>(dPrev), n, dRec, capacity, n_phrases, ws);
+    });
+}
+template <typename idx_t>
+int lpf_host(const idx_t* SA, const idx_t* LCP, uint64_t n, idx_t* LPF, idx_t* Prev, int device)
+{
+    if (int rc = lz_check_arrays<idx_t>(SA, LCP, n, "SA or LCP is null")) return rc;
+    if (n && !LPF && !Prev) return fail(CAPS_SA_EINVAL, "LPF and Prev are both null");
+    if (n == 0) return CAPS_SA_OK;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        Backend be(nullptr);
+        DevAllocs da(be);
+        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
+        idx_t* dLPF = LPF ? da.get<idx_t>(n) : nullptr;
+        idx_t* dPrev = Prev ? da.get<idx_t>(n) : nullptr;
+        // slots whose position never occurs in SA keep what they held
+        if (LPF) be.h2d(dLPF, LPF, n * sizeof(idx_t));
+        if (Prev) be.h2d(dPrev, Prev, n * sizeof(idx_t));
+        char* ws = lz_ws(da, nullptr, 0, lpf_plan(n, sizeof(idx_t)).bytes);
+        const int rc = run_lpf<idx_t>(be, a.sa, a.lcp, n, dLPF, dPrev, ws);
+        if (LPF) be.d2h(LPF, dLPF, n * sizeof(idx_t));
+        if (Prev) be.d2h(Prev, dPrev, n * sizeof(idx_t));
+        be.sync();
+        return rc;
+    });
+}
+template <typename idx_t>
+int lz77_host(const idx_t* SA, const idx_t* LCP, uint64_t n, void* records, uint64_t capacity, uint64_t* n_phrases, int device)
+{
+    if (int rc = lz_check_arrays<idx_t>(SA, LCP, n, "SA or LCP is null")) return rc;
+    if (!n_phrases) return fail(CAPS_SA_EINVAL, "n_phrases is null");
+    if (reinterpret_cast<uintptr_t>(records) & 7u) return fail(CAPS_SA_EINVAL, "records must be 8-byte aligned");
+    if (n == 0) { *n_phrases = 0; return CAPS_SA_OK; }
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        Backend be(nullptr);
+        DevAllocs da(be);
+        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
+        idx_t* dLPF = da.get<idx_t>(n);
+        idx_t* dPrev = da.get<idx_t>(n);
+        be.memset(dLPF, 0, n * sizeof(idx_t));              // a position that SA never names parses as a literal
+        be.memset(dPrev, 0xFF, n * sizeof(idx_t));
+        char* ws = lz_ws(da, nullptr, 0, std::max(lpf_plan(n, sizeof(idx_t)).bytes, lz_plan(n, sizeof(idx_t)).bytes));
+        if (int rc = run_lpf<idx_t>(be, a.sa, a.lcp, n, dLPF, dPrev, ws)) return rc;
+        if (int rc = run_lz77<idx_t>(be, dLPF, dPrev, n, nullptr, 0, n_phrases, ws)) return rc;
+        if (!records) return CAPS_SA_OK;
+        if (*n_phrases > capacity) return fail(CAPS_SA_EINVAL, "capacity is smaller than the number of phrases (*n_phrases; a call with records = NULL counts them)");
+        const uint64_t found = *n_phrases;
+        uint64_t* dRec = da.get<uint64_t>(3 * found);
+        if (int rc = run_lz77<idx_t>(be, dLPF, dPrev, n, dRec, found, n_phrases, ws, true)) return rc;    // entry[] and cnt[] are still there
+        be.d2h(records, dRec, found * 24);
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+
 // Text on the device for the kernel-level entry points.
 struct DevText {
     uint8_t* raw = nullptr;
@@ -3452,6 +3695,23 @@ int CAPS_API(kmer_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) {
 CAPS_DEFINE_KMER(u32, uint32_t)
 CAPS_DEFINE_KMER(u64, uint64_t)
 #undef CAPS_DEFINE_KMER
+int CAPS_API(lpf_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::lpf_workspace_bytes(n, idx_bytes, bytes); }
+int CAPS_API(lz77_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::lz77_workspace_bytes(n, idx_bytes, bytes); }
+#define CAPS_DEFINE_LZ(SFX, IDX)                                                                                            \
+    int CAPS_API(lpf_device_##SFX)(const void* dSA, const void* dLCP, uint64_t n, void* dLPF, void* dPrev, void* ws,        \
+                                   uint64_t ws_bytes, void* stream)                                                         \
+    { return caps::lpf_device<IDX>(dSA, dLCP, n, dLPF, dPrev, ws, ws_bytes, stream); }                                      \
+    int CAPS_API(lpf_##SFX)(const IDX* SA, const IDX* LCP, uint64_t n, IDX* LPF, IDX* Prev, int device)                     \
+    { return caps::lpf_host<IDX>(SA, LCP, n, LPF, Prev, device); }                                                          \
+    int CAPS_API(lz77_device_##SFX)(const void* dLPF, const void* dPrev, uint64_t n, void* dRecords, uint64_t capacity,     \
+                                    uint64_t* n_phrases, void* ws, uint64_t ws_bytes, void* stream)                         \
+    { return caps::lz77_device<IDX>(dLPF, dPrev, n, dRecords, capacity, n_phrases, ws, ws_bytes, stream); }                 \
+    int CAPS_API(lz77_##SFX)(const IDX* SA, const IDX* LCP, uint64_t n, void* records, uint64_t capacity,                   \
+                             uint64_t* n_phrases, int device)                                                               \
+    { return caps::lz77_host<IDX>(SA, LCP, n, records, capacity, n_phrases, device); }
+CAPS_DEFINE_LZ(u32, uint32_t)
+CAPS_DEFINE_LZ(u64, uint64_t)
+#undef CAPS_DEFINE_LZ
 
 int CAPS_API(fm_mems_workspace_bytes)(uint64_t total_pattern_bytes, uint64_t q, uint64_t* bytes)
 { return caps::fm_mems_workspace_bytes(total_pattern_bytes, q, bytes); }

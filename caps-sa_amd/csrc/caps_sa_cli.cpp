@@ -3,6 +3,7 @@
 //
 //     caps_sa <input_path> <output_path> [subproblem-count] [bounded-context] [--pretty-print] [--gpus N] [--bwt PATH]
 //     caps_sa <input_path> <output_path> [subproblem-count] [--kmers K PATH [--min-count A] [--max-count B]] [--kmer-spectrum K PATH]
+//     caps_sa <input_path> <output_path> [subproblem-count] [--lz77 PATH]
 //     caps_sa --inverse-bwt IN.bwt OUT
 //     caps_sa <input_path> <output_path> [subproblem-count] --fm-index PATH [--fm-sample S] [--fm-text-sample T]
 //     caps_sa <input_path> <output_path> [subproblem-count] --raw [--bwt PATH] [--fm-index PATH [--fm-sample S]]
@@ -19,6 +20,10 @@
 // * --kmer-spectrum K PATH (not in the reference; on the build line): the multiplicity spectrum to PATH, one line "c number" for
 //   c = 1 .. 1024: the distinct K-mers that occur c times (the last line: 1024 times or more).  Allowed with --raw; refused with a
 //   bounded context;
+// * --lz77 PATH (not in the reference; on the build line): after the SA / LCP output, the LZ77 factorization of the text as built
+//   (remapped, or with --raw the file's own bytes) to PATH (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP"): one line
+//   "pos<TAB>len<TAB>src" per phrase in text order, the phrase being a copy of len bytes from position src (the two may overlap); a
+//   literal is "pos<TAB>0<TAB>byte value in decimal", so the file alone decodes to the text.  Refused with a bounded context;
 // * --raw (not in the reference; on the build line only): the text as given, no remap to {A,C,G,T} -- SA, LCP and --bwt are those of
 //   the file's own bytes, and --fm-index PATH writes the wide format (include/caps_sa_hip.h "FM-index: the wide format") for 1 .. 256
 //   distinct bytes.  --fm-search and --fm-mems tell a wide index by its magic and take the pattern lines as bytes, unremapped (a
@@ -79,6 +84,10 @@
 #if defined(caps_sa_hip_build_multi_u32) && !defined(caps_sa_hip_kmers_u32)
 #define CAPS_CLI_NO_KMERS 1
 #endif
+// ... and the same for a driver that predates the LZ77 entry points: the CLI without --lz77.
+#if defined(caps_sa_hip_build_multi_u32) && !defined(caps_sa_hip_lz77_u32)
+#define CAPS_CLI_NO_LZ 1
+#endif
 
 static bool read_input(const std::string& path, std::string& text)
 {
@@ -113,7 +122,7 @@ struct KmerJob {
 template <typename idx_t>
 static int run(const std::string& text, const std::string& out_path, size_t p, size_t ctx, bool pretty, const std::vector<int>& devices,
                const std::string& bwt_path, const std::string& fm_path = std::string(), uint32_t fm_sample = 32, uint32_t fm_text_sample = 0, bool raw = false,
-               const KmerJob& km = KmerJob())
+               const KmerJob& km = KmerJob(), const std::string& lz_path = std::string())
 {
     if (p > std::numeric_limits<idx_t>::max()) { std::cerr << "subproblem-count does not fit the index type\n"; return EXIT_FAILURE; }
     // the bounded-context mode replays the reference's merge history, one GPU thread per merge node -- the top levels
@@ -177,6 +186,19 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
         if (!out) { std::cerr << km.spectrum_path << " : cannot open for writing\n"; return EXIT_FAILURE; }
         for (size_t c = 1; c <= 1024; ++c) out << c << ' ' << hist[c] << '\n';
         if (!out) return EXIT_FAILURE;
+    }
+#endif
+#ifndef CAPS_CLI_NO_LZ
+    if (!lz_path.empty()) {
+        const auto parse = suf_arr.lz77();
+        std::ofstream out(lz_path, std::ios::binary);
+        if (!out) { std::cerr << lz_path << " : cannot open for writing\n"; return EXIT_FAILURE; }
+        for (const auto& ph : parse) {
+            if (ph.src == suf_arr.literal) out << ph.pos << "\t0\t" << static_cast<unsigned>(static_cast<unsigned char>(text[ph.pos])) << '\n';
+            else out << ph.pos << '\t' << ph.len << '\t' << ph.src << '\n';
+        }
+        if (!out) return EXIT_FAILURE;
+        std::cerr << "LZ77: " << parse.size() << " phrases written.\n";
     }
 #endif
     return 0;
@@ -443,7 +465,8 @@ int main(int argc, char* argv[])
     size_t gpus = 1, fm_sample = 32, fm_text_sample = 0;
     std::string bwt_path, fm_path;
     KmerJob km;
-    bool kmers = false, spectrum = false, min_count_given = false, max_count_given = false;
+    std::string lz_path;                                   // --lz77 (empty: not asked for)
+    bool kmers = false, spectrum = false, min_count_given = false, max_count_given = false, lz = false;
     for (int i = 1; i < argc; ++i) {
         if (std::strcmp(argv[i], "--pretty-print") == 0) pretty = true;
         else if (std::strcmp(argv[i], "--kmers") == 0 || std::strcmp(argv[i], "--kmer-spectrum") == 0) {
@@ -458,6 +481,12 @@ int main(int argc, char* argv[])
             if (table) { kmers = true; km.k = k; km.path = argv[i + 2]; }
             else { spectrum = true; km.spectrum_k = k; km.spectrum_path = argv[i + 2]; }
             i += 2;
+        }
+        else if (std::strcmp(argv[i], "--lz77") == 0) {
+            if (lz) { std::cerr << "--lz77: given twice\n"; return EXIT_FAILURE; }
+            if (i + 1 >= argc || std::strncmp(argv[i + 1], "--", 2) == 0) { std::cerr << "--lz77: usage: --lz77 PATH\n"; return EXIT_FAILURE; }
+            lz = true;
+            lz_path = argv[++i];
         }
         else if (std::strcmp(argv[i], "--min-count") == 0 || std::strcmp(argv[i], "--max-count") == 0) {
             const bool lo = std::strcmp(argv[i], "--min-count") == 0;
@@ -501,7 +530,7 @@ int main(int argc, char* argv[])
         std::cerr << "Usage: caps_sa <input_path> <output_path> <(optional)-subproblem-count> "
                      "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH> "
                      "<(optional)--fm-index PATH [--fm-sample S] [--fm-text-sample T]> <(optional)--raw> "
-                     "<(optional)--kmers K PATH [--min-count A] [--max-count B]> <(optional)--kmer-spectrum K PATH>\n"
+                     "<(optional)--kmers K PATH [--min-count A] [--max-count B]> <(optional)--kmer-spectrum K PATH> <(optional)--lz77 PATH>\n"
                      "       caps_sa --inverse-bwt IN.bwt OUT\n"
                      "       caps_sa --fm-search INDEX PATTERNS [--locate K]\n"
                      "       caps_sa --fm-mems INDEX PATTERNS [--min-len L]\n"
@@ -535,6 +564,17 @@ int main(int argc, char* argv[])
         struct stat sb;
         if (ctx != 0 && stat(pos[0].c_str(), &sb) == 0 && ctx < static_cast<size_t>(sb.st_size)) {
             std::cerr << opt << ": a bounded-context order (bounded-context " << ctx << ") is not a suffix array and has no k-mer table\n";
+            return EXIT_FAILURE;
+        }
+    }
+    // --lz77: the same manners
+#ifdef CAPS_CLI_NO_LZ
+    if (lz) { std::cerr << "--lz77: not built into this driver\n"; return EXIT_FAILURE; }
+#endif
+    if (lz) {
+        struct stat sb;
+        if (ctx != 0 && stat(pos[0].c_str(), &sb) == 0 && ctx < static_cast<size_t>(sb.st_size)) {
+            std::cerr << "--lz77: a bounded-context order (bounded-context " << ctx << ") is not a suffix array and has no LZ77 factorization\n";
             return EXIT_FAILURE;
         }
     }
@@ -580,8 +620,8 @@ int main(int argc, char* argv[])
 
     std::cerr << "Text length: " << text.size() << ".\n";
     try {
-        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km);
-        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km);
+        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path);
+        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path);
     } catch (const std::exception& e) {
         std::cerr << e.what() << "\n";
         return EXIT_FAILURE;

@@ -6794,4 +6794,520 @@ GLOBAL_FN LAUNCH_BOUNDS(FM_NT) kmer_census_kernel(KCTX const idx_t* __restrict__
     }
 }
 
+// ---- LPF and LZ77 from SA and LCP (capi_impl.h lpf_* / lz_*; include/caps_sa_hip.h "LPF and LZ77 from SA and LCP") -----------------------
+// For rank r with i = SA[r]: p = the nearest rank below r whose SA value is below i, q = the nearest above; LPF[i] = the larger of
+// min LCP(p, r] and min LCP(r, q].  A tree of fan-out LPF_F over the ranks holds (min SA, min LCP) of every node: level 1 = blocks of
+// LPF_F ranks, level 2 = tiles of LPF_F blocks, and so on up to one node.  A search walks outwards over the siblings of its node, folds
+// the min LCP of every node whose min SA >= i and climbs at the end of the group; the first node whose min SA < i holds the answer and
+// the search descends through it, one group per level.  That is at most LPF_F steps per level and direction for ANY permutation; inside
+// a tile the two lowest levels are in LDS.  A search ends early once its running minimum is 0 (left) or no larger than the left result
+// (right: it cannot win any more).
+//   lpf_block_kernel   level 1 from SA and LCP, coalesced 16-byte loads
+//   lpf_up_kernel      level l from level l - 1 (one thread per parent; the levels above 1 are a 64th of the one below each)
+//   lpf_tile_kernel    per tile: SA and LCP into LDS, the tile's block summaries beside them, one search pair per rank, two scattered
+//                      stores; a search that leaves the tile goes on in lpf_far over the levels in global memory
+// A value SA[r] >= n is never used as an index: the rank is skipped and *bad is raised.
+//   lz_exit_kernel     per tile of LZ_TILE positions: ex[s] = the first position at or beyond the tile's end that the chain
+//                      s -> s + len(s) reaches, by pointer doubling in LDS (the fixed point "the last chain position inside the tile")
+//   lz_group_kernel    the exits composed over groups of LZ_GROUP tiles, for the first LZ_SPEC positions of every group, one lane each
+//   lz_hop_kernel      one workgroup: the chain over the GROUPS, gentry[g] = where the parse enters group g (all-ones: it jumps over g);
+//                      the composed exits of LZ_BATCH groups are fetched side by side before the lane walks them
+//   lz_entry_kernel    one lane per group: from gentry[g] over the group's tiles, entry[t] = where the parse enters tile t
+//   lz_walk_kernel     per tile with an entry: block exits right to left in LDS (one lane per block), one lane hops the blocks, then
+//                      one lane per block walks at most LZ_BLOCK phrases: count / fm_scan_kernel / write, as kmer_run_kernel does
+#if CAPS_TILE_E >= 4096
+constexpr uint32_t LPF_SHIFT = 6;
+#else
+constexpr uint32_t LPF_SHIFT = 4;                                  // the small-tile emulation builds: blocks of 16, tiles of 256 ranks
+#endif
+constexpr uint32_t LPF_F = 1u << LPF_SHIFT;                        // fan-out of every level: ranks of a block, blocks of a tile
+constexpr uint32_t LPF_TILE = LPF_F * LPF_F;                       // 4096 ranks: SA + LCP of a tile are 32 KiB (u32) / 64 KiB (u64) of LDS
+constexpr uint32_t LPF_MAX_LEVELS = 16;                            // levels 1 .. 15 at most (n <= 2^60, fan-out >= 16)
+constexpr uint32_t LZ_BLOCK = LPF_F;
+constexpr uint32_t LZ_TILE = FM_NT * LZ_BLOCK;                     // 16,384 positions: one lane per block
+constexpr uint32_t LZ_GROUP = LPF_F;                               // tiles of a group: the second level of the hop
+constexpr uint64_t LZ_GPOS = (uint64_t)LZ_GROUP * LZ_TILE;         // 1,048,576 positions
+constexpr uint32_t LZ_SPEC = 64;                                   // composed exits kept per group: its first positions
+constexpr uint32_t LZ_BATCH = FM_NT;                               // groups fetched ahead at once
+constexpr uint32_t LZ_ROUNDS = LPF_SHIFT + 8;                      // log2(LZ_TILE)
+enum { LZ_COUNT = 0, LZ_WRITE = 1 };
+static_assert(LZ_TILE == (1u << LZ_ROUNDS) && LZ_TILE <= 32768, "a tile-relative position and LZ_TILE itself fit 16 bits");
+
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lpf_block_kernel(KCTX const idx_t* __restrict__ SA, const idx_t* __restrict__ LCP, uint64_t n, uint64_t n_tiles,
+                                                 uint64_t n_blocks, idx_t* __restrict__ sumSA, idx_t* __restrict__ sumLCP)
+{
+    constexpr uint32_t PER = KmerGeom<idx_t>::PER, CH = LPF_TILE / PER, CPB = LPF_F / PER;
+    constexpr idx_t TOP = (idx_t)~(idx_t)0;
+    SHARED_ARRAY(idx_t, cs, CH);
+    SHARED_ARRAY(idx_t, cl, CH);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t t0 = tile * LPF_TILE;
+        PAR(tid) {
+            for (uint32_t c = tid; c < CH; c += FM_NT) {
+                const uint64_t i0 = t0 + (uint64_t)c * PER;
+                idx_t ms = TOP, ml = 0;
+                if (i0 < n) {
+                    const KmerChunk<idx_t> s = kmer_load<idx_t>(SA, n, i0), l = kmer_load<idx_t>(LCP, n, i0);
+                    ml = TOP;
+                    UNROLL
+                    for (uint32_t j = 0; j < PER; ++j) {
+                        const bool in = i0 + j < n;
+                        ms = in && s.v[j] < ms ? s.v[j] : ms;
+                        const idx_t lv = in && i0 + j != 0 ? l.v[j] : (idx_t)0;      // LCP[0] and what lies behind the array count as 0
+                        ml = lv < ml ? lv : ml;
+                    }
+                }
+                cs[c] = ms;
+                cl[c] = ml;
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            for (uint32_t b = tid; b < LPF_F; b += FM_NT) {
+                const uint64_t g = tile * LPF_F + b;
+                if (g < n_blocks) {
+                    idx_t ms = TOP, ml = TOP;
+                    for (uint32_t c = 0; c < CPB; ++c) {
+                        const idx_t a = cs[b * CPB + c], d = cl[b * CPB + c];
+                        ms = a < ms ? a : ms;
+                        ml = d < ml ? d : ml;
+                    }
+                    sumSA[g] = ms;
+                    sumLCP[g] = ml;
+                }
+            }
+        }
+        SYNC();
+    }
+}
+
+// parents [0, n_par) at par_off from the children [0, n_child) at child_off of the same two arrays
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lpf_up_kernel(KCTX idx_t* __restrict__ sumSA, idx_t* __restrict__ sumLCP, uint64_t child_off, uint64_t n_child,
+                                              uint64_t par_off, uint64_t n_par)
+{
+    constexpr idx_t TOP = (idx_t)~(idx_t)0;
+    PAR(tid) {
+        for (uint64_t p = (uint64_t)K_BLOCK_IDX * FM_NT + tid; p < n_par; p += (uint64_t)K_GRID_DIM * FM_NT) {
+            const uint64_t c0 = p * LPF_F, c1 = std::min<uint64_t>(n_child, c0 + LPF_F);
+            idx_t ms = TOP, ml = TOP;
+            for (uint64_t c = c0; c < c1; ++c) {
+                const idx_t a = sumSA[child_off + c], d = sumLCP[child_off + c];
+                ms = a < ms ? a : ms;
+                ml = d < ml ? d : ml;
+            }
+            sumSA[par_off + p] = ms;
+            sumLCP[par_off + p] = ml;
+        }
+    }
+}
+
+// The search of value i beyond its tile: `pos` = its tile (a node of level 2), m = the minimum so far.  Ascends over the siblings at
+// levels 2 .. top, descends through the first node whose min SA < i.  tab[2 l] / tab[2 l + 1] = offset / nodes of level l.  Ends as
+// soon as m <= stop (found stays false: the caller's result is then 0).  found: val = the SA value, m = the minimum.
+template <typename idx_t, bool RIGHT>
+DEV_INLINE void lpf_far(const idx_t* __restrict__ SA, const idx_t* __restrict__ LCP, uint64_t n, const idx_t* __restrict__ sumSA,
+                        const idx_t* __restrict__ sumLCP, const uint64_t* __restrict__ tab, uint32_t top, uint64_t pos, idx_t i, idx_t stop,
+                        idx_t& m, bool& found, idx_t& val)
+{
+    uint32_t lev = 2;
+    uint64_t hit = 0;
+    bool have = false;
+    while (lev <= top && !have) {
+        const uint64_t off = tab[2 * lev], cnt = tab[2 * lev + 1];
+        const uint64_t lo = pos & ~(uint64_t)(LPF_F - 1), hi = std::min<uint64_t>(cnt, lo + LPF_F);
+        for (uint64_t k = 1; k < LPF_F; ++k) {
+            if (RIGHT ? pos + k >= hi : pos < lo + k) break;
+            const uint64_t j = RIGHT ? pos + k : pos - k;
+            if (sumSA[off + j] < i) { have = true; hit = j; break; }
+            const idx_t d = sumLCP[off + j];
+            m = d < m ? d : m;
+            if (m <= stop) return;
+        }
+        if (!have) { pos >>= LPF_SHIFT; ++lev; }
+    }
+    if (!have) return;
+    while (lev > 1) {                                                               // into the children at level lev - 1
+        --lev;
+        const uint64_t off = tab[2 * lev], cnt = tab[2 * lev + 1];
+        const uint64_t c0 = hit * LPF_F, c1 = std::min<uint64_t>(cnt, c0 + LPF_F);
+        have = false;
+        for (uint64_t k = 0; c0 + k < c1; ++k) {
+            const uint64_t j = RIGHT ? c0 + k : c1 - 1 - k;
+            if (sumSA[off + j] < i) { have = true; hit = j; break; }
+            const idx_t d = sumLCP[off + j];
+            m = d < m ? d : m;
+            if (m <= stop) return;
+        }
+        if (!have) return;                                                          // (a summary and its children disagree: no answer)
+    }
+    const uint64_t c0 = hit * LPF_F, c1 = std::min<uint64_t>(n, c0 + LPF_F);        // the ranks of the block
+    for (uint64_t k = 0; c0 + k < c1; ++k) {
+        const uint64_t j = RIGHT ? c0 + k : c1 - 1 - k;
+        const idx_t s = SA[j], d = j ? LCP[j] : (idx_t)0;
+        if (RIGHT) {
+            m = d < m ? d : m;
+            if (m <= stop) return;
+            if (s < i) { found = true; val = s; return; }
+        } else {
+            if (s < i) { found = true; val = s; return; }
+            m = d < m ? d : m;
+            if (m <= stop) return;
+        }
+    }
+}
+
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lpf_tile_kernel(KCTX const idx_t* __restrict__ SA, const idx_t* __restrict__ LCP, uint64_t n, uint64_t n_tiles,
+                                                uint64_t n_blocks, const idx_t* __restrict__ sumSA, const idx_t* __restrict__ sumLCP,
+                                                const uint64_t* __restrict__ tab, uint32_t top, idx_t* __restrict__ LPF, idx_t* __restrict__ Prev,
+                                                uint32_t* __restrict__ bad)
+{
+    constexpr uint32_t PER = KmerGeom<idx_t>::PER, CH = LPF_TILE / PER;
+    constexpr idx_t TOP = (idx_t)~(idx_t)0;
+    SHARED_ARRAY(idx_t, sSA, LPF_TILE);
+    SHARED_ARRAY(idx_t, sLCP, LPF_TILE);
+    SHARED_ARRAY(idx_t, bSA, LPF_F);
+    SHARED_ARRAY(idx_t, bLCP, LPF_F);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t t0 = tile * LPF_TILE;
+        PAR(tid) {
+            for (uint32_t c = tid; c < CH; c += FM_NT) {
+                const uint64_t i0 = t0 + (uint64_t)c * PER;
+                KmerChunk<idx_t> s{}, l{};
+                if (i0 < n) {
+                    s = kmer_load<idx_t>(SA, n, i0);
+                    l = kmer_load<idx_t>(LCP, n, i0);
+                }
+                UNROLL
+                for (uint32_t j = 0; j < PER; ++j) {
+                    const bool in = i0 + j < n;
+                    sSA[c * PER + j] = in ? s.v[j] : TOP;                            // behind the array: never below i, and a 0 that ends the search
+                    sLCP[c * PER + j] = in && i0 + j != 0 ? l.v[j] : (idx_t)0;
+                }
+            }
+            for (uint32_t b = tid; b < LPF_F; b += FM_NT) {
+                const uint64_t g = tile * LPF_F + b;
+                bSA[b] = g < n_blocks ? sumSA[g] : TOP;
+                bLCP[b] = g < n_blocks ? sumLCP[g] : (idx_t)0;
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            for (uint32_t x = tid; x < LPF_TILE; x += FM_NT) {
+                if (t0 + x >= n) break;
+                const idx_t i = sSA[x];
+                if ((uint64_t)i >= n) { ATOMIC_MAX_U32(bad, 1u); continue; }
+                // left: p < r, min LCP(p, r]
+                idx_t m = sLCP[x], pv = TOP;
+                bool found = false;
+                if (m != 0) {
+                    bool out = true;                                                // no node below i seen yet, m still above 0
+                    uint32_t j = x;
+                    while (j & (LPF_F - 1)) {
+                        --j;
+                        if (sSA[j] < i) { found = true; pv = sSA[j]; out = false; break; }
+                        const idx_t d = sLCP[j];
+                        m = d < m ? d : m;
+                        if (m == 0) { out = false; break; }
+                    }
+                    uint32_t b = x >> LPF_SHIFT;
+                    while (out && b) {
+                        --b;
+                        if (bSA[b] < i) {
+                            out = false;
+                            for (j = (b + 1) * LPF_F; j-- > b * LPF_F;) {
+                                if (sSA[j] < i) { found = true; pv = sSA[j]; break; }
+                                const idx_t d = sLCP[j];
+                                m = d < m ? d : m;
+                                if (m == 0) break;
+                            }
+                        } else {
+                            const idx_t d = bLCP[b];
+                            m = d < m ? d : m;
+                            if (m == 0) out = false;
+                        }
+                    }
+                    if (out && tile) lpf_far<idx_t, false>(SA, LCP, n, sumSA, sumLCP, tab, top, tile, i, (idx_t)0, m, found, pv);
+                }
+                const idx_t left = found ? m : (idx_t)0;
+                // right: q > r, min LCP(r, q]; it wins only if it is larger than left
+                idx_t qv = TOP;
+                m = TOP;
+                found = false;
+                if (left != TOP) {
+                    bool out = true;
+                    uint32_t j = x;
+                    while ((j + 1) & (LPF_F - 1)) {
+                        ++j;
+                        const idx_t d = sLCP[j];
+                        m = d < m ? d : m;
+                        if (m <= left) { out = false; break; }
+                        if (sSA[j] < i) { found = true; qv = sSA[j]; out = false; break; }
+                    }
+                    uint32_t b = x >> LPF_SHIFT;
+                    while (out && b + 1 < LPF_F) {
+                        ++b;
+                        if (bSA[b] < i) {
+                            out = false;
+                            for (j = b * LPF_F; j < (b + 1) * LPF_F; ++j) {
+                                const idx_t d = sLCP[j];
+                                m = d < m ? d : m;
+                                if (m <= left) break;
+                                if (sSA[j] < i) { found = true; qv = sSA[j]; break; }
+                            }
+                        } else {
+                            const idx_t d = bLCP[b];
+                            m = d < m ? d : m;
+                            if (m <= left) out = false;
+                        }
+                    }
+                    if (out && tile + 1 < n_tiles) lpf_far<idx_t, true>(SA, LCP, n, sumSA, sumLCP, tab, top, tile, i, left, m, found, qv);
+                }
+                const idx_t right = found ? m : (idx_t)0;
+                idx_t len = 0, src = TOP;
+                if (right > left) { len = right; src = qv; }
+                else if (left > 0) { len = left; src = pv; }
+                if (LPF) LPF[i] = len;
+                if (Prev) Prev[i] = src;
+            }
+        }
+        SYNC();
+    }
+}
+
+// the phrase at position s (s < n): max(1, LPF[s]) clamped to the text's end
+HD uint64_t lz_len(uint64_t lpf, uint64_t n, uint64_t s) { return std::min<uint64_t>(lpf ? lpf : 1, n - s); }
+
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lz_exit_kernel(KCTX const idx_t* __restrict__ LPF, uint64_t n, uint64_t n_tiles, idx_t* __restrict__ ex)
+{
+    SHARED_ARRAY(uint16_t, bufa, LZ_TILE);
+    SHARED_ARRAY(uint16_t, bufb, LZ_TILE);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t t0 = tile * LZ_TILE;
+        PAR(tid) {
+            for (uint32_t s = tid; s < LZ_TILE; s += FM_NT) {
+                const uint64_t pos = t0 + s;
+                uint32_t nx = s;                                                    // the fixed point: the chain leaves the tile from here
+                if (pos < n) {
+                    const uint64_t len = lz_len((uint64_t)LPF[pos], n, pos);
+                    if (len < LZ_TILE - s && pos + len < n) nx = s + (uint32_t)len;
+                }
+                bufa[s] = (uint16_t)nx;
+            }
+        }
+        SYNC();
+        uint16_t* src = bufa;
+        uint16_t* dst = bufb;
+        for (uint32_t r = 0; r < LZ_ROUNDS; ++r) {
+            PAR(tid) { for (uint32_t s = tid; s < LZ_TILE; s += FM_NT) dst[s] = src[src[s]]; }
+            SYNC();
+            uint16_t* t = src; src = dst; dst = t;
+        }
+        PAR(tid) {
+            for (uint32_t s = tid; s < LZ_TILE; s += FM_NT) {
+                const uint64_t pos = t0 + s;
+                if (pos < n) {
+                    const uint64_t last = t0 + src[s];                              // (>= pos, < n: the chain never passes n)
+                    ex[pos] = (idx_t)(last + lz_len((uint64_t)LPF[last], n, last));
+                }
+            }
+        }
+        SYNC();
+    }
+}
+
+// gx[g * LZ_SPEC + o] = where the chain from position g * LZ_GPOS + o leaves group g: the exits of at most LZ_GROUP tiles composed,
+// for the first LZ_SPEC positions of every group, one lane each
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lz_group_kernel(KCTX const idx_t* __restrict__ ex, uint64_t n, uint64_t n_groups, idx_t* __restrict__ gx)
+{
+    PAR(tid) {
+        for (uint64_t k = (uint64_t)K_BLOCK_IDX * FM_NT + tid; k < n_groups * LZ_SPEC; k += (uint64_t)K_GRID_DIM * FM_NT) {
+            const uint64_t g = k / LZ_SPEC, end = std::min<uint64_t>(n, (g + 1) * LZ_GPOS);
+            uint64_t e = g * LZ_GPOS + k % LZ_SPEC;
+            for (uint32_t hop = 0; hop < LZ_GROUP && e < end; ++hop) {              // (an exit lies beyond its tile: a hop per tile at most)
+                const uint64_t nx = (uint64_t)ex[e];
+                e = nx > e ? nx : n;
+            }
+            gx[k] = (idx_t)std::min<uint64_t>(e, n);
+        }
+    }
+}
+
+// one workgroup: the chain over the GROUPS, gentry[g] = the position at which the parse enters group g (all-ones: it jumps over g).
+// The composed exits of LZ_BATCH groups go into LDS before the lane walks them; an entry at LZ_SPEC or more positions into its group
+// hops the group's tiles instead (at most LZ_GROUP dependent loads).
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lz_hop_kernel(KCTX const idx_t* __restrict__ ex, const idx_t* __restrict__ gx, uint64_t n, uint64_t n_groups,
+                                              uint64_t* __restrict__ gentry)
+{
+    SHARED_ARRAY(idx_t, spec, LZ_BATCH * LZ_SPEC);
+    SHARED_ARRAY(uint64_t, st, 1);
+    PAR(tid) {
+        for (uint64_t g = tid; g < n_groups; g += FM_NT) gentry[g] = ~(uint64_t)0;
+        if (tid == 0) st[0] = 0;
+    }
+    SYNC();
+    for (uint64_t base = 0; base < n_groups; base += LZ_BATCH) {                    // block-uniform
+        PAR(tid) {
+            if (st[0] / LZ_GPOS < base + LZ_BATCH) {                                // (else the chain jumps over the whole batch)
+                for (uint32_t k = tid; k < LZ_BATCH * LZ_SPEC; k += FM_NT) {
+                    const uint64_t at = base * LZ_SPEC + k;
+                    spec[k] = at < n_groups * LZ_SPEC ? gx[at] : (idx_t)0;
+                }
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            if (tid == 0) {
+                uint64_t e = st[0];
+                while (e < n) {
+                    const uint64_t g = e / LZ_GPOS;
+                    if (g >= base + LZ_BATCH) break;
+                    gentry[g] = e;
+                    const uint64_t off = e - g * LZ_GPOS;
+                    uint64_t nx = e;
+                    if (off < LZ_SPEC) {
+                        nx = (uint64_t)spec[(g - base) * LZ_SPEC + off];
+                    } else {
+                        const uint64_t end = std::min<uint64_t>(n, (g + 1) * LZ_GPOS);
+                        for (uint32_t hop = 0; hop < LZ_GROUP && nx < end; ++hop) {
+                            const uint64_t t = (uint64_t)ex[nx];
+                            nx = t > nx ? t : n;
+                        }
+                    }
+                    e = nx > e ? nx : n;                                            // (always forward)
+                }
+                st[0] = e;
+            }
+        }
+        SYNC();
+    }
+}
+
+// one lane per group: entry[t] for the group's tiles (all-ones: the parse jumps over t), at most LZ_GROUP dependent loads
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lz_entry_kernel(KCTX const idx_t* __restrict__ ex, uint64_t n, uint64_t n_tiles, uint64_t n_groups,
+                                                const uint64_t* __restrict__ gentry, uint64_t* __restrict__ entry)
+{
+    PAR(tid) {
+        for (uint64_t g = (uint64_t)K_BLOCK_IDX * FM_NT + tid; g < n_groups; g += (uint64_t)K_GRID_DIM * FM_NT) {
+            const uint64_t t1 = std::min<uint64_t>(n_tiles, (g + 1) * LZ_GROUP), end = std::min<uint64_t>(n, (g + 1) * LZ_GPOS);
+            for (uint64_t t = g * LZ_GROUP; t < t1; ++t) entry[t] = ~(uint64_t)0;
+            uint64_t e = gentry[g];
+            if (e < g * LZ_GPOS) e = end;                                           // (all-ones is beyond `end` anyway)
+            for (uint32_t hop = 0; hop < LZ_GROUP && e < end; ++hop) {
+                entry[e / LZ_TILE] = e;
+                const uint64_t nx = (uint64_t)ex[e];
+                e = nx > e ? nx : n;
+            }
+        }
+    }
+}
+
+// MODE LZ_COUNT: cnt[tile] = the phrases that start in the tile.  MODE LZ_WRITE: cnt[] scanned; the records (pos | len | src) at
+// cnt[tile] + their number in the tile; a slot at or beyond cap is not written.
+template <typename idx_t, int MODE>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lz_walk_kernel(KCTX const idx_t* __restrict__ LPF, const idx_t* __restrict__ Prev, uint64_t n, uint64_t n_tiles,
+                                               const uint64_t* __restrict__ entry, uint64_t* __restrict__ cnt, uint64_t* __restrict__ rec,
+                                               uint64_t cap)
+{
+    SHARED_ARRAY(uint16_t, nxt, LZ_TILE);                  // the next phrase's start, tile-relative; LZ_TILE: beyond the tile or the text
+    SHARED_ARRAY(uint16_t, bx, LZ_TILE);                   // the first chain position beyond the block
+    SHARED_ARRAY(uint16_t, bent, FM_NT);                   // per block: where the parse enters it (LZ_TILE: nowhere)
+    SHARED_ARRAY(uint32_t, lane, FM_NT);
+    SHARED_ARRAY(uint32_t, scan, FM_NT);
+    SHARED_ARRAY(uint32_t, grp, 2 * KMER_GROUP);
+    SHARED_ARRAY(uint32_t, h, 1);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t t0 = tile * LZ_TILE, e = entry[tile];
+        if (e < t0 || e - t0 >= LZ_TILE || e >= n) {                                // the parse jumps over this tile
+            if (MODE == LZ_COUNT) { PAR(tid) { if (tid == 0) cnt[tile] = 0; } }
+            continue;
+        }
+        PAR(tid) {
+            for (uint32_t s = tid; s < LZ_TILE; s += FM_NT) {
+                const uint64_t pos = t0 + s;
+                uint32_t nx = LZ_TILE;
+                if (pos < n) {
+                    const uint64_t len = lz_len((uint64_t)LPF[pos], n, pos);
+                    if (len < LZ_TILE - s && pos + len < n) nx = s + (uint32_t)len;
+                }
+                nxt[s] = (uint16_t)nx;
+            }
+            bent[tid] = (uint16_t)LZ_TILE;
+            if (tid == 0) h[0] = 0;
+        }
+        SYNC();
+        PAR(tid) {                                          // one lane per block, right to left
+            const uint32_t b0 = tid * LZ_BLOCK, b1 = b0 + LZ_BLOCK;
+            for (uint32_t s = b1; s-- > b0;) {
+                const uint32_t v = nxt[s];
+                bx[s] = v >= b1 ? (uint16_t)v : bx[v];
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            if (tid == 0) {
+                uint32_t cur = (uint32_t)(e - t0);
+                while (cur < LZ_TILE) {
+                    bent[cur / LZ_BLOCK] = (uint16_t)cur;
+                    const uint32_t v = bx[cur];
+                    cur = v > cur ? v : LZ_TILE;
+                }
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            const uint32_t b1 = (tid + 1) * LZ_BLOCK;
+            uint32_t mine = 0;
+            for (uint32_t cur = bent[tid]; cur < b1; cur = nxt[cur]) ++mine;
+            if (MODE == LZ_COUNT) { if (mine) FETCH_ADD_U32(&h[0], mine); }
+            else lane[tid] = mine;
+        }
+        SYNC();
+        if (MODE == LZ_COUNT) {
+            PAR(tid) { if (tid == 0) cnt[tile] = h[0]; }
+            SYNC();
+        } else {
+            PAR(tid) {                                      // forward: the records of the lanes before every lane
+                if (tid < KMER_GROUP) {
+                    uint32_t run = 0;
+                    for (uint32_t j = 0; j < KMER_GROUP; ++j) {
+                        const uint32_t at = tid * KMER_GROUP + j, x = lane[at];
+                        scan[at] = run;
+                        run += x;
+                    }
+                    grp[tid] = run;
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                if (tid == 0) {
+                    uint32_t run = 0;
+                    for (uint32_t g = 0; g < KMER_GROUP; ++g) { const uint32_t x = grp[g]; grp[KMER_GROUP + g] = run; run += x; }
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                const uint32_t b1 = (tid + 1) * LZ_BLOCK;
+                uint64_t at = cnt[tile] + scan[tid] + grp[KMER_GROUP + tid / KMER_GROUP];
+                for (uint32_t cur = bent[tid]; cur < b1; cur = nxt[cur]) {
+                    const uint64_t pos = t0 + cur, lp = (uint64_t)LPF[pos];
+                    if (at < cap) {
+                        rec[3 * at] = pos;
+                        rec[3 * at + 1] = lz_len(lp, n, pos);
+                        rec[3 * at + 2] = lp ? (uint64_t)Prev[pos] : ~(uint64_t)0;
+                    }
+                    ++at;
+                }
+            }
+            SYNC();
+        }
+    }
+}
+
 }  // namespace caps

@@ -688,6 +688,64 @@ int caps_sa_hip_kmer_census_u32(const uint32_t* SA, const uint32_t* LCP, uint64_
 int caps_sa_hip_kmer_census_u64(const uint64_t* SA, const uint64_t* LCP, uint64_t n, uint32_t max_k, uint64_t* distinct,
                                 uint64_t* unique, int device);
 
+/* ---- LPF and LZ77 from SA and LCP ---------------------------------------------------
+ * The longest-previous-factor array with a previous occurrence for every position, and the LZ77 factorization that follows from
+ * it, from the two arrays a full-context construct() gives: the text is not read. n entries; SA is a permutation of 0 .. n - 1; LCP
+ * is any array, and LCP[0] counts as 0 whatever it holds. For rank r with i = SA[r]:
+ *   - p = the largest rank < r with SA[p] < i. If there is one, left = min(LCP[p + 1 .. r]); if there is none, left = 0.
+ *   - q = the smallest rank > r with SA[q] < i. If there is one, right = min(LCP[r + 1 .. q]); if there is none, right = 0.
+ *   - LPF[i] = max(left, right).
+ *   - Prev[i] = SA[p] if left >= right and left > 0; Prev[i] = SA[q] if right > left; Prev[i] = the all-ones value of the index
+ *     width if LPF[i] = 0. On equal lengths the lower-rank side wins.
+ * When (SA, LCP) are the arrays of a full-context build of T, LPF[i] is the longest prefix of T[i ..) that also starts at some j < i
+ * (the two may overlap), Prev[i] is such a j, and LPF[i] <= n - i. Arrays of a bounded-context build are no suffix array: the
+ * result is then unspecified.
+ *
+ * lpf: dLPF and dPrev are n entries of the index width in TEXT order; either may be NULL and is then not written (both NULL with
+ * n > 0 is CAPS_SA_EINVAL). A value SA[r] >= n is never used as an index: that rank is skipped, the call returns CAPS_SA_EINVAL
+ * ("not a suffix array") and its outputs are unspecified. Duplicate SA values are not detected; a slot whose position never occurs
+ * in SA keeps what it held. The work per rank is bounded for ANY permutation: at most 2 * 64 steps per level of a 64-ary tree of
+ * (min SA, min LCP) summaries over the ranks and per direction, 2 + ceil(log64(n / 4096)) levels.
+ *
+ * LZ77 from (LPF, Prev), both in text order: s_0 = 0; the phrase at s has len = min(max(1, LPF[s]), n - s) and src = Prev[s] if
+ * LPF[s] > 0, else UINT64_MAX (a literal of one byte); s_{j+1} = s_j + len_j until s = n. Records of 24 bytes, little-endian, in
+ * text order:
+ *     u64 pos | u64 len | u64 src
+ * z = the number of records. The clamp makes the chain defined for any arrays, and it moves strictly forward.
+ * *n_phrases (host) is always written. dRecords = NULL is the counting call. A non-null dRecords (8-byte aligned) with
+ * *n_phrases > capacity is CAPS_SA_EINVAL: *n_phrases is still valid and no record is written.
+ *
+ * Common: a null array with n > 0, a null n_phrases, n > UINT32_MAX with _u32 or a workspace that is too small are CAPS_SA_EINVAL,
+ * checked before any allocation, nothing written. n = 0 succeeds with z = 0. For any input every call terminates and reads and
+ * writes only inside its arrays. Workspaces (W = the index width in bytes; NULL is allocated and freed by the call):
+ *   lpf   no array of n entries: 2 W (ceil(n / 64) + ceil(n / 64^2) + ... + 1) bytes of summaries, each array rounded up to 256
+ *         bytes, plus 1,024 bytes (the level table, the flag, alignment) -- less than n W / 31 + 2 KiB;
+ *   lz77  one array of n entries of the index width (where the chain from every position leaves its tile of 16,384). Exactly, with
+ *         t = ceil(n / 16,384) tiles, g = ceil(n / 1,048,576) groups of 64 tiles and up(b) = b rounded up to 256:
+ *         up(n W) + up(64 g W) + up(8 g) + up(8 t) + up(8 (t + 1)) + 512 bytes.
+ * (lpf exactly: 2 up(W nodes) + 1,024 with nodes = ceil(n / 64) + ceil(n / 64^2) + ... + 1.)
+ * dSA, dLCP, dLPF, dPrev, dRecords and workspace are device pointers on the current device; the work runs on hip_stream and has
+ * completed on return. Ranks beyond 2^32 (_u64 with n > UINT32_MAX) are untested.
+ */
+int caps_sa_hip_lpf_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes);
+int caps_sa_hip_lpf_device_u32(const void* dSA, const void* dLCP, uint64_t n, void* dLPF, void* dPrev, void* workspace,
+                               uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_lpf_device_u64(const void* dSA, const void* dLCP, uint64_t n, void* dLPF, void* dPrev, void* workspace,
+                               uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_lz77_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes);
+int caps_sa_hip_lz77_device_u32(const void* dLPF, const void* dPrev, uint64_t n, void* dRecords, uint64_t capacity, uint64_t* n_phrases,
+                                void* workspace, uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_lz77_device_u64(const void* dLPF, const void* dPrev, uint64_t n, void* dRecords, uint64_t capacity, uint64_t* n_phrases,
+                                void* workspace, uint64_t workspace_bytes, void* hip_stream);
+/* Host arrays: SA and LCP go up into device buffers of the call's own on `device`, the results come down. lz77 is lpf followed by the
+ * parse: an SA value >= n is CAPS_SA_EINVAL here too. */
+int caps_sa_hip_lpf_u32(const uint32_t* SA, const uint32_t* LCP, uint64_t n, uint32_t* LPF, uint32_t* Prev, int device);
+int caps_sa_hip_lpf_u64(const uint64_t* SA, const uint64_t* LCP, uint64_t n, uint64_t* LPF, uint64_t* Prev, int device);
+int caps_sa_hip_lz77_u32(const uint32_t* SA, const uint32_t* LCP, uint64_t n, void* records, uint64_t capacity, uint64_t* n_phrases,
+                         int device);
+int caps_sa_hip_lz77_u64(const uint64_t* SA, const uint64_t* LCP, uint64_t n, void* records, uint64_t capacity, uint64_t* n_phrases,
+                         int device);
+
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
 /* merge_sort (src/Suffix_Array.cpp:112-129) of an arbitrary list of cnt distinct suffix
