@@ -77,6 +77,11 @@ def lpf(SA, LCP, device: int = 0, _lib: CapsLib | None = None):
     return (_lib or lib()).lpf(SA, LCP, device=device)
 
 
+def isa(SA, device: int = 0, _lib: CapsLib | None = None) -> np.ndarray:
+    """The inverse suffix array of SA, in SA's dtype: ISA[SA[r]] = r.  Anything but a permutation of 0 .. n - 1: CapsSaError (-1)."""
+    return (_lib or lib()).isa(SA, device=device)
+
+
 def lz77(SA, LCP, device: int = 0, _lib: CapsLib | None = None) -> np.ndarray:
     """The LZ77 factorization of that text: a structured array (LZ_DTYPE: pos, len, src) in text order; phrase j is
     T[src : src + len] (the two may overlap), or the one byte T[pos] where src = LZ_LITERAL."""
@@ -184,6 +189,11 @@ class SuffixArray:
         T()[pos] where src = LZ_LITERAL."""
         SA, LCP = self._kmer_arrays("LPF and LZ77")
         return lib().lz77(SA, LCP, self._bits, self._device)
+
+    def ISA(self) -> np.ndarray:
+        """The inverse suffix array: ISA()[SA()[r]] = r (the rank of every text position)."""
+        SA, _ = self._kmer_arrays("ISA and the LCE index")
+        return lib().isa(SA, self._bits, self._device)
 
     def dump(self, path: str) -> None:
         """Suffix_Array::dump format (src/Suffix_Array.cpp:497-509): u64 n, SA, LCP."""
@@ -311,4 +321,64 @@ class FMIndex:
 
     @classmethod
     def load(cls, path: str, device: int = 0, _lib: CapsLib | None = None) -> "FMIndex":
+        return cls(np.fromfile(path, dtype=np.uint8), device, _lib)
+
+
+class LCEIndex:
+    """ISA, LCP and range-minimum tables over a suffix array as one blob (include/caps_sa_hip.h "ISA and longest common extensions"):
+    batched ``lce(i, j, mismatches)`` of text positions and ``range_min(lo, hi)`` of ranks on the GPU.  The blob alone answers
+    (``blob``, np.uint8; ``nbytes``); ``save`` / ``load`` write and read exactly it."""
+
+    def __init__(self, blob: np.ndarray, device: int = 0, _lib: CapsLib | None = None):
+        self.blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        self._device = device
+        self._lib = _lib
+        if self.blob.size < 256 or bytes(self.blob[:8]) != b"CAPSLCE1":
+            raise ValueError("not an LCE index blob")
+        hdr = self.blob[:256].view(np.uint64)
+        self._n, self._w = int(hdr[2]), int(hdr[3])
+        if self._w not in (4, 8) or int(hdr[15]) > self.blob.size or int(hdr[9]) != 256 or int(hdr[10]) < 256 + self._n * self._w:
+            raise ValueError("not an LCE index blob")
+
+    def _l(self) -> CapsLib:
+        return self._lib or lib()
+
+    @classmethod
+    def from_arrays(cls, SA, LCP, idx_bits: int | None = None, device: int = 0, _lib: CapsLib | None = None) -> "LCEIndex":
+        """From the full-context SA and LCP of a text, e.g. arrays read from a dump."""
+        return cls((_lib or lib()).lce_build(SA, LCP, idx_bits, device), device, _lib)
+
+    @classmethod
+    def from_suffix_array(cls, sa_obj: "SuffixArray") -> "LCEIndex":
+        """From a constructed full-context ``SuffixArray``; a bounded-context one raises ValueError."""
+        SA, LCP = sa_obj._kmer_arrays("ISA and the LCE index")
+        return cls.from_arrays(SA, LCP, sa_obj._bits, sa_obj._device)
+
+    @property
+    def n(self) -> int:
+        return self._n
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.blob.size)
+
+    def lce(self, i, j, mismatches: int = 0) -> np.ndarray:
+        """np.uint64: the largest l such that T[i : i + l] and T[j : j + l] differ in at most ``mismatches`` (0 .. 1024) places."""
+        return self._l().lce(self.blob, i, j, mismatches, self._device)
+
+    def range_min(self, lo, hi) -> np.ndarray:
+        """np.uint64: min LCP[lo .. hi] over ranks, both ends inclusive (LCP[0] read as 0): the string depth of the SA interval
+        [lo - 1, hi], e.g. ``range_min(first + 1, first + count - 1)`` for the (first, count) of ``FMIndex.count``."""
+        return self._l().lce_range_min(self.blob, lo, hi, self._device)
+
+    def isa(self) -> np.ndarray:
+        """The inverse suffix array the blob holds (a copy), in the index dtype."""
+        return self.blob[256:256 + self._n * self._w].view(np.uint32 if self._w == 4 else np.uint64).copy()
+
+    def save(self, path: str) -> None:
+        with open(path, "wb") as f:
+            f.write(self.blob.tobytes())
+
+    @classmethod
+    def load(cls, path: str, device: int = 0, _lib: CapsLib | None = None) -> "LCEIndex":
         return cls(np.fromfile(path, dtype=np.uint8), device, _lib)

@@ -125,14 +125,15 @@ EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_b
            "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_from_bwt_workspace_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device",
            "fm_index_bytes_ex", "fm_add_text_samples", "fm_add_text_samples_device", "fm_extract_workspace_bytes", "fm_extract", "fm_extract_device",
            "fm_match", "fm_match_device", "fm_mems_workspace_bytes", "fm_mems", "fm_mems_device", "fm_wide_index_bytes",
-           "fm_wide_workspace_bytes", "kmer_workspace_bytes", "lpf_workspace_bytes", "lz77_workspace_bytes"] + SHARD_EXPORTS + [
+           "fm_wide_workspace_bytes", "kmer_workspace_bytes", "lpf_workspace_bytes", "lz77_workspace_bytes", "lce_index_bytes",
+           "lce_range_min", "lce_range_min_device", "lce", "lce_device"] + SHARD_EXPORTS + [
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
     for name in ("build", "build_multi", "build_device", "verify_device", "verify_slice_device", "sort_suffixes", "sort_segments", "merge",
                  "upper_bound", "lcp", "build_bwt", "bwt_device", "inverse_bwt", "inverse_bwt_device", "fm_build", "fm_build_device",
                  "fm_build_from_bwt", "fm_build_from_bwt_device", "fm_build_wide", "fm_build_wide_device",
                  "kmers", "kmers_device", "kmer_spectrum", "kmer_spectrum_device", "kmer_census", "kmer_census_device",
-                 "lpf", "lpf_device", "lz77", "lz77_device")
+                 "lpf", "lpf_device", "lz77", "lz77_device", "isa", "isa_device", "lce_build", "lce_build_device")
 ]
 
 
@@ -232,7 +233,25 @@ class CapsLib:
         for name in ("lpf_workspace_bytes", "lz77_workspace_bytes"):
             f(name).restype = _ci
             f(name).argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
+        f("lce_index_bytes").restype = _ci
+        f("lce_index_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
+        f("lce_range_min").restype = _ci
+        f("lce_range_min").argtypes = [_vp, _u64, _vp, _vp, _u64, _vp, _ci]
+        f("lce_range_min_device").restype = _ci
+        f("lce_range_min_device").argtypes = [_vp, _u64, _vp, _vp, _u64, _vp, _vp]
+        f("lce").restype = _ci
+        f("lce").argtypes = [_vp, _u64, _vp, _vp, _u64, _u64, _vp, _ci]
+        f("lce_device").restype = _ci
+        f("lce_device").argtypes = [_vp, _u64, _vp, _vp, _u64, _u64, _vp, _vp]
         for sfx in ("u32", "u64"):
+            f(f"isa_{sfx}").restype = _ci
+            f(f"isa_{sfx}").argtypes = [_vp, _u64, _vp, _ci]
+            f(f"isa_device_{sfx}").restype = _ci
+            f(f"isa_device_{sfx}").argtypes = [_vp, _u64, _vp, _vp]
+            f(f"lce_build_{sfx}").restype = _ci
+            f(f"lce_build_{sfx}").argtypes = [_vp, _vp, _u64, _vp, _u64, _ci]
+            f(f"lce_build_device_{sfx}").restype = _ci
+            f(f"lce_build_device_{sfx}").argtypes = [_vp, _vp, _u64, _vp, _u64, _vp]
             f(f"lpf_{sfx}").restype = _ci
             f(f"lpf_{sfx}").argtypes = [_vp, _vp, _u64, _vp, _vp, _ci]
             f(f"lpf_device_{sfx}").restype = _ci
@@ -869,6 +888,69 @@ class CapsLib:
             err.n_phrases = found.value
             raise err
         return found.value
+
+    # ------------------------------------------------------------------ ISA and the LCE index (include/caps_sa_hip.h "ISA and longest common extensions")
+    def isa(self, SA, idx_bits: int | None = None, device: int = 0) -> np.ndarray:
+        """The inverse suffix array, ISA[SA[r]] = r, in SA's dtype (or idx_bits).  Not a permutation of 0 .. n - 1: CapsSaError (-1)."""
+        SA = np.asarray(SA)
+        sfx, dt = _sfx(idx_bits or (64 if SA.dtype.itemsize == 8 else 32))
+        SA = np.ascontiguousarray(SA, dtype=dt)
+        if SA.ndim != 1:
+            raise ValueError("SA: a 1-d array")
+        n = int(SA.size)
+        ISA = np.zeros(n, dtype=dt)
+        self._check(self._f(f"isa_{sfx}")(SA.ctypes.data if n else None, n, ISA.ctypes.data if n else None, device))
+        return ISA
+
+    def isa_device(self, dSA_ptr: int, n: int, dISA_ptr: int, idx_bits: int = 32, stream: int = 0) -> None:
+        sfx, _ = _sfx(idx_bits)
+        self._check(self._f(f"isa_device_{sfx}")(dSA_ptr or None, n, dISA_ptr or None, stream or None))
+
+    def lce_index_bytes(self, n: int, idx_bits: int = 32) -> int:
+        out = _u64(0)
+        self._check(self._f("lce_index_bytes")(n, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    def lce_build(self, SA, LCP, idx_bits: int | None = None, device: int = 0) -> np.ndarray:
+        """The LCE index of (SA, LCP) as one np.uint8 blob: ISA, LCP and the two tiers of range-minimum tables."""
+        SA, LCP, n, sfx = self._sa_lcp(SA, LCP, idx_bits)
+        blob = np.zeros(self.lce_index_bytes(n, SA.dtype.itemsize * 8), dtype=np.uint8)
+        self._check(self._f(f"lce_build_{sfx}")(SA.ctypes.data if n else None, LCP.ctypes.data if n else None, n, blob.ctypes.data, blob.size, device))
+        return blob
+
+    def lce_build_device(self, dSA_ptr: int, dLCP_ptr: int, n: int, dIndex_ptr: int, index_bytes: int, idx_bits: int = 32, stream: int = 0) -> None:
+        sfx, _ = _sfx(idx_bits)
+        self._check(self._f(f"lce_build_device_{sfx}")(dSA_ptr or None, dLCP_ptr or None, n, dIndex_ptr or None, index_bytes, stream or None))
+
+    def _lce_pairs(self, name, index, a, b, extra, device):
+        index = np.ascontiguousarray(index, dtype=np.uint8)
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+        b = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1)
+        if a.size != b.size:
+            raise ValueError("two arrays of one size")
+        q = int(a.size)
+        out = np.zeros(q, dtype=np.uint64)
+        self._check(self._f(name)(index.ctypes.data, index.size, a.ctypes.data if q else None, b.ctypes.data if q else None, q, *extra,
+                                  out.ctypes.data if q else None, device))
+        return out
+
+    def lce_range_min(self, index: np.ndarray, lo, hi, device: int = 0) -> np.ndarray:
+        """min LCP[lo[x] .. hi[x]] over RANKS, both ends inclusive, as np.uint64; lo > hi or hi >= n: CapsSaError (-1)."""
+        return self._lce_pairs("lce_range_min", index, lo, hi, (), device)
+
+    def lce(self, index: np.ndarray, i, j, mismatches: int = 0, device: int = 0) -> np.ndarray:
+        """The longest common extension of T[i[x]:] and T[j[x]:] with at most `mismatches` (0 .. 1024) differing places, np.uint64."""
+        if mismatches < 0:
+            raise ValueError("mismatches: 0 .. 1024")
+        return self._lce_pairs("lce", index, i, j, (int(mismatches),), device)
+
+    def lce_range_min_device(self, dIndex_ptr: int, index_bytes: int, dLo_ptr: int, dHi_ptr: int, q: int, dMin_ptr: int, stream: int = 0) -> None:
+        self._check(self._f("lce_range_min_device")(dIndex_ptr or None, index_bytes, dLo_ptr or None, dHi_ptr or None, q, dMin_ptr or None,
+                                                    stream or None))
+
+    def lce_device(self, dIndex_ptr: int, index_bytes: int, dI_ptr: int, dJ_ptr: int, q: int, mismatches: int, dLen_ptr: int, stream: int = 0) -> None:
+        self._check(self._f("lce_device")(dIndex_ptr or None, index_bytes, dI_ptr or None, dJ_ptr or None, q, mismatches, dLen_ptr or None,
+                                          stream or None))
 
     # ------------------------------------------------------------------ kernel-level entry points
     def sort_suffixes(self, T, idx, idx_bits: int = 32, device: int = 0):

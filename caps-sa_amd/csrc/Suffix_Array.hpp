@@ -22,6 +22,8 @@
 //    after a full-context construct() (include/caps_sa_hip.h "k-mers from SA and LCP").
 //  * lpf() / lz77() (not in the reference): the longest-previous-factor array with a previous occurrence for every position, and the LZ77
 //    factorization, from SA() and LCP() after a full-context construct() (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP").
+//  * ISA() (not in the reference): the inverse suffix array, after a full-context construct() (include/caps_sa_hip.h "ISA and longest
+//    common extensions"); and the class LCE_Index: batched longest common extensions and range minima over LCP from one blob.
 //  * the free function inverse_bwt() (not in the reference): the text back from (BWT, primary).
 //  * the class FM_Index (not in the reference either): count, locate, matching statistics, MEMs and extract over (BWT, primary) and a sample of the SA.
 #ifndef CAPS_SA_AMD_SUFFIX_ARRAY_HPP
@@ -202,6 +204,22 @@ public:
         out.resize(static_cast<std::size_t>(z));
         return out;
     }
+
+    // ---- the inverse suffix array (include/caps_sa_hip.h "ISA and longest common extensions"; not in the reference): ISA()[SA()[r]] = r.
+    // After a full-context construct(); with max_context set it throws std::invalid_argument.  On devices()[0].
+    std::vector<idx_t> ISA() const
+    {
+        if (max_context_ != 0 && max_context_ < n_)
+            throw std::invalid_argument("Suffix_Array::ISA: the inverse needs a full-context suffix array (max_context is set)");
+        std::vector<idx_t> out(static_cast<std::size_t>(n_));
+        const int rc = std::is_same<idx_t, uint32_t>::value
+            ? caps_sa_hip_isa_u32(reinterpret_cast<const uint32_t*>(SA_), n_, reinterpret_cast<uint32_t*>(out.data()), devices_[0])
+            : caps_sa_hip_isa_u64(reinterpret_cast<const uint64_t*>(SA_), n_, reinterpret_cast<uint64_t*>(out.data()), devices_[0]);
+        if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_isa: ") + caps_sa_hip_last_error());
+        return out;
+    }
+    bool full_context() const { return max_context_ == 0 || max_context_ >= n_; }
+    int device() const { return devices_[0]; }
 
     // Reference: src/Suffix_Array.cpp:497-509 -- u64 n, then SA, then LCP, native endianness.
     void dump(std::ofstream& output)
@@ -477,6 +495,93 @@ public:
         in.seekg(0);
         if (size > 0 && !in.read(reinterpret_cast<char*>(fm.blob_.data()), size)) throw std::runtime_error(path + " : cannot read");
         return fm;
+    }
+
+private:
+    static void check(int rc, const char* what)
+    {
+        if (rc != CAPS_SA_OK) throw std::runtime_error(std::string(what) + ": " + caps_sa_hip_last_error());
+    }
+    std::vector<uint8_t> blob_;
+    int device_;
+};
+
+// LCE index over (SA, LCP) (include/caps_sa_hip.h "ISA and longest common extensions"; not in the reference): ISA, a copy of LCP and
+// two tiers of range-minimum tables in one blob (data(), size()); lce() and range_min() answer batches on the GPU from the blob alone;
+// save / load write and read exactly it.  Every error of the C ABI is thrown as std::runtime_error with its message.
+class LCE_Index
+{
+public:
+    LCE_Index() : device_(0) {}
+
+    template <typename idx_t>
+    static LCE_Index build(const idx_t* SA, const idx_t* LCP, uint64_t n, int device = 0)
+    {
+        static_assert(std::is_same<idx_t, uint32_t>::value || std::is_same<idx_t, uint64_t>::value, "uint32_t or uint64_t");
+        LCE_Index x;
+        x.device_ = device;
+        uint64_t bytes = 0;
+        check(caps_sa_hip_lce_index_bytes(n, (int)sizeof(idx_t), &bytes), "caps_sa_hip_lce_index_bytes");
+        x.blob_.resize(static_cast<std::size_t>(bytes));
+        if (sizeof(idx_t) == 4)
+            check(caps_sa_hip_lce_build_u32(reinterpret_cast<const uint32_t*>(SA), reinterpret_cast<const uint32_t*>(LCP), n, x.blob_.data(), bytes, device),
+                  "caps_sa_hip_lce_build_u32");
+        else
+            check(caps_sa_hip_lce_build_u64(reinterpret_cast<const uint64_t*>(SA), reinterpret_cast<const uint64_t*>(LCP), n, x.blob_.data(), bytes, device),
+                  "caps_sa_hip_lce_build_u64");
+        return x;
+    }
+    // from a constructed full-context Suffix_Array; a bounded-context one throws std::invalid_argument
+    template <typename idx_t>
+    static LCE_Index build(const Suffix_Array<idx_t>& sa)
+    {
+        if (!sa.full_context()) throw std::invalid_argument("LCE_Index::build: the index needs a full-context suffix array (max_context is set)");
+        return build<idx_t>(sa.SA(), sa.LCP(), sa.n(), sa.device());
+    }
+
+    const uint8_t* data() const { return blob_.data(); }
+    std::size_t size() const { return blob_.size(); }
+    uint64_t n() const
+    {
+        uint64_t v = 0;
+        if (blob_.size() >= 256) std::memcpy(&v, blob_.data() + 2 * 8, 8);      // header word 2
+        return v;
+    }
+
+    // len[x] = the largest l such that T[i[x] .. i[x] + l) and T[j[x] .. j[x] + l) differ in at most `mismatches` (0 .. 1024) places
+    std::vector<uint64_t> lce(const std::vector<uint64_t>& i, const std::vector<uint64_t>& j, uint64_t mismatches = 0) const
+    {
+        if (i.size() != j.size()) throw std::invalid_argument("LCE_Index::lce: two vectors of one size");
+        std::vector<uint64_t> len(i.size());
+        check(caps_sa_hip_lce(blob_.data(), blob_.size(), i.data(), j.data(), i.size(), mismatches, len.data(), device_), "caps_sa_hip_lce");
+        return len;
+    }
+    // min[x] = min LCP[lo[x] .. hi[x]] over ranks, both ends inclusive, LCP[0] read as 0
+    std::vector<uint64_t> range_min(const std::vector<uint64_t>& lo, const std::vector<uint64_t>& hi) const
+    {
+        if (lo.size() != hi.size()) throw std::invalid_argument("LCE_Index::range_min: two vectors of one size");
+        std::vector<uint64_t> out(lo.size());
+        check(caps_sa_hip_lce_range_min(blob_.data(), blob_.size(), lo.data(), hi.data(), lo.size(), out.data(), device_), "caps_sa_hip_lce_range_min");
+        return out;
+    }
+
+    void save(const std::string& path) const
+    {
+        std::ofstream out(path, std::ios::binary);
+        if (out) out.write(reinterpret_cast<const char*>(blob_.data()), static_cast<std::streamsize>(blob_.size()));
+        if (!out) throw std::runtime_error(path + " : cannot write");
+    }
+    static LCE_Index load(const std::string& path, int device = 0)
+    {
+        std::ifstream in(path, std::ios::binary | std::ios::ate);
+        if (!in) throw std::runtime_error(path + " : cannot open");
+        const std::streamsize size = in.tellg();
+        LCE_Index x;
+        x.device_ = device;
+        x.blob_.resize(size > 0 ? static_cast<std::size_t>(size) : 0);
+        in.seekg(0);
+        if (size > 0 && !in.read(reinterpret_cast<char*>(x.blob_.data()), size)) throw std::runtime_error(path + " : cannot read");
+        return x;
     }
 
 private:

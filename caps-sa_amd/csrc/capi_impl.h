@@ -3197,6 +3197,281 @@ int lz77_host(const idx_t* SA, const idx_t* LCP, uint64_t n, void* records, uint
     });
 }
 
+// ---- ISA and the LCE index (include/caps_sa_hip.h "ISA and longest common extensions"; kernels.h isa_* / lce_*) -----------------------
+// The blob: a header of LCE_HDR_WORDS 64-bit words, then ISA[n] | LCP[n] | M_0 .. M_6 (nb entries each) | T_0 .. T_{tlevels-1} (ns
+// entries each), every array rounded up to 256 bytes.  Every header word follows from n and the index width.
+constexpr uint64_t LCE_MAGIC = 0x3145434C53504143ull;     // "CAPSLCE1"
+constexpr uint64_t LCE_VERSION = 1;
+constexpr uint32_t LCE_HDR_WORDS = 32;
+static_assert(LCE_HDR_WORDS == FM_HDR_WORDS, "fm_mark_resident keeps a header of this size and sums the body behind it");
+enum { LCEH_MAGIC = 0, LCEH_VERSION, LCEH_N, LCEH_IDX_BYTES, LCEH_BLOCK, LCEH_SUPER, LCEH_NB, LCEH_NS, LCEH_TLEVELS, LCEH_OFF_ISA, LCEH_OFF_LCP,
+       LCEH_OFF_M, LCEH_M_STRIDE, LCEH_OFF_T, LCEH_T_STRIDE, LCEH_TOTAL };
+
+struct LceLayout {
+    uint64_t nb = 0, ns = 0, tlevels = 0, off_isa = 0, off_lcp = 0, off_m = 0, m_stride = 0, off_t = 0, t_stride = 0, total = 0;
+};
+inline LceLayout lce_layout(uint64_t n, uint64_t w)
+{
+    auto up = [](uint64_t b) { return (b + 255) & ~uint64_t(255); };
+    LceLayout l;
+    l.nb = (n + LCE_BLOCK - 1) / LCE_BLOCK;
+    l.ns = (n + LCE_SUPER - 1) / LCE_SUPER;
+    l.tlevels = l.ns ? 64u - (uint64_t)caps_clz64(l.ns) : 0;          // floor(log2 ns) + 1
+    l.off_isa = LCE_HDR_WORDS * sizeof(uint64_t);
+    l.off_lcp = l.off_isa + up(n * w);
+    l.off_m = l.off_lcp + up(n * w);
+    l.m_stride = up(l.nb * w);
+    l.off_t = l.off_m + LCE_MLEVELS * l.m_stride;
+    l.t_stride = up(l.ns * w);
+    l.total = l.off_t + l.tlevels * l.t_stride;
+    return l;
+}
+inline void lce_header(uint64_t* h, uint64_t n, uint64_t w)
+{
+    const LceLayout l = lce_layout(n, w);
+    std::memset(h, 0, LCE_HDR_WORDS * sizeof(uint64_t));
+    h[LCEH_MAGIC] = LCE_MAGIC; h[LCEH_VERSION] = LCE_VERSION; h[LCEH_N] = n; h[LCEH_IDX_BYTES] = w; h[LCEH_BLOCK] = LCE_BLOCK;
+    h[LCEH_SUPER] = LCE_SUPER; h[LCEH_NB] = l.nb; h[LCEH_NS] = l.ns; h[LCEH_TLEVELS] = l.tlevels; h[LCEH_OFF_ISA] = l.off_isa;
+    h[LCEH_OFF_LCP] = l.off_lcp; h[LCEH_OFF_M] = l.off_m; h[LCEH_M_STRIDE] = l.m_stride; h[LCEH_OFF_T] = l.off_t; h[LCEH_T_STRIDE] = l.t_stride;
+    h[LCEH_TOTAL] = l.total;
+}
+inline int lce_index_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
+{
+    if (int rc = lz_ws_args(n, idx_bytes, bytes)) return rc;
+    *bytes = lce_layout(n, (uint64_t)idx_bytes).total;
+    return CAPS_SA_OK;
+}
+// the header, checked on the host before any kernel reads the body: every word is recomputed from n and the index width
+inline int lce_check_header(const uint64_t* h, uint64_t index_bytes, const void* dIndex, LceView& v)
+{
+    if (h[LCEH_MAGIC] != LCE_MAGIC) return fail(CAPS_SA_EINVAL, "not an LCE index of this library (wrong magic)");
+    if (h[LCEH_VERSION] != LCE_VERSION) return fail(CAPS_SA_EINVAL, "LCE index of another format version");
+    const uint64_t w = h[LCEH_IDX_BYTES], n = h[LCEH_N];
+    if (w != 4 && w != 8) return fail(CAPS_SA_EINVAL, "LCE index header: bad index width");
+    if ((w == 4 && n > 0xFFFFFFFFull) || n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "LCE index header: n does not fit its index width");
+    uint64_t want[LCE_HDR_WORDS];
+    lce_header(want, n, w);
+    if (std::memcmp(want, h, sizeof want) != 0) return fail(CAPS_SA_EINVAL, "LCE index header: a word does not follow from n and the index width");
+    if (want[LCEH_TOTAL] > index_bytes) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than the LCE index (truncated blob)");
+    const LceLayout l = lce_layout(n, w);
+    const char* base = static_cast<const char*>(dIndex);
+    v.n = n; v.nb = l.nb; v.ns = l.ns; v.tlevels = (uint32_t)l.tlevels;
+    v.isa = base + l.off_isa; v.lcp = base + l.off_lcp; v.m = base + l.off_m; v.t = base + l.off_t;
+    v.m_stride = l.m_stride; v.t_stride = l.t_stride;
+    return CAPS_SA_OK;
+}
+inline int lce_check_blob_args(const void* index, uint64_t index_bytes)
+{
+    if (!index) return fail(CAPS_SA_EINVAL, "null index");
+    if (reinterpret_cast<uintptr_t>(index) & 15u) return fail(CAPS_SA_EINVAL, "the index must be 16-byte aligned");
+    if (index_bytes < LCE_HDR_WORDS * sizeof(uint64_t)) return fail(CAPS_SA_EINVAL, "index_bytes is smaller than an LCE index header");
+    return CAPS_SA_OK;
+}
+
+// n >= 1.  dISA is overwritten whatever SA holds; flags: a device word of the call
+template <typename idx_t> int run_isa(Backend& be, const idx_t* dSA, uint64_t n, idx_t* dISA, uint32_t* flags)
+{
+    constexpr uint32_t PER = 16u / sizeof(idx_t);
+    const uint32_t g = capped_grid(std::min<uint64_t>(((n + PER - 1) / PER + FM_NT - 1) / FM_NT, 1u << 16), FM_NT);
+    be.memset(flags, 0, sizeof(uint32_t));
+    be.memset(dISA, 0xFF, n * sizeof(idx_t));
+    CAPS_LAUNCH((isa_scatter_kernel<idx_t>), g, FM_NT, be, dSA, n, dISA, flags);
+    CAPS_LAUNCH((isa_check_kernel<idx_t>), g, FM_NT, be, (const idx_t*)dISA, n, flags);
+    uint32_t f = 0;
+    be.d2h(&f, flags, sizeof f);
+    be.sync();
+    if (f & 1u) return fail(CAPS_SA_EINVAL, "not a suffix array: a value of SA is n or more");
+    if (f & 2u) return fail(CAPS_SA_EINVAL, "not a suffix array: a position occurs twice and another never");
+    return CAPS_SA_OK;
+}
+
+// the blob of (dSA, dLCP) at dIndex (room for lce_layout(n).total bytes); no workspace beyond it
+template <typename idx_t> int run_lce_build(Backend& be, const idx_t* dSA, const idx_t* dLCP, uint64_t n, char* dIndex)
+{
+    constexpr uint64_t w = sizeof(idx_t);
+    const LceLayout l = lce_layout(n, w);
+    uint64_t h[LCE_HDR_WORDS];
+    lce_header(h, n, w);
+    be.h2d(dIndex, h, sizeof h);
+    if (n == 0) { be.sync(); return CAPS_SA_OK; }
+    auto pad = [&](uint64_t off, uint64_t bytes) {                  // the section's padding is zero: equal inputs, equal blobs
+        const uint64_t end = (bytes + 255) & ~uint64_t(255);
+        if (end > bytes) be.memset(dIndex + off + bytes, 0, end - bytes);
+    };
+    pad(l.off_isa, n * w);
+    pad(l.off_lcp, n * w);
+    for (uint64_t j = 0; j < LCE_MLEVELS; ++j) pad(l.off_m + j * l.m_stride, l.nb * w);
+    for (uint64_t j = 0; j < l.tlevels; ++j) pad(l.off_t + j * l.t_stride, l.ns * w);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(fm_words(be));
+    if (int rc = run_isa<idx_t>(be, dSA, n, reinterpret_cast<idx_t*>(dIndex + l.off_isa), flags)) { be.sync(); return rc; }
+    auto M = [&](uint64_t j) { return reinterpret_cast<idx_t*>(dIndex + l.off_m + j * l.m_stride); };
+    auto T = [&](uint64_t j) { return reinterpret_cast<idx_t*>(dIndex + l.off_t + j * l.t_stride); };
+    auto grid = [](uint64_t lanes) { return capped_grid(std::min<uint64_t>((lanes + FM_NT - 1) / FM_NT, 1u << 16), FM_NT); };
+    CAPS_LAUNCH((lce_block_kernel<idx_t>), capped_grid(std::min<uint64_t>(l.ns, 1u << 20), FM_NT), FM_NT, be, dLCP, n, l.ns, l.nb,
+                reinterpret_cast<idx_t*>(dIndex + l.off_lcp), M(0));
+    for (uint64_t j = 1; j < LCE_MLEVELS; ++j)
+        CAPS_LAUNCH((lce_table_kernel<idx_t>), grid(l.nb), FM_NT, be, (const idx_t*)M(j - 1), l.nb, M(j), l.nb, (uint64_t)1, (uint64_t)1 << (j - 1));
+    CAPS_LAUNCH((lce_table_kernel<idx_t>), grid(l.ns), FM_NT, be, (const idx_t*)M(LCE_MLEVELS - 1), l.nb, T(0), l.ns, (uint64_t)LCE_BPS, (uint64_t)0);
+    for (uint64_t j = 1; j < l.tlevels; ++j)
+        CAPS_LAUNCH((lce_table_kernel<idx_t>), grid(l.ns), FM_NT, be, (const idx_t*)T(j - 1), l.ns, T(j), l.ns, (uint64_t)1, (uint64_t)1 << (j - 1));
+    be.sync();
+    return CAPS_SA_OK;
+}
+
+template <typename idx_t> int isa_check_args(const void* SA, uint64_t n, const void* ISA)
+{
+    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
+    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
+    if (n && (!SA || !ISA)) return fail(CAPS_SA_EINVAL, "SA or ISA is null");
+    return CAPS_SA_OK;
+}
+template <typename idx_t> int isa_device(const void* dSA, uint64_t n, void* dISA, void* stream)
+{
+    if (int rc = isa_check_args<idx_t>(dSA, n, dISA)) return rc;
+    if (n == 0) return CAPS_SA_OK;
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        return run_isa<idx_t>(be, static_cast<const idx_t*>(dSA), n, static_cast<idx_t*>(dISA), reinterpret_cast<uint32_t*>(fm_words(be)));
+    });
+}
+template <typename idx_t> int isa_host(const idx_t* SA, uint64_t n, idx_t* ISA, int device)
+{
+    if (int rc = isa_check_args<idx_t>(SA, n, ISA)) return rc;
+    if (n == 0) return CAPS_SA_OK;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        hc.fm_host = nullptr;
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const size_t off_isa = up(n * sizeof(idx_t));
+        fm_host_block(hc, be, device, off_isa + up(n * sizeof(idx_t)));
+        idx_t* dSA = reinterpret_cast<idx_t*>(hc.base);
+        idx_t* dISA = reinterpret_cast<idx_t*>(hc.base + off_isa);
+        be.h2d(dSA, SA, n * sizeof(idx_t));
+        if (int rc = run_isa<idx_t>(be, dSA, n, dISA, reinterpret_cast<uint32_t*>(fm_words(be)))) return rc;      // ISA is not written
+        be.d2h(ISA, dISA, n * sizeof(idx_t));
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+
+template <typename idx_t> int lce_check_build(const void* SA, const void* LCP, uint64_t n, const void* index, uint64_t index_bytes)
+{
+    if (int rc = lz_check_arrays<idx_t>(SA, LCP, n, "SA or LCP is null")) return rc;
+    if (!index) return fail(CAPS_SA_EINVAL, "null index");
+    if (reinterpret_cast<uintptr_t>(index) & 15u) return fail(CAPS_SA_EINVAL, "the index must be 16-byte aligned");
+    if (index_bytes < lce_layout(n, sizeof(idx_t)).total) return fail(CAPS_SA_EINVAL, "index_bytes too small (caps_sa_hip_lce_index_bytes)");
+    return CAPS_SA_OK;
+}
+template <typename idx_t> int lce_build_device(const void* dSA, const void* dLCP, uint64_t n, void* dIndex, uint64_t index_bytes, void* stream)
+{
+    if (int rc = lce_check_build<idx_t>(dSA, dLCP, n, dIndex, index_bytes)) return rc;
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        return run_lce_build<idx_t>(be, static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), n, static_cast<char*>(dIndex));
+    });
+}
+template <typename idx_t> int lce_build_host(const idx_t* SA, const idx_t* LCP, uint64_t n, void* index, uint64_t index_bytes, int device)
+{
+    if (int rc = lce_check_build<idx_t>(SA, LCP, n, index, index_bytes)) return rc;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        hc.fm_host = nullptr;
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const size_t need = lce_layout(n, sizeof(idx_t)).total, off_sa = up(need), off_lcp = off_sa + up(n * sizeof(idx_t));
+        fm_host_block(hc, be, device, off_lcp + up(n * sizeof(idx_t)) + 256);
+        idx_t* dSA = reinterpret_cast<idx_t*>(hc.base + off_sa);
+        idx_t* dLCP = reinterpret_cast<idx_t*>(hc.base + off_lcp);
+        be.h2d(dSA, SA, n * sizeof(idx_t));
+        be.h2d(dLCP, LCP, n * sizeof(idx_t));
+        if (int rc = run_lce_build<idx_t>(be, dSA, dLCP, n, hc.base)) return rc;                                  // the caller's blob is not written
+        be.d2h(index, hc.base, need);
+        be.sync();
+        fm_mark_resident(hc, index, need);
+        return CAPS_SA_OK;
+    });
+}
+
+// one batch of queries on a blob at dIndex whose header (hdr, or fetched from the device) is checked first.  mismatches < 0: range_min
+// of ranks (A = lo, B = hi), else lce of positions with that many mismatches.  A refused query has 0 in its slot and the call fails.
+inline int run_lce_query(Backend& be, const void* dIndex, uint64_t index_bytes, const uint64_t* hdr, const void* dA, const void* dB, uint64_t q,
+                         int64_t mismatches, void* dOut)
+{
+    uint64_t h[LCE_HDR_WORDS];
+    if (hdr) std::memcpy(h, hdr, sizeof h);
+    else { be.d2h(h, dIndex, sizeof h); be.sync(); }
+    LceView v;
+    if (int rc = lce_check_header(h, index_bytes, dIndex, v)) return rc;
+    if (q == 0) return CAPS_SA_OK;
+    uint32_t* flags = reinterpret_cast<uint32_t*>(fm_words(be));
+    be.memset(flags, 0, sizeof(uint32_t));
+    const uint32_t g = capped_grid(std::min<uint64_t>((q + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
+    const uint64_t* A = static_cast<const uint64_t*>(dA);
+    const uint64_t* B = static_cast<const uint64_t*>(dB);
+    uint64_t* out = static_cast<uint64_t*>(dOut);
+    if (mismatches < 0) {
+        if (h[LCEH_IDX_BYTES] == 4) CAPS_LAUNCH((lce_range_min_kernel<uint32_t>), g, FM_NT, be, v, A, B, q, out, flags);
+        else CAPS_LAUNCH((lce_range_min_kernel<uint64_t>), g, FM_NT, be, v, A, B, q, out, flags);
+    } else {
+        if (h[LCEH_IDX_BYTES] == 4) CAPS_LAUNCH((lce_query_kernel<uint32_t>), g, FM_NT, be, v, A, B, q, (uint32_t)mismatches, out, flags);
+        else CAPS_LAUNCH((lce_query_kernel<uint64_t>), g, FM_NT, be, v, A, B, q, (uint32_t)mismatches, out, flags);
+    }
+    uint32_t f = 0;
+    be.d2h(&f, flags, sizeof f);
+    be.sync();
+    if (f & 1u) return fail(CAPS_SA_EINVAL, mismatches < 0 ? "a range with lo > hi or hi >= n (its slot holds 0)" : "a position >= n (its slot holds 0)");
+    return CAPS_SA_OK;
+}
+inline int lce_query_device(const void* dIndex, uint64_t index_bytes, const void* dA, const void* dB, uint64_t q, int64_t mismatches, void* dOut,
+                            void* stream)
+{
+    if (int rc = lce_check_blob_args(dIndex, index_bytes)) return rc;
+    if (q && (!dA || !dB || !dOut)) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (mismatches > (int64_t)LCE_MAX_MISMATCHES) return fail(CAPS_SA_EINVAL, "mismatches must be 0 .. 1024");
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        return run_lce_query(be, dIndex, index_bytes, nullptr, dA, dB, q, mismatches, dOut);
+    });
+}
+// the host form: the blob at the head of the host-path block (uploaded unless it is the one there already), the query arrays behind it
+inline int lce_query_host(const void* index, uint64_t index_bytes, const uint64_t* A, const uint64_t* B, uint64_t q, int64_t mismatches, uint64_t* out,
+                          int device)
+{
+    if (int rc = lce_check_blob_args(index, index_bytes)) return rc;
+    if (q && (!A || !B || !out)) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (mismatches > (int64_t)LCE_MAX_MISMATCHES) return fail(CAPS_SA_EINVAL, "mismatches must be 0 .. 1024");
+    uint64_t h[LCE_HDR_WORDS];
+    std::memcpy(h, index, sizeof h);
+    LceView v;
+    if (int rc = lce_check_header(h, index_bytes, index, v)) return rc;
+    if (q == 0) return CAPS_SA_OK;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        HostPathCache& hc = host_cache();
+        std::lock_guard<std::mutex> lock(hc.mu);
+        Backend be(nullptr);
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const uint64_t blob = h[LCEH_TOTAL];
+        const size_t off_a = up(blob), off_b = off_a + up(q * 8), off_out = off_b + up(q * 8);
+        fm_upload(hc, be, device, index, blob, off_out + up(q * 8));
+        be.h2d(hc.base + off_a, A, q * 8);
+        be.h2d(hc.base + off_b, B, q * 8);
+        const int rc = run_lce_query(be, hc.base, blob, h, hc.base + off_a, hc.base + off_b, q, mismatches, hc.base + off_out);
+        if (rc != CAPS_SA_OK && rc != CAPS_SA_EINVAL) return rc;
+        be.d2h(out, hc.base + off_out, q * 8);                       // (a refused query: the slots are defined, 0 in the refused ones)
+        be.sync();
+        return rc;
+    });
+}
+
 // Text on the device for the kernel-level entry points.
 struct DevText {
     uint8_t* raw = nullptr;
@@ -3712,6 +3987,29 @@ int CAPS_API(lz77_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) {
 CAPS_DEFINE_LZ(u32, uint32_t)
 CAPS_DEFINE_LZ(u64, uint64_t)
 #undef CAPS_DEFINE_LZ
+int CAPS_API(lce_index_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::lce_index_bytes(n, idx_bytes, bytes); }
+#define CAPS_DEFINE_LCE(SFX, IDX)                                                                                           \
+    int CAPS_API(isa_device_##SFX)(const void* dSA, uint64_t n, void* dISA, void* stream)                                   \
+    { return caps::isa_device<IDX>(dSA, n, dISA, stream); }                                                                 \
+    int CAPS_API(isa_##SFX)(const IDX* SA, uint64_t n, IDX* ISA, int device) { return caps::isa_host<IDX>(SA, n, ISA, device); } \
+    int CAPS_API(lce_build_device_##SFX)(const void* dSA, const void* dLCP, uint64_t n, void* dIndex, uint64_t index_bytes, \
+                                         void* stream)                                                                      \
+    { return caps::lce_build_device<IDX>(dSA, dLCP, n, dIndex, index_bytes, stream); }                                      \
+    int CAPS_API(lce_build_##SFX)(const IDX* SA, const IDX* LCP, uint64_t n, void* index, uint64_t index_bytes, int device) \
+    { return caps::lce_build_host<IDX>(SA, LCP, n, index, index_bytes, device); }
+CAPS_DEFINE_LCE(u32, uint32_t)
+CAPS_DEFINE_LCE(u64, uint64_t)
+#undef CAPS_DEFINE_LCE
+int CAPS_API(lce_range_min_device)(const void* dIndex, uint64_t index_bytes, const void* dLo, const void* dHi, uint64_t q, void* dMin, void* stream)
+{ return caps::lce_query_device(dIndex, index_bytes, dLo, dHi, q, -1, dMin, stream); }
+int CAPS_API(lce_range_min)(const void* index, uint64_t index_bytes, const uint64_t* lo, const uint64_t* hi, uint64_t q, uint64_t* min, int device)
+{ return caps::lce_query_host(index, index_bytes, lo, hi, q, -1, min, device); }
+int CAPS_API(lce_device)(const void* dIndex, uint64_t index_bytes, const void* dI, const void* dJ, uint64_t q, uint64_t mismatches, void* dLen,
+                         void* stream)
+{ return caps::lce_query_device(dIndex, index_bytes, dI, dJ, q, (int64_t)std::min<uint64_t>(mismatches, 1025), dLen, stream); }
+int CAPS_API(lce)(const void* index, uint64_t index_bytes, const uint64_t* i, const uint64_t* j, uint64_t q, uint64_t mismatches, uint64_t* len,
+                  int device)
+{ return caps::lce_query_host(index, index_bytes, i, j, q, (int64_t)std::min<uint64_t>(mismatches, 1025), len, device); }
 
 int CAPS_API(fm_mems_workspace_bytes)(uint64_t total_pattern_bytes, uint64_t q, uint64_t* bytes)
 { return caps::fm_mems_workspace_bytes(total_pattern_bytes, q, bytes); }

@@ -4,6 +4,8 @@
 //     caps_sa <input_path> <output_path> [subproblem-count] [bounded-context] [--pretty-print] [--gpus N] [--bwt PATH]
 //     caps_sa <input_path> <output_path> [subproblem-count] [--kmers K PATH [--min-count A] [--max-count B]] [--kmer-spectrum K PATH]
 //     caps_sa <input_path> <output_path> [subproblem-count] [--lz77 PATH]
+//     caps_sa <input_path> <output_path> [subproblem-count] [--lce-index PATH]
+//     caps_sa --lce INDEX PAIRS [--mismatches K]
 //     caps_sa --inverse-bwt IN.bwt OUT
 //     caps_sa <input_path> <output_path> [subproblem-count] --fm-index PATH [--fm-sample S] [--fm-text-sample T]
 //     caps_sa <input_path> <output_path> [subproblem-count] --raw [--bwt PATH] [--fm-index PATH [--fm-sample S]]
@@ -24,6 +26,11 @@
 //   (remapped, or with --raw the file's own bytes) to PATH (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP"): one line
 //   "pos<TAB>len<TAB>src" per phrase in text order, the phrase being a copy of len bytes from position src (the two may overlap); a
 //   literal is "pos<TAB>0<TAB>byte value in decimal", so the file alone decodes to the text.  Refused with a bounded context;
+// * --lce-index PATH (not in the reference; on the build line): after the SA / LCP output, the LCE index of the two arrays to PATH
+//   (include/caps_sa_hip.h "ISA and longest common extensions"): one blob that answers longest common extensions and range minima
+//   over LCP without the text or the arrays.  Refused with a bounded context;
+// * --lce INDEX PAIRS [--mismatches K] (not in the reference): one pair of text positions "i j" per line of PAIRS; per pair one line
+//   on stdout, the length of the longest common extension of T[i ..) and T[j ..) with at most K (0 .. 1024, default 0) mismatches;
 // * --raw (not in the reference; on the build line only): the text as given, no remap to {A,C,G,T} -- SA, LCP and --bwt are those of
 //   the file's own bytes, and --fm-index PATH writes the wide format (include/caps_sa_hip.h "FM-index: the wide format") for 1 .. 256
 //   distinct bytes.  --fm-search and --fm-mems tell a wide index by its magic and take the pattern lines as bytes, unremapped (a
@@ -88,6 +95,10 @@
 #if defined(caps_sa_hip_build_multi_u32) && !defined(caps_sa_hip_lz77_u32)
 #define CAPS_CLI_NO_LZ 1
 #endif
+// ... and for one that predates the LCE entry points: the CLI without --lce-index and --lce.
+#if defined(caps_sa_hip_build_multi_u32) && !defined(caps_sa_hip_lce_build_u32)
+#define CAPS_CLI_NO_LCE 1
+#endif
 
 static bool read_input(const std::string& path, std::string& text)
 {
@@ -122,7 +133,7 @@ struct KmerJob {
 template <typename idx_t>
 static int run(const std::string& text, const std::string& out_path, size_t p, size_t ctx, bool pretty, const std::vector<int>& devices,
                const std::string& bwt_path, const std::string& fm_path = std::string(), uint32_t fm_sample = 32, uint32_t fm_text_sample = 0, bool raw = false,
-               const KmerJob& km = KmerJob(), const std::string& lz_path = std::string())
+               const KmerJob& km = KmerJob(), const std::string& lz_path = std::string(), const std::string& lce_path = std::string())
 {
     if (p > std::numeric_limits<idx_t>::max()) { std::cerr << "subproblem-count does not fit the index type\n"; return EXIT_FAILURE; }
     // the bounded-context mode replays the reference's merge history, one GPU thread per merge node -- the top levels
@@ -199,6 +210,13 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
         }
         if (!out) return EXIT_FAILURE;
         std::cerr << "LZ77: " << parse.size() << " phrases written.\n";
+    }
+#endif
+#ifndef CAPS_CLI_NO_LCE
+    if (!lce_path.empty()) {
+        const CaPS_SA::LCE_Index x = CaPS_SA::LCE_Index::build(suf_arr);
+        x.save(lce_path);
+        std::cerr << "LCE index: " << x.size() << " bytes written.\n";
     }
 #endif
     return 0;
@@ -423,6 +441,66 @@ static int fm_extract_main(const std::vector<std::string>& args)
     return 0;
 }
 
+// caps_sa --lce INDEX PAIRS [--mismatches K]: args = everything after the program name
+static int lce_main(const std::vector<std::string>& args)
+{
+#ifdef CAPS_CLI_NO_LCE
+    std::cerr << "--lce: not built into this driver\n";
+    return EXIT_FAILURE;
+#else
+    const char* usage = "--lce: usage: caps_sa --lce INDEX PAIRS [--mismatches K] (no other option or argument)\n";
+    if (args.size() < 3 || args[0] != "--lce" || (args.size() != 3 && args.size() != 5) || args[1].compare(0, 2, "--") == 0 ||
+        args[2].compare(0, 2, "--") == 0) {
+        std::cerr << usage;
+        return EXIT_FAILURE;
+    }
+    size_t k = 0;
+    if (args.size() == 5 && (args[3] != "--mismatches" || !parse_count(args[4], k) || k > 1024)) {
+        std::cerr << "--mismatches: needs a number in 0 .. 1024\n" << usage;
+        return EXIT_FAILURE;
+    }
+    std::string lines;
+    if (!read_input(args[2], lines)) { std::cerr << "--lce: no pairs read\n"; return EXIT_FAILURE; }
+    std::vector<uint64_t> I, J;
+    size_t line_no = 0;
+    for (size_t a = 0; a < lines.size();) {                  // "i j", one blank or tab between them, nothing else
+        size_t b = lines.find('\n', a);
+        if (b == std::string::npos) b = lines.size();
+        size_t e = b;
+        if (e > a && lines[e - 1] == '\r') --e;
+        ++line_no;
+        const std::string line = lines.substr(a, e - a);
+        const size_t sp = line.find_first_of(" \t");
+        size_t i = 0, j = 0;
+        if (sp == std::string::npos || !parse_count(line.substr(0, sp), i) || !parse_count(line.substr(sp + 1), j)) {
+            std::cerr << "--lce: " << args[2] << " line " << line_no << ": expected \"i j\", two numbers\n";
+            return EXIT_FAILURE;
+        }
+        I.push_back(i);
+        J.push_back(j);
+        a = b + 1;
+    }
+    try {
+        const CaPS_SA::LCE_Index x = CaPS_SA::LCE_Index::load(args[1]);
+        if (x.size() < 256 || std::memcmp(x.data(), "CAPSLCE1", 8) != 0) {
+            std::cerr << "--lce: " << args[1] << " is not an LCE index of this library\n";
+            return EXIT_FAILURE;
+        }
+        for (size_t q = 0; q < I.size(); ++q)
+            if (I[q] >= x.n() || J[q] >= x.n()) {
+                std::cerr << "--lce: " << args[2] << " line " << q + 1 << ": a position is past the text (n = " << x.n() << ")\n";
+                return EXIT_FAILURE;
+            }
+        const std::vector<uint64_t> len = x.lce(I, J, k);
+        for (size_t q = 0; q < len.size(); ++q) std::cout << len[q] << '\n';
+    } catch (const std::exception& e) {
+        std::cerr << "--lce: " << e.what() << "\n";
+        return EXIT_FAILURE;
+    }
+    return 0;
+#endif
+}
+
 // caps_sa --inverse-bwt IN OUT: args = everything after the program name
 static int inverse_bwt_main(const std::vector<std::string>& args)
 {
@@ -460,7 +538,11 @@ int main(int argc, char* argv[])
         if (std::strcmp(argv[i], "--fm-from-bwt") == 0) return fm_from_bwt_main(std::vector<std::string>(argv + 1, argv + argc));
     for (int i = 1; i < argc; ++i)
         if (std::strcmp(argv[i], "--fm-extract") == 0) return fm_extract_main(std::vector<std::string>(argv + 1, argv + argc));
+    for (int i = 1; i < argc; ++i)
+        if (std::strcmp(argv[i], "--lce") == 0) return lce_main(std::vector<std::string>(argv + 1, argv + argc));
     std::vector<std::string> pos;
+    std::string lce_path;                                  // --lce-index (empty: not asked for)
+    bool lce = false;
     bool pretty = false, bwt = false, fm = false, fm_sample_given = false, fm_text_given = false, raw = false;
     size_t gpus = 1, fm_sample = 32, fm_text_sample = 0;
     std::string bwt_path, fm_path;
@@ -488,6 +570,13 @@ int main(int argc, char* argv[])
             lz = true;
             lz_path = argv[++i];
         }
+        else if (std::strcmp(argv[i], "--lce-index") == 0) {
+            if (lce) { std::cerr << "--lce-index: given twice\n"; return EXIT_FAILURE; }
+            if (i + 1 >= argc || std::strncmp(argv[i + 1], "--", 2) == 0) { std::cerr << "--lce-index: usage: --lce-index PATH\n"; return EXIT_FAILURE; }
+            lce = true;
+            lce_path = argv[++i];
+        }
+        else if (std::strcmp(argv[i], "--mismatches") == 0) { std::cerr << "--mismatches: only with --lce\n"; return EXIT_FAILURE; }
         else if (std::strcmp(argv[i], "--min-count") == 0 || std::strcmp(argv[i], "--max-count") == 0) {
             const bool lo = std::strcmp(argv[i], "--min-count") == 0;
             size_t v = 0;
@@ -530,7 +619,9 @@ int main(int argc, char* argv[])
         std::cerr << "Usage: caps_sa <input_path> <output_path> <(optional)-subproblem-count> "
                      "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH> "
                      "<(optional)--fm-index PATH [--fm-sample S] [--fm-text-sample T]> <(optional)--raw> "
-                     "<(optional)--kmers K PATH [--min-count A] [--max-count B]> <(optional)--kmer-spectrum K PATH> <(optional)--lz77 PATH>\n"
+                     "<(optional)--kmers K PATH [--min-count A] [--max-count B]> <(optional)--kmer-spectrum K PATH> <(optional)--lz77 PATH> "
+                     "<(optional)--lce-index PATH>\n"
+                     "       caps_sa --lce INDEX PAIRS [--mismatches K]\n"
                      "       caps_sa --inverse-bwt IN.bwt OUT\n"
                      "       caps_sa --fm-search INDEX PATTERNS [--locate K]\n"
                      "       caps_sa --fm-mems INDEX PATTERNS [--min-len L]\n"
@@ -578,6 +669,17 @@ int main(int argc, char* argv[])
             return EXIT_FAILURE;
         }
     }
+    // --lce-index: the same manners
+#ifdef CAPS_CLI_NO_LCE
+    if (lce) { std::cerr << "--lce-index: not built into this driver\n"; return EXIT_FAILURE; }
+#endif
+    if (lce) {
+        struct stat sb;
+        if (ctx != 0 && stat(pos[0].c_str(), &sb) == 0 && ctx < static_cast<size_t>(sb.st_size)) {
+            std::cerr << "--lce-index: a bounded-context order (bounded-context " << ctx << ") is not a suffix array and has no LCE index\n";
+            return EXIT_FAILURE;
+        }
+    }
     // --fm-index: the same manners
     if (fm_sample_given && !fm) { std::cerr << "--fm-sample: only with --fm-index PATH\n"; return EXIT_FAILURE; }
     if (fm_text_given && !fm) { std::cerr << "--fm-text-sample: only with --fm-index PATH or --fm-from-bwt\n"; return EXIT_FAILURE; }
@@ -620,8 +722,8 @@ int main(int argc, char* argv[])
 
     std::cerr << "Text length: " << text.size() << ".\n";
     try {
-        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path);
-        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path);
+        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path, lce_path);
+        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path, lce_path);
     } catch (const std::exception& e) {
         std::cerr << e.what() << "\n";
         return EXIT_FAILURE;

@@ -7310,4 +7310,302 @@ GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lz_walk_kernel(KCTX const idx_t* __restrict__ LPF
     }
 }
 
+// ---- ISA and the LCE index (capi_impl.h isa_* / lce_*; include/caps_sa_hip.h "ISA and longest common extensions") ----------------------
+// ISA[SA[r]] = r, and an index that answers range_min(lo, hi) = min LCP[lo .. hi] over ranks and, from it, the longest common extension
+// of two text positions with up to k mismatches (kangaroo jumps).  The blob holds ISA, a copy of LCP with entry 0 stored as 0, and two
+// tiers of sparse tables: M_j[b] = the minimum of the blocks b .. b + 2^j - 1 (blocks of LCE_BLOCK ranks, j = 0 .. 6) and T_j[s] = the
+// minimum of the superblocks s .. s + 2^j - 1 (LCE_SUPER ranks, j = 0 .. floor(log2 ns)), both clipped at the end of the array.
+//   isa_scatter_kernel    SA streamed with 16-byte loads, one scattered store per rank into a destination preset to all ones; a value
+//                         >= n is never used as an index and raises bit 0 of *bad
+//   isa_check_kernel      streams the destination: a slot that is still all ones raises bit 1 (with n in-range stores, no empty slot
+//                         means a permutation: a duplicate leaves a slot empty)
+//   lce_block_kernel      one pass over LCP: the copy and M_0, the chunk minima through LDS (lpf_block_kernel's shape)
+//   lce_table_kernel      one level from another: dst[x] = min(src[x * mul], src[x * mul + half]) -- M_j from M_{j-1} (mul 1, half
+//                         2^(j-1)), T_0 from M_6 at superblock starts (mul 64, half 0), T_j from T_{j-1}
+//   lce_range_min_kernel  one lane per query: the two partial blocks by 16-byte loads (single entries only at their unaligned ends), the
+//   lce_query_kernel      whole blocks between them by two overlapping reads of M_j, or by M_j up to the next superblock edge, T_j over
+//                         the whole superblocks, M_j from the last edge: at most 126 LCP reads and 6 table reads for ANY blob body; a
+//                         round of lce adds 2 ISA reads, clamped to n - 1.  Nothing walks a data-dependent distance.
+// LCE_BLOCK and LCE_SUPER are the blob's format: the same in every build, the small-tile emulation builds included.
+constexpr uint32_t LCE_BLOCK = 64;
+constexpr uint32_t LCE_SUPER = 4096;
+constexpr uint32_t LCE_BPS = LCE_SUPER / LCE_BLOCK;               // blocks of a superblock
+constexpr uint32_t LCE_MLEVELS = 7;                               // M_0 .. M_6: runs of up to 64 blocks
+constexpr uint32_t LCE_MAX_TLEVELS = 64;
+constexpr uint32_t LCE_MAX_MISMATCHES = 1024;
+static_assert(LCE_BPS == (1u << (LCE_MLEVELS - 1)), "M_6 at a superblock start is the superblock");
+
+// the kernels' view of a checked blob (capi_impl.h lce_check_header): section pointers, strides between the levels in bytes
+struct LceView {
+    uint64_t n = 0, nb = 0, ns = 0;
+    uint32_t tlevels = 0;                                          // T_0 .. T_{tlevels - 1}
+    const char* isa = nullptr;
+    const char* lcp = nullptr;
+    const char* m = nullptr;
+    const char* t = nullptr;
+    uint64_t m_stride = 0, t_stride = 0;
+};
+
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) isa_scatter_kernel(KCTX const idx_t* __restrict__ SA, uint64_t n, idx_t* __restrict__ ISA, uint32_t* __restrict__ bad)
+{
+    constexpr uint32_t PER = KmerGeom<idx_t>::PER;
+    const uint64_t chunks = (n + PER - 1) / PER;
+    PAR(tid) {
+        for (uint64_t c = (uint64_t)K_BLOCK_IDX * FM_NT + tid; c < chunks; c += (uint64_t)K_GRID_DIM * FM_NT) {
+            const uint64_t i0 = c * PER;
+            const KmerChunk<idx_t> s = kmer_load<idx_t>(SA, n, i0);
+            UNROLL
+            for (uint32_t j = 0; j < PER; ++j) {
+                if (i0 + j >= n) break;
+                const uint64_t v = (uint64_t)s.v[j];
+                if (v < n) ISA[v] = (idx_t)(i0 + j);
+                else ATOMIC_OR_U32(bad, 1u);
+            }
+        }
+    }
+}
+
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) isa_check_kernel(KCTX const idx_t* __restrict__ ISA, uint64_t n, uint32_t* __restrict__ bad)
+{
+    constexpr uint32_t PER = KmerGeom<idx_t>::PER;
+    constexpr idx_t TOP = (idx_t)~(idx_t)0;
+    const uint64_t chunks = (n + PER - 1) / PER;
+    PAR(tid) {
+        bool empty = false;
+        for (uint64_t c = (uint64_t)K_BLOCK_IDX * FM_NT + tid; c < chunks; c += (uint64_t)K_GRID_DIM * FM_NT) {
+            const uint64_t i0 = c * PER;
+            const KmerChunk<idx_t> s = kmer_load<idx_t>(ISA, n, i0);
+            UNROLL
+            for (uint32_t j = 0; j < PER; ++j) empty = empty || (i0 + j < n && s.v[j] == TOP);
+        }
+        if (empty) ATOMIC_OR_U32(bad, 2u);
+    }
+}
+
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lce_block_kernel(KCTX const idx_t* __restrict__ LCP, uint64_t n, uint64_t n_tiles, uint64_t nb,
+                                                 idx_t* __restrict__ copy, idx_t* __restrict__ M0)
+{
+    constexpr uint32_t PER = KmerGeom<idx_t>::PER, CH = LCE_SUPER / PER, CPB = LCE_BLOCK / PER;
+    constexpr idx_t TOP = (idx_t)~(idx_t)0;
+    SHARED_ARRAY(idx_t, cl, CH);
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t t0 = tile * LCE_SUPER;
+        PAR(tid) {
+            for (uint32_t c = tid; c < CH; c += FM_NT) {
+                const uint64_t i0 = t0 + (uint64_t)c * PER;
+                idx_t ml = TOP;
+                if (i0 < n) {
+                    KmerChunk<idx_t> l = kmer_load<idx_t>(LCP, n, i0);
+                    if (i0 == 0) l.v[0] = 0;                                         // LCP[0] counts as 0 and is stored as 0
+                    UNROLL
+                    for (uint32_t j = 0; j < PER; ++j) ml = i0 + j < n && l.v[j] < ml ? l.v[j] : ml;
+                    if (i0 + PER <= n) {
+                        *reinterpret_cast<KmerChunk<idx_t>*>(copy + i0) = l;
+                    } else {
+                        for (uint32_t j = 0; i0 + j < n; ++j) copy[i0 + j] = l.v[j];
+                    }
+                }
+                cl[c] = ml;
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            for (uint32_t b = tid; b < LCE_BPS; b += FM_NT) {
+                const uint64_t g = tile * LCE_BPS + b;
+                if (g < nb) {
+                    idx_t ml = TOP;
+                    for (uint32_t c = 0; c < CPB; ++c) {
+                        const idx_t d = cl[b * CPB + c];
+                        ml = d < ml ? d : ml;
+                    }
+                    M0[g] = ml;
+                }
+            }
+        }
+        SYNC();
+    }
+}
+
+// dst[x] = min(src[x * mul], src[x * mul + half]) for x < n_dst; the second only where half != 0 and it exists
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lce_table_kernel(KCTX const idx_t* __restrict__ src, uint64_t n_src, idx_t* __restrict__ dst, uint64_t n_dst,
+                                                 uint64_t mul, uint64_t half)
+{
+    PAR(tid) {
+        for (uint64_t x = (uint64_t)K_BLOCK_IDX * FM_NT + tid; x < n_dst; x += (uint64_t)K_GRID_DIM * FM_NT) {
+            const uint64_t a = x * mul;
+            if (a >= n_src) continue;                                                // (never, for the shapes the host launches)
+            idx_t m = src[a];
+            if (half && a + half < n_src) {
+                const idx_t d = src[a + half];
+                m = d < m ? d : m;
+            }
+            dst[x] = m;
+        }
+    }
+}
+
+// min of m and LCP over two rank ranges [a0, e0) and [a1, e1), each inside one block and inside the array, either may be empty: single
+// entries up to the first 16-byte edge and behind the last, 16-byte chunks between.  A query is a chain of dependent rounds (load,
+// wait, fold), and a wave makes as many as its slowest lane.  So the two ranges share their rounds; the single entries of all four ends
+// are loaded up front and folded last; and the chunks go U at a time per range, in order (taking every R-th chunk per round instead, so
+// that the first round touches every line, was measured and is slower: a range of 8 chunks then needs 4 rounds, not 2).
+template <typename idx_t>
+DEV_INLINE idx_t lce_scan2(const idx_t* __restrict__ lcp, uint64_t a0, uint64_t e0, uint64_t a1, uint64_t e1, idx_t m)
+{
+    constexpr uint32_t PER = KmerGeom<idx_t>::PER, U = 4;
+    constexpr idx_t TOP = (idx_t)~(idx_t)0;
+    const uint64_t lo[2] = {a0, a1}, hi[2] = {e0 > a0 ? e0 : a0, e1 > a1 ? e1 : a1};
+    uint64_t c0[2], c1[2];                                                          // the whole chunks of a range are [c0, c1)
+    idx_t v[2][2][PER];
+    UNROLL
+    for (uint32_t r = 0; r < 2; ++r) {
+        const uint64_t edge = (lo[r] + PER - 1) & ~(uint64_t)(PER - 1);
+        c0[r] = edge < hi[r] ? edge : hi[r];
+        c1[r] = c0[r] + ((hi[r] - c0[r]) & ~(uint64_t)(PER - 1));
+        UNROLL
+        for (uint32_t s = 0; s + 1 < PER; ++s) {
+            v[r][0][s] = lo[r] + s < c0[r] ? lcp[lo[r] + s] : TOP;
+            v[r][1][s] = c1[r] + s < hi[r] ? lcp[c1[r] + s] : TOP;
+        }
+    }
+    for (uint64_t k = 0; c0[0] + k < c1[0] || c0[1] + k < c1[1]; k += (uint64_t)U * PER) {
+        KmerChunk<idx_t> ch[2][U];
+        UNROLL
+        for (uint32_t r = 0; r < 2; ++r) {
+            UNROLL
+            for (uint32_t u = 0; u < U; ++u) {
+                const uint64_t at = c0[r] + k + (uint64_t)u * PER;
+                if (at < c1[r]) {
+                    ch[r][u] = *reinterpret_cast<const KmerChunk<idx_t>*>(lcp + at);
+                } else {
+                    UNROLL
+                    for (uint32_t j = 0; j < PER; ++j) ch[r][u].v[j] = TOP;
+                }
+            }
+        }
+        UNROLL
+        for (uint32_t r = 0; r < 2; ++r) {
+            UNROLL
+            for (uint32_t u = 0; u < U; ++u) {
+                UNROLL
+                for (uint32_t j = 0; j < PER; ++j) m = ch[r][u].v[j] < m ? ch[r][u].v[j] : m;
+            }
+        }
+    }
+    UNROLL
+    for (uint32_t r = 0; r < 2; ++r) {
+        UNROLL
+        for (uint32_t s = 0; s + 1 < PER; ++s) {
+            m = v[r][0][s] < m ? v[r][0][s] : m;
+            m = v[r][1][s] < m ? v[r][1][s] : m;
+        }
+    }
+    return m;
+}
+// `cnt` entries from `first` (1 <= cnt, first + cnt <= size) of the table tier at base are covered by the first and the last 2^level
+// entries of the run, level = floor(log2 cnt): the table of that level and the two indices.  Level and indices are clamped to the
+// tier, whatever the arguments.
+template <typename idx_t>
+DEV_INLINE void lce_cover(const char* __restrict__ base, uint64_t stride, uint32_t levels, uint64_t size, uint64_t first, uint64_t cnt,
+                          const idx_t*& tab, uint64_t& x, uint64_t& y)
+{
+    uint32_t j = 63u - (uint32_t)caps_clz64(cnt | 1);
+    j = j < levels ? j : levels - 1;
+    tab = reinterpret_cast<const idx_t*>(base + (uint64_t)j * stride);
+    const uint64_t w = (uint64_t)1 << j;
+    x = first;
+    y = first + cnt - (cnt < w ? cnt : w);
+    x = x < size ? x : size - 1;
+    y = y < size ? y : size - 1;
+}
+// range_min(lo, hi), lo <= hi < v.n.  The (up to six) table reads are issued first, so that they are in flight during the scans.
+template <typename idx_t>
+DEV_INLINE idx_t lce_range_min(const LceView& v, uint64_t lo, uint64_t hi)
+{
+    constexpr idx_t TOP = (idx_t)~(idx_t)0;
+    const idx_t* __restrict__ lcp = reinterpret_cast<const idx_t*>(v.lcp);
+    const uint64_t bl = lo / LCE_BLOCK, bh = hi / LCE_BLOCK;
+    const bool head_whole = lo % LCE_BLOCK == 0, tail_whole = hi % LCE_BLOCK == LCE_BLOCK - 1 || hi == v.n - 1;
+    if (bl == bh && !(head_whole && tail_whole)) return lce_scan2<idx_t>(lcp, lo, hi + 1, 0, 0, TOP);
+    const uint64_t fb = head_whole ? bl : bl + 1, le = tail_whole ? bh + 1 : bh;    // the whole blocks fb .. le - 1
+    const uint64_t cnt = le > fb ? le - fb : 0;
+    // three runs: blocks (all of them if at most 64, else those up to the next superblock edge), blocks from the last edge, superblocks
+    uint64_t e1 = (fb + LCE_BPS - 1) / LCE_BPS * LCE_BPS, e2 = le / LCE_BPS * LCE_BPS;   // superblock edges, e1 <= e2 where cnt > 64
+    const bool small = cnt <= LCE_BPS;
+    const uint64_t cA = small ? cnt : e1 - fb, cB = small ? 0 : le - e2, cC = small ? 0 : (e2 - e1) / LCE_BPS;
+    const idx_t* tA = nullptr;
+    const idx_t* tB = nullptr;
+    const idx_t* tC = nullptr;
+    uint64_t xA = 0, yA = 0, xB = 0, yB = 0, xC = 0, yC = 0;
+    idx_t r0 = TOP, r1 = TOP, r2 = TOP, r3 = TOP, r4 = TOP, r5 = TOP;
+    if (cA) { lce_cover<idx_t>(v.m, v.m_stride, LCE_MLEVELS, v.nb, fb, cA, tA, xA, yA); r0 = tA[xA]; r1 = tA[yA]; }
+    if (cB) { lce_cover<idx_t>(v.m, v.m_stride, LCE_MLEVELS, v.nb, e2, cB, tB, xB, yB); r2 = tB[xB]; r3 = tB[yB]; }
+    if (cC) { lce_cover<idx_t>(v.t, v.t_stride, v.tlevels, v.ns, e1 / LCE_BPS, cC, tC, xC, yC); r4 = tC[xC]; r5 = tC[yC]; }
+    idx_t m = lce_scan2<idx_t>(lcp, lo, head_whole ? lo : (bl + 1) * LCE_BLOCK, bh * LCE_BLOCK, tail_whole ? bh * LCE_BLOCK : hi + 1, TOP);
+    m = r0 < m ? r0 : m;
+    m = r1 < m ? r1 : m;
+    m = r2 < m ? r2 : m;
+    m = r3 < m ? r3 : m;
+    m = r4 < m ? r4 : m;
+    return r5 < m ? r5 : m;
+}
+
+// out[x] = range_min(lo[x], hi[x]); lo > hi or hi >= n: 0 and bit 0 of *flags
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lce_range_min_kernel(KCTX LceView v, const uint64_t* __restrict__ lo, const uint64_t* __restrict__ hi, uint64_t q,
+                                                     uint64_t* __restrict__ out, uint32_t* __restrict__ flags)
+{
+    PAR(tid) {
+        for (uint64_t x = (uint64_t)K_BLOCK_IDX * FM_NT + tid; x < q; x += (uint64_t)K_GRID_DIM * FM_NT) {
+            const uint64_t a = lo[x], b = hi[x];
+            if (a > b || b >= v.n) {
+                out[x] = 0;
+                ATOMIC_OR_U32(flags, 1u);
+                continue;
+            }
+            out[x] = (uint64_t)lce_range_min<idx_t>(v, a, b);
+        }
+    }
+}
+
+// out[x] = lce(I[x], J[x], k) by kangaroo jumps: at most k + 1 rounds of two ISA reads and one range minimum.  A position >= n: 0 and
+// bit 0 of *flags.  Two equal ranks (no permutation) extend by 0.
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lce_query_kernel(KCTX LceView v, const uint64_t* __restrict__ I, const uint64_t* __restrict__ J, uint64_t q,
+                                                 uint32_t k, uint64_t* __restrict__ out, uint32_t* __restrict__ flags)
+{
+    const idx_t* __restrict__ isa = reinterpret_cast<const idx_t*>(v.isa);
+    PAR(tid) {
+        for (uint64_t x = (uint64_t)K_BLOCK_IDX * FM_NT + tid; x < q; x += (uint64_t)K_GRID_DIM * FM_NT) {
+            const uint64_t i = I[x], j = J[x];
+            if (i >= v.n || j >= v.n) {
+                out[x] = 0;
+                ATOMIC_OR_U32(flags, 1u);
+                continue;
+            }
+            const uint64_t room = v.n - (i > j ? i : j);                             // no extension is longer
+            uint64_t l = room;
+            if (i != j) {
+                l = 0;
+                for (uint32_t used = 0;; ++used) {
+                    uint64_t a = (uint64_t)isa[i + l], b = (uint64_t)isa[j + l];
+                    a = a < v.n ? a : v.n - 1;
+                    b = b < v.n ? b : v.n - 1;
+                    uint64_t e = 0;
+                    if (a != b) e = (uint64_t)lce_range_min<idx_t>(v, (a < b ? a : b) + 1, a < b ? b : a);
+                    l += e < room - l ? e : room - l;
+                    if (l == room || used == k) break;
+                    ++l;                                                             // the mismatch
+                    if (l == room) break;
+                }
+            }
+            out[x] = l;
+        }
+    }
+}
+
 }  // namespace caps

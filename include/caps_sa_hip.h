@@ -746,6 +746,75 @@ int caps_sa_hip_lz77_u32(const uint32_t* SA, const uint32_t* LCP, uint64_t n, vo
 int caps_sa_hip_lz77_u64(const uint64_t* SA, const uint64_t* LCP, uint64_t n, void* records, uint64_t capacity, uint64_t* n_phrases,
                          int device);
 
+/* ---- ISA and longest common extensions ---------------------------------------------
+ * The inverse suffix array, and an index over (SA, LCP) that answers range minima over LCP and, from them, the longest common
+ * extension of two text positions, exact or with up to k mismatches. n entries of width W (4 or 8 bytes); SA is a permutation of
+ * 0 .. n - 1; LCP is any array, and LCP[0] counts as 0 whatever it holds.
+ *   - ISA[SA[r]] = r.
+ *   - range_min(lo, hi) = min LCP[lo .. hi] for RANKS lo <= hi < n, both ends inclusive, LCP[0] read as 0.
+ *   - lce0(i, j) for positions i, j < n: n - i if i == j; otherwise min(range_min(min(a, b) + 1, max(a, b)), n - max(i, j)) with
+ *     a = ISA[i], b = ISA[j]. For the arrays of a full-context build the clamp never bites; it keeps every read in range for any
+ *     arrays. (Two equal ranks, which no permutation has, extend by 0.)
+ *   - lce(i, j, k), 0 <= k <= 1024: the largest l <= n - max(i, j) such that T[i .. i + l) and T[j .. j + l) differ in at most k
+ *     places, by kangaroo jumps: l = 0, used = 0; (2) l += lce0(i + l, j + l); stop if max(i, j) + l == n or used == k; otherwise
+ *     l += 1, used += 1 and again from (2). At most k + 1 rounds.
+ *
+ * isa: dISA is n entries of the index width. A value SA[r] >= n is never used as an index; it, or a value that occurs twice (the
+ * destination is preset to all ones and a slot still all ones afterwards is a position no rank names), is CAPS_SA_EINVAL ("not a
+ * suffix array"). dISA is then unspecified (the host form leaves ISA as it was).
+ *
+ * The index is one relocatable blob, little-endian, every section rounded up to 256 bytes with zero padding (equal inputs give equal
+ * blobs). B = 64 ranks per block, nb = ceil(n / 64); S = 4,096 ranks per superblock, ns = ceil(n / 4096); tl = 0 if n = 0, else
+ * floor(log2 ns) + 1; up(b) = b rounded up to 256.
+ *     offset                       bytes          content
+ *     0                            256            header: 32 u64 words
+ *                                                   0 magic "CAPSLCE1" (0x3145434C53504143)   1 version = 1     2 n
+ *                                                   3 W (4 or 8)    4 B = 64    5 S = 4096    6 nb    7 ns    8 tl
+ *                                                   9 off_isa    10 off_lcp    11 off_m    12 m_stride = up(nb W)
+ *                                                   13 off_t     14 t_stride = up(ns W)    15 total    16 .. 31 zero
+ *     off_isa = 256                up(n W)        ISA[n]
+ *     off_lcp = off_isa + up(n W)  up(n W)        LCP[n], entry 0 stored as 0
+ *     off_m = off_lcp + up(n W)    7 m_stride     M_0 .. M_6, nb entries each: M_j[b] = min LCP over the blocks
+ *                                                 b .. min(b + 2^j, nb) - 1
+ *     off_t = off_m + 7 m_stride   tl t_stride    T_0 .. T_{tl-1}, ns entries each: T_j[s] = min LCP over the superblocks
+ *                                                 s .. min(s + 2^j, ns) - 1
+ *     total = off_t + tl t_stride
+ * caps_sa_hip_lce_index_bytes gives total: below 2 n W + n W / 8 + 16 KiB. The build needs no workspace beyond the blob, and the
+ * blob alone answers queries: SA and LCP may be freed. Every header word follows from n and W: the query calls recompute all 32 on
+ * the host and compare before a kernel reads the body; a blob with any other header, or longer than index_bytes, is CAPS_SA_EINVAL.
+ * The body is not checked and need not be: for ANY body a range minimum makes at most 126 LCP reads and 6 table reads at addresses
+ * that follow from (lo, hi) alone, a round of lce adds 2 ISA reads whose values are clamped to n - 1, and nothing walks a
+ * data-dependent distance. A range minimum scans the partial blocks at its two ends (a block the range covers whole is taken from
+ * M_0 instead), covers up to 64 whole blocks between them by two overlapping reads of M_j, j = floor(log2 count), and more than 64
+ * by the blocks up to the next superblock edge (two reads of M_j), the whole superblocks (two reads of T_j) and the blocks from the
+ * last edge (two reads of M_j).
+ *
+ * Queries: dLo, dHi, dI, dJ, dMin, dLen are u64[q]; the index width is read from the blob. A range with lo > hi or hi >= n, or a
+ * position >= n, writes 0 to its slot and the call returns CAPS_SA_EINVAL after answering the others. Also CAPS_SA_EINVAL, checked
+ * before any allocation, nothing written: a null pointer with n > 0 or q > 0, a null or not 16-byte aligned index, n > UINT32_MAX
+ * with _u32, index_bytes below caps_sa_hip_lce_index_bytes (build) or below the blob (query), mismatches > 1024. n = 0 and q = 0
+ * succeed. Device pointers are on the current device; the work runs on hip_stream and has completed on return. The host forms run
+ * in the device block of the host-buffer builds; the blob a host build made, or the last one a host query uploaded, stays resident
+ * there and is not uploaded again. Ranks beyond 2^32 (_u64 with n > UINT32_MAX) are untested: _u64 is tested at small sizes only.
+ */
+int caps_sa_hip_isa_device_u32(const void* dSA, uint64_t n, void* dISA, void* hip_stream);
+int caps_sa_hip_isa_device_u64(const void* dSA, uint64_t n, void* dISA, void* hip_stream);
+int caps_sa_hip_isa_u32(const uint32_t* SA, uint64_t n, uint32_t* ISA, int device);
+int caps_sa_hip_isa_u64(const uint64_t* SA, uint64_t n, uint64_t* ISA, int device);
+int caps_sa_hip_lce_index_bytes(uint64_t n, int idx_bytes, uint64_t* bytes);
+int caps_sa_hip_lce_build_device_u32(const void* dSA, const void* dLCP, uint64_t n, void* dIndex, uint64_t index_bytes, void* hip_stream);
+int caps_sa_hip_lce_build_device_u64(const void* dSA, const void* dLCP, uint64_t n, void* dIndex, uint64_t index_bytes, void* hip_stream);
+int caps_sa_hip_lce_build_u32(const uint32_t* SA, const uint32_t* LCP, uint64_t n, void* index, uint64_t index_bytes, int device);
+int caps_sa_hip_lce_build_u64(const uint64_t* SA, const uint64_t* LCP, uint64_t n, void* index, uint64_t index_bytes, int device);
+int caps_sa_hip_lce_range_min_device(const void* dIndex, uint64_t index_bytes, const void* dLo, const void* dHi, uint64_t q, void* dMin,
+                                     void* hip_stream);
+int caps_sa_hip_lce_range_min(const void* index, uint64_t index_bytes, const uint64_t* lo, const uint64_t* hi, uint64_t q, uint64_t* min,
+                              int device);
+int caps_sa_hip_lce_device(const void* dIndex, uint64_t index_bytes, const void* dI, const void* dJ, uint64_t q, uint64_t mismatches,
+                           void* dLen, void* hip_stream);
+int caps_sa_hip_lce(const void* index, uint64_t index_bytes, const uint64_t* i, const uint64_t* j, uint64_t q, uint64_t mismatches,
+                    uint64_t* len, int device);
+
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
 /* merge_sort (src/Suffix_Array.cpp:112-129) of an arbitrary list of cnt distinct suffix
