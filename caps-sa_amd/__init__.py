@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from ._binding import CapsLib, CapsSaError, Stats, Shard, ShardInfo, EXPORTS, MEM_DTYPE, KMER_DTYPE, LZ_DTYPE, LZ_LITERAL  # noqa: F401
+from ._binding import CapsLib, CapsSaError, Stats, Shard, ShardInfo, EXPORTS, MEM_DTYPE, KMER_DTYPE, LZ_DTYPE, LZ_LITERAL, CROSS_DTYPE, CROSS_MAX_OCC  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CAPS_SA_LIB selects a tuning variant built by `make variant` (benchmarking only).
@@ -88,6 +88,31 @@ def lz77(SA, LCP, device: int = 0, _lib: CapsLib | None = None) -> np.ndarray:
     return (_lib or lib()).lz77(SA, LCP, device=device)
 
 
+def _cross_result(rec, summary, sort: bool, return_summary: bool):
+    if sort:
+        rec = rec[np.argsort(rec["a"], kind="stable")]
+    return (rec, CapsLib.cross_summary(summary)) if return_summary else rec
+
+
+def cross_mums(SA, LCP, BWT, split: int, min_len: int = 1, sort: bool = False, return_summary: bool = False, device: int = 0,
+               _lib: CapsLib | None = None):
+    """The maximal unique matches between A = T[:split] (with its separator at split - 1) and B = T[split:], from the full-context
+    SA and LCP of T = A . sep . B and its BWT in rank order (include/caps_sa_hip.h "MUMs and MEMs between two texts"), e.g. arrays
+    read from a dump: a structured array (CROSS_DTYPE: a, b, len) -- T[a : a + len] == T[b : b + len], a on side A, b on side B, both
+    absolute in T -- in rank order, or ordered by ``a`` with sort=True.  return_summary=True: (records, dict with records,
+    skipped_runs, lcs_len, lcs_a, lcs_b -- the longest common substring of A and B).  The index width is SA's dtype."""
+    rec, summary = (_lib or lib()).cross_mums(SA, LCP, BWT, split, min_len, device=device)
+    return _cross_result(rec, summary, sort, return_summary)
+
+
+def cross_mems(SA, LCP, BWT, split: int, min_len: int = 1, max_occ: int = CROSS_MAX_OCC, sort: bool = False, return_summary: bool = False,
+               device: int = 0, _lib: CapsLib | None = None):
+    """Every maximal exact match of at least min_len bytes between A and B whose first min_len bytes occur at most max_occ (2 .. 64)
+    times in T, each once; the summary's skipped_runs counts the more frequent seeds that were left out."""
+    rec, summary = (_lib or lib()).cross_mems(SA, LCP, BWT, split, min_len, max_occ, device=device)
+    return _cross_result(rec, summary, sort, return_summary)
+
+
 class SuffixArray:
     """Python mirror of ``CaPS_SA::Suffix_Array<T_idx_>`` (include/Suffix_Array.hpp:22-181).
 
@@ -114,6 +139,7 @@ class SuffixArray:
         self._LCP = None
         self._BWT = None
         self._primary: int | None = None
+        self._cross_bwt = None                                   # the BWT made for cross_* by a build without bwt=True
         self.stats: dict | None = None
 
     def T(self) -> np.ndarray:
@@ -194,6 +220,46 @@ class SuffixArray:
         """The inverse suffix array: ISA()[SA()[r]] = r (the rank of every text position)."""
         SA, _ = self._kmer_arrays("ISA and the LCE index")
         return lib().isa(SA, self._bits, self._device)
+
+    def _cross_arrays(self):
+        """(SA, LCP, BWT in rank order): the BWT of a bwt=True build, otherwise made once from T and SA on the device
+        (caps_sa_hip_bwt_device_*; torch carries the arrays there and back)."""
+        SA, LCP = self._kmer_arrays("MUMs and MEMs")
+        if self._bwt:
+            return SA, LCP, self.BWT()
+        if self._cross_bwt is None:
+            import torch
+            dev = torch.device("cuda", self._device)
+            signed = np.int32 if self._bits == 32 else np.int64
+            dT = torch.from_numpy(self._T).to(dev)
+            dSA = torch.from_numpy(np.ascontiguousarray(SA).view(signed)).to(dev)
+            dB = torch.empty(self._n, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)
+            with torch.cuda.device(dev):
+                lib().bwt_device(dT.data_ptr(), self._n, dSA.data_ptr(), 0, self._n, dB.data_ptr(), self._bits)
+            self._cross_bwt = dB.cpu().numpy()
+        return SA, LCP, self._cross_bwt
+
+    def cross_mums(self, split: int, min_len: int = 1, sort: bool = False, return_summary: bool = False):
+        """The maximal unique matches between T()[:split] and T()[split:] (``caps_sa_amd.cross_mums``); the byte at split - 1 is
+        the separator and occurs nowhere else."""
+        SA, LCP, BWT = self._cross_arrays()
+        rec, summary = lib().cross_mums(SA, LCP, BWT, split, min_len, self._bits, self._device)
+        return _cross_result(rec, summary, sort, return_summary)
+
+    def cross_mems(self, split: int, min_len: int = 1, max_occ: int = CROSS_MAX_OCC, sort: bool = False, return_summary: bool = False):
+        """The maximal exact matches between the two sides whose first min_len bytes occur at most max_occ times
+        (``caps_sa_amd.cross_mems``)."""
+        SA, LCP, BWT = self._cross_arrays()
+        rec, summary = lib().cross_mems(SA, LCP, BWT, split, min_len, max_occ, self._bits, self._device)
+        return _cross_result(rec, summary, sort, return_summary)
+
+    def longest_common_substring(self, split: int):
+        """(len, a, b): the longest common substring of T()[:split] and T()[split:], T()[a : a + len] == T()[b : b + len] with a on
+        the first side; (0, 0, 0) when the sides share no byte."""
+        SA, LCP, BWT = self._cross_arrays()
+        _, summary = lib().cross_mums(SA, LCP, BWT, split, max(self._n, 1), self._bits, self._device)
+        return int(summary[2]), int(summary[3]), int(summary[4])
 
     def dump(self, path: str) -> None:
         """Suffix_Array::dump format (src/Suffix_Array.cpp:497-509): u64 n, SA, LCP."""

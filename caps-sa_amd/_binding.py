@@ -125,7 +125,7 @@ EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_b
            "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_from_bwt_workspace_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device",
            "fm_index_bytes_ex", "fm_add_text_samples", "fm_add_text_samples_device", "fm_extract_workspace_bytes", "fm_extract", "fm_extract_device",
            "fm_match", "fm_match_device", "fm_mems_workspace_bytes", "fm_mems", "fm_mems_device", "fm_wide_index_bytes",
-           "fm_wide_workspace_bytes", "kmer_workspace_bytes", "lpf_workspace_bytes", "lz77_workspace_bytes", "lce_index_bytes",
+           "fm_wide_workspace_bytes", "kmer_workspace_bytes", "cross_workspace_bytes", "lpf_workspace_bytes", "lz77_workspace_bytes", "lce_index_bytes",
            "lce_range_min", "lce_range_min_device", "lce", "lce_device"] + SHARD_EXPORTS + [
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
@@ -133,7 +133,8 @@ EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_b
                  "upper_bound", "lcp", "build_bwt", "bwt_device", "inverse_bwt", "inverse_bwt_device", "fm_build", "fm_build_device",
                  "fm_build_from_bwt", "fm_build_from_bwt_device", "fm_build_wide", "fm_build_wide_device",
                  "kmers", "kmers_device", "kmer_spectrum", "kmer_spectrum_device", "kmer_census", "kmer_census_device",
-                 "lpf", "lpf_device", "lz77", "lz77_device", "isa", "isa_device", "lce_build", "lce_build_device")
+                 "lpf", "lpf_device", "lz77", "lz77_device", "isa", "isa_device", "lce_build", "lce_build_device",
+                 "cross_mums", "cross_mums_device", "cross_mems", "cross_mems_device")
 ]
 
 
@@ -142,6 +143,10 @@ MEM_DTYPE = np.dtype([("pattern", "<u8"), ("start", "<u4"), ("length", "<u4"), (
 
 # a record of kmers (include/caps_sa_hip.h "k-mers from SA and LCP"): 24 bytes, little-endian
 KMER_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("pos", "<u8")])
+
+# a record of cross_mums / cross_mems (include/caps_sa_hip.h "MUMs and MEMs between two texts"): 24 bytes, little-endian
+CROSS_DTYPE = np.dtype([("a", "<u8"), ("b", "<u8"), ("len", "<u8")])
+CROSS_MAX_OCC = 64
 
 # a phrase of lz77 (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP"): 24 bytes, little-endian; src = LZ_LITERAL: one byte
 LZ_DTYPE = np.dtype([("pos", "<u8"), ("len", "<u8"), ("src", "<u8")])
@@ -230,6 +235,8 @@ class CapsLib:
         f("fm_wide_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
         f("kmer_workspace_bytes").restype = _ci
         f("kmer_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
+        f("cross_workspace_bytes").restype = _ci
+        f("cross_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
         for name in ("lpf_workspace_bytes", "lz77_workspace_bytes"):
             f(name).restype = _ci
             f(name).argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
@@ -260,6 +267,14 @@ class CapsLib:
             f(f"lz77_{sfx}").argtypes = [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _ci]
             f(f"lz77_device_{sfx}").restype = _ci
             f(f"lz77_device_{sfx}").argtypes = [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64, _vp]
+            f(f"cross_mums_{sfx}").restype = _ci
+            f(f"cross_mums_{sfx}").argtypes = [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _ci]
+            f(f"cross_mems_{sfx}").restype = _ci
+            f(f"cross_mems_{sfx}").argtypes = [_vp, _vp, _vp, _u64, _u64, _u64, ctypes.c_uint32, _vp, _u64, _vp, _ci]
+            f(f"cross_mums_device_{sfx}").restype = _ci
+            f(f"cross_mums_device_{sfx}").argtypes = [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp]
+            f(f"cross_mems_device_{sfx}").restype = _ci
+            f(f"cross_mems_device_{sfx}").argtypes = [_vp, _vp, _vp, _u64, _u64, _u64, ctypes.c_uint32, _vp, _u64, _vp, _vp, _u64, _vp]
             f(f"kmers_{sfx}").restype = _ci
             f(f"kmers_{sfx}").argtypes = [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _u64, ctypes.POINTER(_u64), _ci]
             f(f"kmers_device_{sfx}").restype = _ci
@@ -829,6 +844,63 @@ class CapsLib:
         self._check(self._f(f"kmer_census_device_{sfx}")(dSA_ptr or None, dLCP_ptr or None, n, max_k, distinct.ctypes.data,
                                                          unique.ctypes.data, dWS_ptr or None, ws_bytes, stream or None))
         return distinct, unique
+
+    # ------------------------------------------------------------------ MUMs and MEMs between two texts (include/caps_sa_hip.h)
+    def cross_workspace_bytes(self, n: int, idx_bits: int = 32) -> int:
+        out = _u64(0)
+        self._check(self._f("cross_workspace_bytes")(n, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    @staticmethod
+    def cross_summary(words) -> dict:
+        """The 8 summary words of a cross call as a dict."""
+        w = [int(x) for x in words]
+        return {"records": w[0], "skipped_runs": w[1], "lcs_len": w[2], "lcs_a": w[3], "lcs_b": w[4]}
+
+    def _cross(self, which: str, SA, LCP, BWT, split: int, min_len: int, max_occ, idx_bits, device: int):
+        SA, LCP, n, sfx = self._sa_lcp(SA, LCP, idx_bits)
+        BWT = np.ascontiguousarray(np.frombuffer(BWT, dtype=np.uint8) if isinstance(BWT, (bytes, bytearray)) else BWT, dtype=np.uint8)
+        if BWT.shape != SA.shape:
+            raise ValueError("BWT: one byte per rank")
+        summary = np.zeros(8, dtype=np.uint64)
+        args = (SA.ctypes.data if n else None, LCP.ctypes.data if n else None, BWT.ctypes.data if n else None, n, split, min_len)
+        if which == "mems":
+            args += (max_occ,)
+        f = self._f(f"cross_{which}_{sfx}")
+        self._check(f(*args, None, 0, summary.ctypes.data, device))
+        rec = np.zeros(int(summary[0]), dtype=CROSS_DTYPE)
+        if rec.size:
+            self._check(f(*args, rec.ctypes.data, rec.size, summary.ctypes.data, device))
+        return rec, summary
+
+    def cross_mums(self, SA, LCP, BWT, split: int, min_len: int = 1, idx_bits: int | None = None, device: int = 0):
+        """(records, summary): the maximal unique matches between T[:split] and T[split:] as a structured array (CROSS_DTYPE: a, b,
+        len) in rank order, and the 8 summary words.  The counting call, then the writing call."""
+        return self._cross("mums", SA, LCP, BWT, split, min_len, None, idx_bits, device)
+
+    def cross_mems(self, SA, LCP, BWT, split: int, min_len: int = 1, max_occ: int = CROSS_MAX_OCC, idx_bits: int | None = None,
+                   device: int = 0):
+        """(records, summary): the maximal exact matches whose first min_len bytes occur at most max_occ times in T, ordered by the
+        upper rank q ascending, then the lower rank p descending; summary[1] counts the runs skipped as too frequent."""
+        return self._cross("mems", SA, LCP, BWT, split, min_len, max_occ, idx_bits, device)
+
+    def cross_device(self, which: str, dSA_ptr: int, dLCP_ptr: int, dBWT_ptr: int, n: int, split: int, min_len: int, max_occ: int = CROSS_MAX_OCC,
+                     dRecords_ptr: int = 0, capacity: int = 0, dWS_ptr: int = 0, ws_bytes: int = 0, idx_bits: int = 32, stream: int = 0) -> np.ndarray:
+        """Device arrays -> the 8 summary words; which: "mums" or "mems".  dRecords_ptr 0: the counting call, else `capacity`
+        24-byte records may be written there.  More records than capacity: CapsSaError (code -1) whose summary attribute holds the
+        words."""
+        sfx, _ = _sfx(idx_bits)
+        summary = np.zeros(8, dtype=np.uint64)
+        args = (dSA_ptr or None, dLCP_ptr or None, dBWT_ptr or None, n, split, min_len)
+        if which == "mems":
+            args += (max_occ,)
+        rc = self._f(f"cross_{which}_device_{sfx}")(*args, dRecords_ptr or None, capacity, summary.ctypes.data, dWS_ptr or None, ws_bytes,
+                                                    stream or None)
+        if rc != 0:
+            err = CapsSaError(rc, self._f("last_error")().decode(errors="replace"))
+            err.summary = summary
+            raise err
+        return summary
 
     # ------------------------------------------------------------------ LPF and LZ77 (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP")
     def lpf_workspace_bytes(self, n: int, idx_bits: int = 32) -> int:

@@ -24,6 +24,9 @@
 //    factorization, from SA() and LCP() after a full-context construct() (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP").
 //  * ISA() (not in the reference): the inverse suffix array, after a full-context construct() (include/caps_sa_hip.h "ISA and longest
 //    common extensions"); and the class LCE_Index: batched longest common extensions and range minima over LCP from one blob.
+//  * cross_mums() / cross_mems() / longest_common_substring() (not in the reference): the maximal unique matches, the rare maximal exact
+//    matches and the longest common substring between T()[0 .. split) and T()[split .. n), from SA(), LCP() and the BWT after a
+//    full-context construct() / construct_bwt() (include/caps_sa_hip.h "MUMs and MEMs between two texts").
 //  * the free function inverse_bwt() (not in the reference): the text back from (BWT, primary).
 //  * the class FM_Index (not in the reference either): count, locate, matching statistics, MEMs and extract over (BWT, primary) and a sample of the SA.
 #ifndef CAPS_SA_AMD_SUFFIX_ARRAY_HPP
@@ -205,6 +208,32 @@ public:
         return out;
     }
 
+    // ---- MUMs and MEMs between two texts (include/caps_sa_hip.h "MUMs and MEMs between two texts"; not in the reference).  T() = A . sep . B
+    // with the separator -- a byte that occurs nowhere else -- at split - 1.  After a full-context construct() / construct_bwt(): with
+    // max_context set these throw std::invalid_argument.  The BWT is construct_bwt()'s; after a plain construct() it is gathered from T()
+    // and SA() on the host at the first call.  On devices()[0].
+    struct Match { uint64_t a, b, len; };                      // the ABI's 24-byte record: T()[a .. a + len) == T()[b .. b + len), a < split <= b
+    struct Cross_Summary { uint64_t records, skipped_runs, lcs_len, lcs_a, lcs_b; };
+    static constexpr uint32_t cross_max_occ = CAPS_SA_CROSS_MAX_OCC;
+    // the maximal unique matches of at least min_len bytes, in rank order
+    std::vector<Match> cross_mums(uint64_t split, uint64_t min_len = 1, Cross_Summary* summary = nullptr) const
+    {
+        return cross(false, split, min_len, 0, summary);
+    }
+    // every maximal exact match of at least min_len bytes whose first min_len bytes occur at most max_occ (2 .. 64) times in T(); the
+    // summary's skipped_runs counts the more frequent seeds that were left out
+    std::vector<Match> cross_mems(uint64_t split, uint64_t min_len = 1, uint32_t max_occ = CAPS_SA_CROSS_MAX_OCC, Cross_Summary* summary = nullptr) const
+    {
+        return cross(true, split, min_len, max_occ, summary);
+    }
+    // the longest common substring of T()[0 .. split) and T()[split .. n): a = the position in the first side; len 0: none
+    Match longest_common_substring(uint64_t split) const
+    {
+        Cross_Summary s{};
+        cross(false, split, std::max<uint64_t>(static_cast<uint64_t>(n_), 1), 0, &s);
+        return Match{s.lcs_a, s.lcs_b, s.lcs_len};
+    }
+
     // ---- the inverse suffix array (include/caps_sa_hip.h "ISA and longest common extensions"; not in the reference): ISA()[SA()[r]] = r.
     // After a full-context construct(); with max_context set it throws std::invalid_argument.  On devices()[0].
     std::vector<idx_t> ISA() const
@@ -262,6 +291,48 @@ private:
         if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_lz77: ") + caps_sa_hip_last_error());
         return true;
     }
+
+    // false: the buffer was too small and the summary says how many records there are; any other failure throws
+    bool cross_call(bool mems, const uint8_t* bwt, uint64_t split, uint64_t min_len, uint32_t max_occ, void* records, uint64_t capacity, uint64_t* summary) const
+    {
+        const uint32_t* s32 = reinterpret_cast<const uint32_t*>(SA_);
+        const uint32_t* l32 = reinterpret_cast<const uint32_t*>(LCP_);
+        const uint64_t* s64 = reinterpret_cast<const uint64_t*>(SA_);
+        const uint64_t* l64 = reinterpret_cast<const uint64_t*>(LCP_);
+        const bool narrow = std::is_same<idx_t, uint32_t>::value;
+        const int rc = mems
+            ? (narrow ? caps_sa_hip_cross_mems_u32(s32, l32, bwt, n_, split, min_len, max_occ, records, capacity, summary, devices_[0])
+                      : caps_sa_hip_cross_mems_u64(s64, l64, bwt, n_, split, min_len, max_occ, records, capacity, summary, devices_[0]))
+            : (narrow ? caps_sa_hip_cross_mums_u32(s32, l32, bwt, n_, split, min_len, records, capacity, summary, devices_[0])
+                      : caps_sa_hip_cross_mums_u64(s64, l64, bwt, n_, split, min_len, records, capacity, summary, devices_[0]));
+        if (rc != CAPS_SA_OK && records && summary[0] > capacity) return false;
+        if (rc != CAPS_SA_OK) throw std::runtime_error(std::string(mems ? "caps_sa_hip_cross_mems: " : "caps_sa_hip_cross_mums: ") + caps_sa_hip_last_error());
+        return true;
+    }
+    std::vector<Match> cross(bool mems, uint64_t split, uint64_t min_len, uint32_t max_occ, Cross_Summary* out) const
+    {
+        static_assert(sizeof(Match) == 24, "the ABI's record");
+        if (max_context_ != 0 && max_context_ < n_)
+            throw std::invalid_argument(std::string("Suffix_Array::") + (mems ? "cross_mems" : "cross_mums") + ": MUMs and MEMs need a full-context suffix array (max_context is set)");
+        if (!SA_ || !LCP_) throw std::logic_error("Suffix_Array: construct() has not been called");
+        const uint8_t* bwt = BWT_;
+        if (!bwt) {
+            const std::size_t n = static_cast<std::size_t>(n_);
+            if (cross_bwt_.size() != n) {
+                cross_bwt_.resize(n);
+                for (std::size_t r = 0; r < n; ++r) cross_bwt_[r] = static_cast<uint8_t>(T_[SA_[r] ? static_cast<std::size_t>(SA_[r]) - 1 : n - 1]);
+            }
+            bwt = cross_bwt_.data();
+        }
+        uint64_t summary[8] = {0};
+        cross_call(mems, bwt, split, min_len, max_occ, nullptr, 0, summary);      // the counting call
+        std::vector<Match> rec(static_cast<std::size_t>(summary[0]));
+        if (!rec.empty() && !cross_call(mems, bwt, split, min_len, max_occ, rec.data(), rec.size(), summary))
+            throw std::runtime_error("caps_sa_hip_cross: the counting call and the writing call disagree");
+        if (out) *out = Cross_Summary{summary[0], summary[1], summary[2], summary[3], summary[4]};
+        return rec;
+    }
+    mutable std::vector<uint8_t> cross_bwt_;                    // the BWT gathered for cross_* after a plain construct()
 
     const char* const T_;
     const idx_t n_;

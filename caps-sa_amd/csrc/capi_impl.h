@@ -2954,6 +2954,156 @@ int kmer_census_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint32_t max
     });
 }
 
+// ---- MUMs and MEMs between two texts (include/caps_sa_hip.h "MUMs and MEMs between two texts"; kernels.h xm_*) ----------------------------
+// Workspace: cnt[XM_KEYS][n_tiles] | tot[XM_KEYS] | lcs[2 * grid] | out[8], 64-bit words.
+struct CrossPlan {
+    uint64_t n_tiles = 0;
+    uint32_t grid = 1;
+    size_t off_cnt = 0, off_tot = 0, off_lcs = 0, off_out = 0, bytes = 0;
+};
+inline CrossPlan cross_plan(uint64_t n)
+{
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    CrossPlan p;
+    p.n_tiles = (n + XM_TILE - 1) / XM_TILE;
+    p.grid = capped_grid(std::min<uint64_t>(p.n_tiles, 8192), FM_NT);
+    p.off_cnt = 0;
+    p.off_tot = p.off_cnt + up((XM_KEYS * p.n_tiles + 1) * 8);
+    p.off_lcs = p.off_tot + up(XM_KEYS * 8);
+    p.off_out = p.off_lcs + up((size_t)2 * p.grid * 8);
+    p.bytes = p.off_out + up(8 * 8);
+    return p;
+}
+inline int cross_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
+{
+    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
+    *bytes = cross_plan(n).bytes + 256;
+    return CAPS_SA_OK;
+}
+struct CrossWs {
+    char* base = nullptr;
+    CrossPlan p;
+    uint64_t* cnt() const { return reinterpret_cast<uint64_t*>(base + p.off_cnt); }
+    uint64_t* tot() const { return reinterpret_cast<uint64_t*>(base + p.off_tot); }
+    uint64_t* lcs() const { return reinterpret_cast<uint64_t*>(base + p.off_lcs); }
+    uint64_t* out() const { return reinterpret_cast<uint64_t*>(base + p.off_out); }
+};
+inline CrossWs cross_ws(DevAllocs& da, void* workspace, uint64_t workspace_bytes, uint64_t n)
+{
+    CrossWs w;
+    w.p = cross_plan(n);
+    uint64_t usable = 0;
+    if (workspace) w.base = kmer_align_ws(workspace, workspace_bytes, usable);
+    else w.base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(da.get<char>(w.p.bytes + 256)) + 255) & ~uintptr_t(255));
+    return w;
+}
+// every refusal that needs no device; max_occ = 0 is MUM mode
+template <typename idx_t>
+int cross_check(const void* SA, const void* LCP, const void* BWT, uint64_t n, uint64_t split, uint64_t min_len, bool mems, uint32_t max_occ,
+                const void* records, const uint64_t* summary, void* workspace, uint64_t workspace_bytes)
+{
+    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
+    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
+    if (n && (!SA || !LCP || !BWT)) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (!summary) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (min_len == 0) return fail(CAPS_SA_EINVAL, "min_len must be at least 1");
+    if (split > n) return fail(CAPS_SA_EINVAL, "split is beyond the text (split <= n)");
+    if (mems && (max_occ < 2 || max_occ > XM_MAX_OCC)) return fail(CAPS_SA_EINVAL, "max_occ must be in 2 .. 64");
+    if (reinterpret_cast<uintptr_t>(records) & 7u) return fail(CAPS_SA_EINVAL, "the records must be 8-byte aligned");
+    if (workspace) {
+        uint64_t usable = 0;
+        kmer_align_ws(workspace, workspace_bytes, usable);
+        if (usable < cross_plan(n).bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_cross_workspace_bytes)");
+    }
+    return CAPS_SA_OK;
+}
+
+// the counting pass: the 8 summary words (n >= 1)
+template <typename idx_t>
+void run_cross_count(Backend& be, const idx_t* dSA, const idx_t* dLCP, const uint8_t* dBWT, uint64_t n, uint64_t split, uint64_t min_len,
+                     uint32_t max_occ, uint64_t* summary, const CrossWs& w)
+{
+    if (max_occ)
+        CAPS_LAUNCH((xm_kernel<idx_t, XM_COUNT, true>), w.p.grid, FM_NT, be, dSA, dLCP, dBWT, n, split, min_len, max_occ, w.p.n_tiles, w.cnt(),
+                    w.lcs(), (uint64_t*)nullptr, (uint64_t)0);
+    else
+        CAPS_LAUNCH((xm_kernel<idx_t, XM_COUNT, false>), w.p.grid, FM_NT, be, dSA, dLCP, dBWT, n, split, min_len, max_occ, w.p.n_tiles, w.cnt(),
+                    w.lcs(), (uint64_t*)nullptr, (uint64_t)0);
+    CAPS_LAUNCH(fm_scan_kernel, XM_KEYS, FM_NT, be, w.cnt(), w.p.n_tiles, 0u, XM_KEYS, w.tot());
+    CAPS_LAUNCH((xm_finish_kernel<idx_t>), 1, FM_NT, be, dSA, n, split, (const uint64_t*)w.lcs(), w.p.grid, (const uint64_t*)w.tot(), w.out());
+    be.d2h(summary, w.out(), 8 * sizeof(uint64_t));
+    be.sync();
+}
+// the writing pass behind a counting pass on the same workspace: summary[0] records, at most `capacity` of them stored
+template <typename idx_t>
+void run_cross_write(Backend& be, const idx_t* dSA, const idx_t* dLCP, const uint8_t* dBWT, uint64_t n, uint64_t split, uint64_t min_len,
+                     uint32_t max_occ, void* dRec, uint64_t capacity, const CrossWs& w)
+{
+    if (max_occ)
+        CAPS_LAUNCH((xm_kernel<idx_t, XM_WRITE, true>), w.p.grid, FM_NT, be, dSA, dLCP, dBWT, n, split, min_len, max_occ, w.p.n_tiles, w.cnt(),
+                    (uint64_t*)nullptr, static_cast<uint64_t*>(dRec), capacity);
+    else
+        CAPS_LAUNCH((xm_kernel<idx_t, XM_WRITE, false>), w.p.grid, FM_NT, be, dSA, dLCP, dBWT, n, split, min_len, max_occ, w.p.n_tiles, w.cnt(),
+                    (uint64_t*)nullptr, static_cast<uint64_t*>(dRec), capacity);
+    be.sync();
+}
+inline const char* cross_capacity_msg() { return "capacity is smaller than the number of records (summary[0]; a call with the records NULL counts them)"; }
+
+template <typename idx_t>
+int cross_device(const void* dSA, const void* dLCP, const void* dBWT, uint64_t n, uint64_t split, uint64_t min_len, bool mems, uint32_t max_occ,
+                 void* dRec, uint64_t capacity, uint64_t* summary, void* workspace, uint64_t workspace_bytes, void* stream)
+{
+    if (int rc = cross_check<idx_t>(dSA, dLCP, dBWT, n, split, min_len, mems, max_occ, dRec, summary, workspace, workspace_bytes)) return rc;
+    std::memset(summary, 0, 8 * sizeof(uint64_t));
+    if (n == 0) return CAPS_SA_OK;
+    if (!mems) max_occ = 0;
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);
+        const CrossWs w = cross_ws(da, workspace, workspace_bytes, n);
+        const idx_t* sa = static_cast<const idx_t*>(dSA);
+        const idx_t* lcp = static_cast<const idx_t*>(dLCP);
+        const uint8_t* bwt = static_cast<const uint8_t*>(dBWT);
+        run_cross_count<idx_t>(be, sa, lcp, bwt, n, split, min_len, max_occ, summary, w);
+        if (!dRec) return CAPS_SA_OK;
+        if (summary[0] > capacity) return fail(CAPS_SA_EINVAL, cross_capacity_msg());
+        if (summary[0]) run_cross_write<idx_t>(be, sa, lcp, bwt, n, split, min_len, max_occ, dRec, capacity, w);
+        return CAPS_SA_OK;
+    });
+}
+// host arrays: up into buffers of the call's own, the device form on them, the records down
+template <typename idx_t>
+int cross_host(const idx_t* SA, const idx_t* LCP, const uint8_t* BWT, uint64_t n, uint64_t split, uint64_t min_len, bool mems, uint32_t max_occ,
+               void* records, uint64_t capacity, uint64_t* summary, int device)
+{
+    if (int rc = cross_check<idx_t>(SA, LCP, BWT, n, split, min_len, mems, max_occ, records, summary, nullptr, 0)) return rc;
+    std::memset(summary, 0, 8 * sizeof(uint64_t));
+    if (n == 0) return CAPS_SA_OK;
+    if (!mems) max_occ = 0;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        Backend be(nullptr);
+        DevAllocs da(be);
+        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
+        uint8_t* bwt = da.get<uint8_t>(n);
+        be.h2d(bwt, BWT, n);
+        const CrossWs w = cross_ws(da, nullptr, 0, n);
+        run_cross_count<idx_t>(be, a.sa, a.lcp, bwt, n, split, min_len, max_occ, summary, w);
+        if (!records) return CAPS_SA_OK;
+        if (summary[0] > capacity) return fail(CAPS_SA_EINVAL, cross_capacity_msg());
+        if (summary[0] == 0) return CAPS_SA_OK;
+        const uint64_t found = summary[0];
+        uint64_t* dRec = da.get<uint64_t>(3 * found);
+        run_cross_write<idx_t>(be, a.sa, a.lcp, bwt, n, split, min_len, max_occ, dRec, found, w);
+        be.d2h(records, dRec, found * 24);
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+
 // ---- LPF and LZ77 from SA and LCP (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP"; kernels.h lpf_* / lz_*) ------------------------
 // lpf workspace: tab[2 * LPF_MAX_LEVELS + 2] (offset, nodes of every level) | bad | sumSA[nodes] | sumLCP[nodes], nodes = all levels.
 struct LpfPlan {
@@ -3970,6 +4120,26 @@ int CAPS_API(kmer_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) {
 CAPS_DEFINE_KMER(u32, uint32_t)
 CAPS_DEFINE_KMER(u64, uint64_t)
 #undef CAPS_DEFINE_KMER
+int CAPS_API(cross_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::cross_workspace_bytes(n, idx_bytes, bytes); }
+#define CAPS_DEFINE_CROSS(SFX, IDX)                                                                                         \
+    int CAPS_API(cross_mums_device_##SFX)(const void* dSA, const void* dLCP, const void* dBWT, uint64_t n, uint64_t split,  \
+                                          uint64_t min_len, void* dRecords, uint64_t capacity, uint64_t* summary, void* ws, \
+                                          uint64_t ws_bytes, void* stream)                                                  \
+    { return caps::cross_device<IDX>(dSA, dLCP, dBWT, n, split, min_len, false, 0, dRecords, capacity, summary, ws, ws_bytes, stream); } \
+    int CAPS_API(cross_mems_device_##SFX)(const void* dSA, const void* dLCP, const void* dBWT, uint64_t n, uint64_t split,  \
+                                          uint64_t min_len, uint32_t max_occ, void* dRecords, uint64_t capacity,            \
+                                          uint64_t* summary, void* ws, uint64_t ws_bytes, void* stream)                     \
+    { return caps::cross_device<IDX>(dSA, dLCP, dBWT, n, split, min_len, true, max_occ, dRecords, capacity, summary, ws, ws_bytes, stream); } \
+    int CAPS_API(cross_mums_##SFX)(const IDX* SA, const IDX* LCP, const uint8_t* BWT, uint64_t n, uint64_t split,           \
+                                   uint64_t min_len, void* records, uint64_t capacity, uint64_t* summary, int device)       \
+    { return caps::cross_host<IDX>(SA, LCP, BWT, n, split, min_len, false, 0, records, capacity, summary, device); }        \
+    int CAPS_API(cross_mems_##SFX)(const IDX* SA, const IDX* LCP, const uint8_t* BWT, uint64_t n, uint64_t split,           \
+                                   uint64_t min_len, uint32_t max_occ, void* records, uint64_t capacity, uint64_t* summary, \
+                                   int device)                                                                              \
+    { return caps::cross_host<IDX>(SA, LCP, BWT, n, split, min_len, true, max_occ, records, capacity, summary, device); }
+CAPS_DEFINE_CROSS(u32, uint32_t)
+CAPS_DEFINE_CROSS(u64, uint64_t)
+#undef CAPS_DEFINE_CROSS
 int CAPS_API(lpf_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::lpf_workspace_bytes(n, idx_bytes, bytes); }
 int CAPS_API(lz77_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::lz77_workspace_bytes(n, idx_bytes, bytes); }
 #define CAPS_DEFINE_LZ(SFX, IDX)                                                                                            \

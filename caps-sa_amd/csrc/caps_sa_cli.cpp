@@ -6,6 +6,7 @@
 //     caps_sa <input_path> <output_path> [subproblem-count] [--lz77 PATH]
 //     caps_sa <input_path> <output_path> [subproblem-count] [--lce-index PATH]
 //     caps_sa --lce INDEX PAIRS [--mismatches K]
+//     caps_sa <input_path> <output_path> [subproblem-count] [--raw] [--cross-mums SPLIT PATH] [--cross-mems SPLIT PATH [--max-occ C]] [--min-len L]
 //     caps_sa --inverse-bwt IN.bwt OUT
 //     caps_sa <input_path> <output_path> [subproblem-count] --fm-index PATH [--fm-sample S] [--fm-text-sample T]
 //     caps_sa <input_path> <output_path> [subproblem-count] --raw [--bwt PATH] [--fm-index PATH [--fm-sample S]]
@@ -31,6 +32,13 @@
 //   over LCP without the text or the arrays.  Refused with a bounded context;
 // * --lce INDEX PAIRS [--mismatches K] (not in the reference): one pair of text positions "i j" per line of PAIRS; per pair one line
 //   on stdout, the length of the longest common extension of T[i ..) and T[j ..) with at most K (0 .. 1024, default 0) mismatches;
+// * --cross-mums SPLIT PATH [--min-len L] and --cross-mems SPLIT PATH [--min-len L] [--max-occ C] (not in the reference; on the build
+//   line): the text as built (remapped, or with --raw the file's own bytes) is A . sep . B with the separator at SPLIT - 1; after the
+//   SA / LCP output, the maximal unique matches, or the maximal exact matches whose first L bytes occur at most C (2 .. 64, default
+//   64) times, of at least L (default 1) bytes between the two sides to PATH (include/caps_sa_hip.h "MUMs and MEMs between two
+//   texts"): one line "a<TAB>b<TAB>len" per record in record order, and on stderr one line with the summary.  A separator that occurs
+//   nowhere else needs --raw (the remap leaves four letters).  One GPU; refused with a bounded context and with SPLIT > n, before
+//   anything is written; --max-occ without --cross-mems is refused;
 // * --raw (not in the reference; on the build line only): the text as given, no remap to {A,C,G,T} -- SA, LCP and --bwt are those of
 //   the file's own bytes, and --fm-index PATH writes the wide format (include/caps_sa_hip.h "FM-index: the wide format") for 1 .. 256
 //   distinct bytes.  --fm-search and --fm-mems tell a wide index by its magic and take the pattern lines as bytes, unremapped (a
@@ -100,6 +108,11 @@
 #define CAPS_CLI_NO_LCE 1
 #endif
 
+// ... and for one that predates the MUM / MEM entry points: the CLI without --cross-mums and --cross-mems.
+#if defined(caps_sa_hip_build_multi_u32) && !defined(caps_sa_hip_cross_mums_u32)
+#define CAPS_CLI_NO_CROSS 1
+#endif
+
 static bool read_input(const std::string& path, std::string& text)
 {
     std::ifstream in(path, std::ios::binary | std::ios::ate);
@@ -130,10 +143,18 @@ struct KmerJob {
     std::string path, spectrum_path;
 };
 
+// what --cross-mums / --cross-mems ask for (an empty path: not asked for)
+struct CrossJob {
+    size_t mums_split = 0, mems_split = 0, min_len = 1, max_occ = 64;
+    std::string mums_path, mems_path;
+    bool any() const { return !mums_path.empty() || !mems_path.empty(); }
+};
+
 template <typename idx_t>
 static int run(const std::string& text, const std::string& out_path, size_t p, size_t ctx, bool pretty, const std::vector<int>& devices,
                const std::string& bwt_path, const std::string& fm_path = std::string(), uint32_t fm_sample = 32, uint32_t fm_text_sample = 0, bool raw = false,
-               const KmerJob& km = KmerJob(), const std::string& lz_path = std::string(), const std::string& lce_path = std::string())
+               const KmerJob& km = KmerJob(), const std::string& lz_path = std::string(), const std::string& lce_path = std::string(),
+               const CrossJob& cross = CrossJob())
 {
     if (p > std::numeric_limits<idx_t>::max()) { std::cerr << "subproblem-count does not fit the index type\n"; return EXIT_FAILURE; }
     // the bounded-context mode replays the reference's merge history, one GPU thread per merge node -- the top levels
@@ -144,7 +165,7 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
                   << " seconds for " << (text.size() >> 20) << " Mi chars; the unbounded construction takes milliseconds.\n";
     CaPS_SA::Suffix_Array<idx_t> suf_arr(text.c_str(), static_cast<idx_t>(text.size()), static_cast<idx_t>(p),
                                          static_cast<idx_t>(ctx >= text.size() ? 0 : ctx), devices);
-    if (bwt_path.empty() && fm_path.empty()) suf_arr.construct();
+    if (bwt_path.empty() && fm_path.empty() && !cross.any()) suf_arr.construct();
     else suf_arr.construct_bwt();
     const caps_sa_stats& st = suf_arr.stats();
     std::cerr << "Constructed the suffix array. Device time: " << st.ms_total / 1e3 << " seconds (h2d "
@@ -217,6 +238,21 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
         const CaPS_SA::LCE_Index x = CaPS_SA::LCE_Index::build(suf_arr);
         x.save(lce_path);
         std::cerr << "LCE index: " << x.size() << " bytes written.\n";
+    }
+#endif
+#ifndef CAPS_CLI_NO_CROSS
+    for (int mems = 0; mems < 2; ++mems) {
+        const std::string& path = mems ? cross.mems_path : cross.mums_path;
+        if (path.empty()) continue;
+        typename CaPS_SA::Suffix_Array<idx_t>::Cross_Summary s{};
+        const auto rec = mems ? suf_arr.cross_mems(cross.mems_split, cross.min_len, static_cast<uint32_t>(cross.max_occ), &s)
+                              : suf_arr.cross_mums(cross.mums_split, cross.min_len, &s);
+        std::ofstream out(path, std::ios::binary);
+        if (!out) { std::cerr << path << " : cannot open for writing\n"; return EXIT_FAILURE; }
+        for (const auto& r : rec) out << r.a << '\t' << r.b << '\t' << r.len << '\n';
+        if (!out) return EXIT_FAILURE;
+        std::cerr << (mems ? "cross-mems: " : "cross-mums: ") << s.records << " records, " << s.skipped_runs << " skipped runs, longest common substring "
+                  << s.lcs_len << " at " << s.lcs_a << " and " << s.lcs_b << ".\n";
     }
 #endif
     return 0;
@@ -549,6 +585,8 @@ int main(int argc, char* argv[])
     KmerJob km;
     std::string lz_path;                                   // --lz77 (empty: not asked for)
     bool kmers = false, spectrum = false, min_count_given = false, max_count_given = false, lz = false;
+    CrossJob cross;                                        // --cross-mums / --cross-mems
+    bool min_len_given = false, max_occ_given = false;
     for (int i = 1; i < argc; ++i) {
         if (std::strcmp(argv[i], "--pretty-print") == 0) pretty = true;
         else if (std::strcmp(argv[i], "--kmers") == 0 || std::strcmp(argv[i], "--kmer-spectrum") == 0) {
@@ -575,6 +613,27 @@ int main(int argc, char* argv[])
             if (i + 1 >= argc || std::strncmp(argv[i + 1], "--", 2) == 0) { std::cerr << "--lce-index: usage: --lce-index PATH\n"; return EXIT_FAILURE; }
             lce = true;
             lce_path = argv[++i];
+        }
+        else if (std::strcmp(argv[i], "--cross-mums") == 0 || std::strcmp(argv[i], "--cross-mems") == 0) {
+            const bool mems = std::strcmp(argv[i], "--cross-mems") == 0;
+            const char* opt = argv[i];
+            size_t split = 0;
+            if (!(mems ? cross.mems_path : cross.mums_path).empty()) { std::cerr << opt << ": given twice\n"; return EXIT_FAILURE; }
+            if (i + 2 >= argc || !parse_count(argv[i + 1], split) || std::strncmp(argv[i + 2], "--", 2) == 0 || !argv[i + 2][0]) {
+                std::cerr << opt << ": usage: " << opt << " SPLIT PATH\n";
+                return EXIT_FAILURE;
+            }
+            (mems ? cross.mems_split : cross.mums_split) = split;
+            (mems ? cross.mems_path : cross.mums_path) = argv[i + 2];
+            i += 2;
+        }
+        else if (std::strcmp(argv[i], "--max-occ") == 0) {
+            if (i + 1 >= argc || !parse_count(argv[i + 1], cross.max_occ) || cross.max_occ < 2 || cross.max_occ > 64) {
+                std::cerr << "--max-occ: a number in 2 .. 64, please\n";
+                return EXIT_FAILURE;
+            }
+            max_occ_given = true;
+            ++i;
         }
         else if (std::strcmp(argv[i], "--mismatches") == 0) { std::cerr << "--mismatches: only with --lce\n"; return EXIT_FAILURE; }
         else if (std::strcmp(argv[i], "--min-count") == 0 || std::strcmp(argv[i], "--max-count") == 0) {
@@ -610,17 +669,22 @@ int main(int argc, char* argv[])
             }
         }
         else if (std::strcmp(argv[i], "--locate") == 0) { std::cerr << "--locate: only with --fm-search\n"; return EXIT_FAILURE; }
-        else if (std::strcmp(argv[i], "--min-len") == 0) { std::cerr << "--min-len: only with --fm-mems\n"; return EXIT_FAILURE; }
+        else if (std::strcmp(argv[i], "--min-len") == 0) {      // (with --cross-mums / --cross-mems; checked behind the loop)
+            min_len_given = true;
+            if (i + 1 < argc && parse_count(argv[i + 1], cross.min_len)) ++i;
+            else cross.min_len = 0;
+        }
         else if (std::strcmp(argv[i], "--gpus") == 0 && i + 1 < argc) {
             if (!parse_count(argv[++i], gpus) || gpus < 1 || gpus > 64) { std::cerr << "--gpus: a device count, please\n"; return EXIT_FAILURE; }
         } else pos.push_back(argv[i]);
     }
+    if (min_len_given && !cross.any()) { std::cerr << "--min-len: only with --fm-mems\n"; return EXIT_FAILURE; }
     if (pos.size() < 2) {
         std::cerr << "Usage: caps_sa <input_path> <output_path> <(optional)-subproblem-count> "
                      "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH> "
                      "<(optional)--fm-index PATH [--fm-sample S] [--fm-text-sample T]> <(optional)--raw> "
                      "<(optional)--kmers K PATH [--min-count A] [--max-count B]> <(optional)--kmer-spectrum K PATH> <(optional)--lz77 PATH> "
-                     "<(optional)--lce-index PATH>\n"
+                     "<(optional)--lce-index PATH> <(optional)--cross-mums SPLIT PATH [--min-len L]> <(optional)--cross-mems SPLIT PATH [--min-len L] [--max-occ C]>\n"
                      "       caps_sa --lce INDEX PAIRS [--mismatches K]\n"
                      "       caps_sa --inverse-bwt IN.bwt OUT\n"
                      "       caps_sa --fm-search INDEX PATTERNS [--locate K]\n"
@@ -680,6 +744,28 @@ int main(int argc, char* argv[])
             return EXIT_FAILURE;
         }
     }
+    // --cross-mums / --cross-mems: the same manners
+#ifdef CAPS_CLI_NO_CROSS
+    if (cross.any()) { std::cerr << (cross.mums_path.empty() ? "--cross-mems" : "--cross-mums") << ": not built into this driver\n"; return EXIT_FAILURE; }
+#endif
+    if (max_occ_given && cross.mems_path.empty()) { std::cerr << "--max-occ: only with --cross-mems SPLIT PATH\n"; return EXIT_FAILURE; }
+    if (cross.any()) {
+        const char* opt = cross.mums_path.empty() ? "--cross-mems" : "--cross-mums";
+        if (min_len_given && cross.min_len < 1) { std::cerr << "--min-len: a length of at least 1, please\n"; return EXIT_FAILURE; }
+        if (gpus > 1) { std::cerr << opt << ": the matches need the BWT, which is built on one GPU; --gpus " << gpus << " has none\n"; return EXIT_FAILURE; }
+        struct stat sb;
+        if (stat(pos[0].c_str(), &sb) == 0) {
+            const size_t n = static_cast<size_t>(sb.st_size);
+            if (ctx != 0 && ctx < n) {
+                std::cerr << opt << ": a bounded-context order (bounded-context " << ctx << ") is not a suffix array and has no matches between two texts\n";
+                return EXIT_FAILURE;
+            }
+            if ((!cross.mums_path.empty() && cross.mums_split > n) || (!cross.mems_path.empty() && cross.mems_split > n)) {
+                std::cerr << opt << ": SPLIT is beyond the text (n = " << n << ")\n";
+                return EXIT_FAILURE;
+            }
+        }
+    }
     // --fm-index: the same manners
     if (fm_sample_given && !fm) { std::cerr << "--fm-sample: only with --fm-index PATH\n"; return EXIT_FAILURE; }
     if (fm_text_given && !fm) { std::cerr << "--fm-text-sample: only with --fm-index PATH or --fm-from-bwt\n"; return EXIT_FAILURE; }
@@ -722,8 +808,8 @@ int main(int argc, char* argv[])
 
     std::cerr << "Text length: " << text.size() << ".\n";
     try {
-        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path, lce_path);
-        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path, lce_path);
+        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path, lce_path, cross);
+        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path, lce_path, cross);
     } catch (const std::exception& e) {
         std::cerr << e.what() << "\n";
         return EXIT_FAILURE;

@@ -7608,4 +7608,281 @@ GLOBAL_FN LAUNCH_BOUNDS(FM_NT) lce_query_kernel(KCTX LceView v, const uint64_t* 
     }
 }
 
+// ---- MUMs and rare MEMs between two texts (capi_impl.h cross_*; include/caps_sa_hip.h "MUMs and MEMs between two texts") ----------------
+// T = A . sep . B, side(p) = (p >= split).  Every decision is a rule over neighbouring ranks of (SA, LCP, BWT); nothing is indexed by a
+// value read from SA or LCP.  Tiles of XM_TILE ranks, FM_NT threads, grid-stride, count -> fm_scan_kernel -> write as the k-mer table:
+//   xm_kernel<COUNT>   coalesced 16-byte loads of LCP; SA and BWT only for a chunk with a rank that can yield a record (LCP >= min_len)
+//                      or beat the thread's longest-common-substring candidate; the neighbours across a chunk or tile edge are read
+//                      from global memory.  Leaves cnt[tile] (records), cnt[n_tiles + tile] (skipped runs, counted at their heads)
+//                      and per workgroup its LCS candidate (length, rank; a thread meets its ranks in ascending order).
+//   xm_kernel<WRITE>   repeats the decisions, leaves every rank's number of records as a byte in LDS; then a lane owns XM_LANE
+//                      consecutive ranks, the lanes' sums are scanned (kmer_run_kernel's two steps) and the records stored in rank order.
+//   xm_finish_kernel   one workgroup: the lowest rank among the longest candidates, the 8 summary words.
+// MEM mode (MEMS, max_occ >= 2): rank q with LCP[q] >= min_len walks back over at most max_occ - 1 ranks to its run's head and
+// forward to its end: at most max_occ + 1 reads of LCP and max_occ - 1 of SA and of BWT per rank, whatever the arrays hold.
+constexpr uint64_t XM_TILE = KMER_TILE;
+constexpr uint32_t XM_LANE = KMER_LANE;
+constexpr uint32_t XM_MAX_OCC = 64;
+constexpr uint32_t XM_KEYS = 2;                                    // columns of the tile counts: records, skipped runs
+enum { XM_COUNT = 0, XM_WRITE = 1 };
+static_assert(KmerGeom<uint32_t>::ROUNDS % 4 == 0 && KmerGeom<uint64_t>::ROUNDS % 4 == 0 && XM_MAX_OCC - 1 <= 255 && XM_LANE * (XM_MAX_OCC - 1) < (1u << 16), "a rank's records fit a byte, a tile's 32 bits");
+template <typename idx_t> struct XmIn {
+    const idx_t* SA;
+    const idx_t* LCP;
+    const uint8_t* BWT;
+    uint64_t n, split, min_len;
+    uint32_t max_occ;
+};
+
+// rank q (1 <= q < n, LCP[q] >= min_len) of MEM mode: its pairs (p, q), p descending -> f(SA[p], SA[q], min LCP[p + 1 .. q]).  CHECK:
+// returns their number, 0 for a run that is given up (no head within max_occ - 1 ranks below q, or no end within max_occ ranks of the head);
+// without CHECK the caller knows that the run is processed.
+template <typename idx_t, bool CHECK, typename F>
+DEV_INLINE uint32_t xm_mem_rank(const XmIn<idx_t>& a, uint64_t q, F&& f)
+{
+    const uint64_t sq = (uint64_t)a.SA[q];
+    const uint32_t bq = a.BWT[q];
+    uint64_t l = (uint64_t)a.LCP[q], h = q;
+    uint32_t found = 0;
+    bool head = false;
+    for (uint32_t d = 1; d < a.max_occ; ++d) {
+        const uint64_t p = q - d, sp = (uint64_t)a.SA[p];
+        if ((sp >= a.split) != (sq >= a.split) && (sp == 0 || sq == 0 || (uint32_t)a.BWT[p] != bq)) { f(sp, sq, l); ++found; }
+        if (p == 0) { h = 0; head = true; break; }
+        const uint64_t lp = (uint64_t)a.LCP[p];
+        if (lp < a.min_len) { h = p; head = true; break; }
+        l = lp < l ? lp : l;
+    }
+    if (!CHECK) return found;
+    if (!head) return 0;
+    for (uint64_t e = q + 1; e <= h + a.max_occ; ++e)
+        if (e >= a.n || (uint64_t)a.LCP[e] < a.min_len) return found;
+    return 0;
+}
+// head h of MEM mode: is its run longer than max_occ ranks?
+template <typename idx_t>
+DEV_INLINE bool xm_run_skipped(const XmIn<idx_t>& a, uint64_t h)
+{
+    for (uint64_t e = h + 1; e <= h + a.max_occ; ++e)
+        if (e >= a.n || (uint64_t)a.LCP[e] < a.min_len) return false;
+    return true;
+}
+HD void xm_store(uint64_t* __restrict__ rec, uint64_t at, uint64_t cap, uint64_t sp, uint64_t sq, uint64_t l, uint64_t split)
+{
+    if (at < cap) {
+        rec[3 * at] = sp < split ? sp : sq;
+        rec[3 * at + 1] = sp < split ? sq : sp;
+        rec[3 * at + 2] = l;
+    }
+}
+
+template <typename idx_t, int MODE, bool MEMS>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) xm_kernel(KCTX const idx_t* __restrict__ SA, const idx_t* __restrict__ LCP, const uint8_t* __restrict__ BWT, uint64_t n,
+                                          uint64_t split, uint64_t min_len, uint32_t max_occ, uint64_t n_tiles, uint64_t* __restrict__ cnt,
+                                          uint64_t* __restrict__ lcs, uint64_t* __restrict__ rec, uint64_t cap)
+{
+    using G = KmerGeom<idx_t>;
+    constexpr uint32_t PER = G::PER;
+    SHARED_ARRAY(uint8_t, rc, MODE == XM_WRITE ? XM_TILE : 1);      // per rank: its records
+    SHARED_ARRAY(uint32_t, lane, FM_NT);
+    SHARED_ARRAY(uint32_t, scan, FM_NT);
+    SHARED_ARRAY(uint32_t, grp, 2 * KMER_GROUP);
+    SHARED_ARRAY(uint32_t, h, XM_KEYS);
+    SHARED_ARRAY(uint64_t, bl, MODE == XM_COUNT ? FM_NT : 1);
+    SHARED_ARRAY(uint64_t, br, MODE == XM_COUNT ? FM_NT : 1);
+    TL_DECL(uint64_t, best, 2);                                     // the thread's LCS candidate: length, rank
+    const XmIn<idx_t> a{SA, LCP, BWT, n, split, min_len, max_occ};
+    constexpr bool mems = MEMS;                                     // (MUM mode: max_occ = 0)
+    PAR(tid) {
+        TL(best, tid, 0) = 0;
+        TL(best, tid, 1) = 0;
+        if (tid < XM_KEYS) h[tid] = 0;
+    }
+    SYNC();
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t t0 = tile * XM_TILE;
+        PAR(tid) {
+            uint32_t mine = 0, skipped = 0;
+            uint64_t bestl = TL(best, tid, 0), bestr = TL(best, tid, 1);
+            // four chunks of LCP in flight (with the rank before and the rank behind each: the neighbours' cache lines), then the decisions
+            for (uint32_t j0 = 0; j0 < G::ROUNDS; j0 += 4) {
+                KmerChunk<idx_t> lc4[4];
+                idx_t bef4[4], beh4[4];
+                UNROLL
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint64_t i0 = t0 + (uint64_t)((j0 + j) * FM_NT + tid) * PER;
+                    bef4[j] = beh4[j] = 0;
+                    if (i0 < n) {
+                        lc4[j] = kmer_load<idx_t>(LCP, n, i0);
+                        if (i0 >= 2) bef4[j] = LCP[i0 - 1];
+                        if (i0 + PER < n) beh4[j] = LCP[i0 + PER];
+                    }
+                }
+                UNROLL
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint32_t c = (j0 + j) * FM_NT + tid;
+                    const uint64_t i0 = t0 + (uint64_t)c * PER;
+                    uint32_t made[PER];
+                    UNROLL
+                    for (uint32_t e = 0; e < PER; ++e) made[e] = 0;
+                    if (i0 < n) {
+                        // eff[1 + e] = LCP[i0 + e] as the rules see it: 0 at rank 0 and behind the last rank
+                        const KmerChunk<idx_t>& lc = lc4[j];
+                        uint64_t eff[PER + 2];
+                        eff[0] = (uint64_t)bef4[j];
+                        UNROLL
+                        for (uint32_t e = 0; e < PER; ++e) eff[1 + e] = (uint64_t)lc.v[e];
+                        if (i0 == 0) eff[1] = 0;
+                        eff[PER + 1] = (uint64_t)beh4[j];
+                        bool want = false;
+                        UNROLL
+                        for (uint32_t e = 0; e < PER; ++e) {
+                            const uint64_t l = eff[1 + e];
+                            bool w = l >= min_len && (mems || (eff[e] < l && eff[2 + e] < l));
+                            if (MODE == XM_COUNT) w = w || l > bestl;
+                            want = want || w;
+                        }
+                        if (want) {                                    // (a rank with l >= 1 is at least 1 and below n)
+                            const KmerChunk<idx_t> sc = kmer_load<idx_t>(SA, n, i0);
+                            const uint64_t before = i0 ? (uint64_t)SA[i0 - 1] : 0;
+                            UNROLL
+                            for (uint32_t e = 0; e < PER; ++e) {
+                                const uint64_t l = eff[1 + e], r = i0 + e;
+                                if (l == 0) continue;
+                                const uint64_t sp = e ? (uint64_t)sc.v[e ? e - 1 : 0] : before, sq = (uint64_t)sc.v[e];
+                                const bool crossing = (sp >= split) != (sq >= split);
+                                if (MODE == XM_COUNT && crossing && l > bestl) { bestl = l; bestr = r; }
+                                if (l < min_len) continue;
+                                if (mems) made[e] = xm_mem_rank<idx_t, true>(a, r, [](uint64_t, uint64_t, uint64_t) {});
+                                else if (crossing && eff[e] < l && eff[2 + e] < l && (sp == 0 || sq == 0 || BWT[r - 1] != BWT[r])) made[e] = 1;
+                            }
+                        }
+                        if (MODE == XM_COUNT && mems) {                 // the heads of the chunk whose next rank is none: runs of 2 ranks or more
+                            UNROLL
+                            for (uint32_t e = 0; e < PER; ++e)
+                                if (i0 + e < n && eff[1 + e] < min_len && eff[2 + e] >= min_len && xm_run_skipped<idx_t>(a, i0 + e)) ++skipped;
+                        }
+                    }
+                    UNROLL
+                    for (uint32_t e = 0; e < PER; ++e) {
+                        mine += made[e];
+                        if (MODE == XM_WRITE) rc[c * PER + e] = (uint8_t)made[e];
+                    }
+                }
+            }
+            if (MODE == XM_COUNT) {
+                TL(best, tid, 0) = bestl;
+                TL(best, tid, 1) = bestr;
+                if (mine) FETCH_ADD_U32(&h[0], mine);
+                if (skipped) FETCH_ADD_U32(&h[1], skipped);
+            }
+        }
+        SYNC();
+        if (MODE == XM_COUNT) {
+            PAR(tid) {
+                if (tid < XM_KEYS) {
+                    cnt[(uint64_t)tid * n_tiles + tile] = h[tid];
+                    h[tid] = 0;
+                }
+            }
+            SYNC();
+        }
+        if (MODE == XM_WRITE) {
+            PAR(tid) {
+                uint32_t s = 0;
+                for (uint32_t k = 0; k < XM_LANE; ++k) s += rc[tid * XM_LANE + k];
+                lane[tid] = s;
+            }
+            SYNC();
+            PAR(tid) {                                      // forward: the records of the lanes before every lane
+                if (tid < KMER_GROUP) {
+                    uint32_t run = 0;
+                    for (uint32_t j = 0; j < KMER_GROUP; ++j) {
+                        const uint32_t at = tid * KMER_GROUP + j, x = lane[at];
+                        scan[at] = run;
+                        run += x;
+                    }
+                    grp[tid] = run;
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                if (tid == 0) {
+                    uint32_t run = 0;
+                    for (uint32_t g = 0; g < KMER_GROUP; ++g) { const uint32_t x = grp[g]; grp[KMER_GROUP + g] = run; run += x; }
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                if (lane[tid]) {
+                    uint64_t at = cnt[tile] + scan[tid] + grp[KMER_GROUP + tid / KMER_GROUP];
+                    for (uint32_t k = 0; k < XM_LANE; ++k) {
+                        if (!rc[tid * XM_LANE + k]) continue;
+                        const uint64_t r = t0 + (uint64_t)tid * XM_LANE + k;         // 1 <= r < n: it made records
+                        if (mems) {
+                            xm_mem_rank<idx_t, false>(a, r, [&](uint64_t sp, uint64_t sq, uint64_t l) { xm_store(rec, at, cap, sp, sq, l, split); ++at; });
+                        } else {
+                            xm_store(rec, at, cap, (uint64_t)SA[r - 1], (uint64_t)SA[r], (uint64_t)LCP[r], split);
+                            ++at;
+                        }
+                    }
+                }
+            }
+            SYNC();
+        }
+    }
+    if (MODE == XM_COUNT) {
+        PAR(tid) {
+            bl[tid] = TL(best, tid, 0);
+            br[tid] = TL(best, tid, 1);
+        }
+        SYNC();
+        PAR(tid) {
+            if (tid == 0) {
+                uint64_t l = 0, r = 0;
+                for (uint32_t k = 0; k < FM_NT; ++k)
+                    if (bl[k] > l || (bl[k] == l && l && br[k] < r)) { l = bl[k]; r = br[k]; }
+                lcs[2 * (uint64_t)K_BLOCK_IDX] = l;
+                lcs[2 * (uint64_t)K_BLOCK_IDX + 1] = r;
+            }
+        }
+    }
+}
+
+// one workgroup: out[0] = records, out[1] = skipped runs (tot[] of fm_scan_kernel), out[2 .. 4] = the LCS (len, a, b) from the lowest rank
+// among the workgroups' longest candidates (a candidate rank r has 1 <= r < n), out[5 .. 7] = 0
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) xm_finish_kernel(KCTX const idx_t* __restrict__ SA, uint64_t n, uint64_t split, const uint64_t* __restrict__ lcs,
+                                                 uint32_t groups, const uint64_t* __restrict__ tot, uint64_t* __restrict__ out)
+{
+    SHARED_ARRAY(uint64_t, bl, FM_NT);
+    SHARED_ARRAY(uint64_t, br, FM_NT);
+    PAR(tid) {
+        uint64_t l = 0, r = 0;
+        for (uint32_t g = tid; g < groups; g += FM_NT) {
+            const uint64_t gl = lcs[2 * (uint64_t)g], gr = lcs[2 * (uint64_t)g + 1];
+            if (gl > l || (gl == l && l && gr < r)) { l = gl; r = gr; }
+        }
+        bl[tid] = l;
+        br[tid] = r;
+    }
+    SYNC();
+    PAR(tid) {
+        if (tid == 0) {
+            uint64_t l = 0, r = 0;
+            for (uint32_t k = 0; k < FM_NT; ++k)
+                if (bl[k] > l || (bl[k] == l && l && br[k] < r)) { l = bl[k]; r = br[k]; }
+            out[0] = tot[0];
+            out[1] = tot[1];
+            out[2] = out[3] = out[4] = out[5] = out[6] = out[7] = 0;
+            if (l && r >= 1 && r < n) {
+                const uint64_t sp = (uint64_t)SA[r - 1], sq = (uint64_t)SA[r];
+                out[2] = l;
+                out[3] = sp < split ? sp : sq;
+                out[4] = sp < split ? sq : sp;
+            }
+        }
+    }
+}
+
 }  // namespace caps

@@ -815,6 +815,78 @@ int caps_sa_hip_lce_device(const void* dIndex, uint64_t index_bytes, const void*
 int caps_sa_hip_lce(const void* index, uint64_t index_bytes, const uint64_t* i, const uint64_t* j, uint64_t q, uint64_t mismatches,
                     uint64_t* len, int device);
 
+/* ---- MUMs and MEMs between two texts ------------------------------------------------
+ * The anchors a whole-sequence comparison starts from -- maximal unique matches (MUMs) and rare maximal exact matches (MEMs) between
+ * A and B -- as rules over neighbouring ranks of the SA, LCP and BWT of T = A . sep . B. One streaming pass; the text is not read.
+ *
+ * Inputs: n entries of width W (4 or 8 bytes): SA, and LCP with LCP[0] counting as 0 whatever it holds. BWT: n bytes in rank order,
+ * as caps_sa_hip_build_bwt_* / caps_sa_hip_bwt_device_* give them (BWT[r] = T[SA[r] - 1]; the byte at the rank with SA[r] == 0 is
+ * never looked at). split in 0 .. n; side(p) = (p >= split): side 0 is A (with the separator), side 1 is B. The caller puts a byte
+ * that occurs nowhere else at split - 1. Without one a match may run across the boundary; the result is then still exactly what the
+ * rules below give on the arrays.
+ *
+ * LEFT-MAXIMAL: ranks p, q are left-maximal iff SA[p] == 0 or SA[q] == 0 or BWT[p] != BWT[q].
+ *
+ * MUM mode (cross_mums): rank r in 1 .. n - 1 yields a record iff, with l = LCP[r],
+ *   1. l >= min_len;
+ *   2. side(SA[r - 1]) != side(SA[r]);
+ *   3. (r - 1 == 0 ? 0 : LCP[r - 1]) < l and (r + 1 < n ? LCP[r + 1] : 0) < l;
+ *   4. r - 1 and r are left-maximal.
+ *
+ * MEM mode (cross_mems), max_occ in 2 .. CAPS_SA_CROSS_MAX_OCC:
+ *   - A RUN is a maximal rank range [h, h') with LCP[i] >= min_len for every h < i < h' (the k-mer runs for k = min_len).
+ *   - Runs with 2 <= h' - h <= max_occ are processed. Longer runs are skipped and counted, so the caller learns that the answer is
+ *     partial.
+ *   - In a processed run every pair p < q with different sides that is left-maximal yields a record with l = min LCP[p + 1 .. q].
+ *   - This is every MEM of at least min_len bytes between A and B whose first min_len bytes occur at most max_occ times in T, each
+ *     reported exactly once.
+ *
+ * Records: 24 bytes, little-endian:
+ *     u64 a | u64 b | u64 len
+ * a is the side-0 position and b the side-1 position, both absolute in T. MUM mode: in rank order. MEM mode: ordered by q ascending,
+ * then p descending.
+ *
+ * summary (host, uint64_t[8]), always written: [0] the number of records; [1] the skipped runs (0 in MUM mode); [2..4] the longest
+ * common substring: the maximum of LCP[r] over r in 1 .. n - 1 with side(SA[r - 1]) != side(SA[r]), independent of min_len and mode,
+ * the lowest such r winning on ties -- its len, a and b, or 0, 0, 0 when there is none or the maximum is 0; [5..7] zero.
+ *
+ * Protocol and errors, as for caps_sa_hip_kmers*: dRecords = NULL is the counting call. A non-null dRecords (8-byte aligned) with
+ * more records than capacity is CAPS_SA_EINVAL: the summary is still valid and no record is written. CAPS_SA_EINVAL, checked before
+ * any allocation, with nothing written: min_len == 0; split > n; max_occ outside 2 .. 64 in MEM mode; a null array with n > 0; a
+ * null summary; n > UINT32_MAX with _u32; a workspace that is too small. n = 0, split = 0 and split = n succeed with no records.
+ *
+ * For arrays that are no text's the calls terminate, read only [0, n) of each array and write only inside the outputs: nothing is
+ * indexed by a value read from SA or LCP, and there is no validation pass. The work per rank is bounded for any input: in MEM mode a
+ * rank reads at most max_occ + 1 entries of LCP and max_occ - 1 each of SA and BWT beside its own. A look-back or look-forward that
+ * has not met a head within max_occ ranks gives the run up, consistently for every rank of it: 'A' * n with min_len = 1 is one run,
+ * skipped, counted once (at its head). The workspace (caps_sa_hip_cross_workspace_bytes) is O(n / 16,384) words, no array of n
+ * entries; NULL is allocated and freed by the call. dSA, dLCP, dBWT, dRecords and workspace are device pointers on the current
+ * device; the work runs on hip_stream and has completed on return. Ranks beyond 2^32 (_u64 with n > UINT32_MAX) are untested.
+ */
+#define CAPS_SA_CROSS_MAX_OCC 64
+int caps_sa_hip_cross_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes);
+int caps_sa_hip_cross_mums_device_u32(const void* dSA, const void* dLCP, const void* dBWT, uint64_t n, uint64_t split, uint64_t min_len,
+                                      void* dRecords, uint64_t capacity, uint64_t* summary, void* workspace, uint64_t workspace_bytes,
+                                      void* hip_stream);
+int caps_sa_hip_cross_mums_device_u64(const void* dSA, const void* dLCP, const void* dBWT, uint64_t n, uint64_t split, uint64_t min_len,
+                                      void* dRecords, uint64_t capacity, uint64_t* summary, void* workspace, uint64_t workspace_bytes,
+                                      void* hip_stream);
+int caps_sa_hip_cross_mems_device_u32(const void* dSA, const void* dLCP, const void* dBWT, uint64_t n, uint64_t split, uint64_t min_len,
+                                      uint32_t max_occ, void* dRecords, uint64_t capacity, uint64_t* summary, void* workspace,
+                                      uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_cross_mems_device_u64(const void* dSA, const void* dLCP, const void* dBWT, uint64_t n, uint64_t split, uint64_t min_len,
+                                      uint32_t max_occ, void* dRecords, uint64_t capacity, uint64_t* summary, void* workspace,
+                                      uint64_t workspace_bytes, void* hip_stream);
+/* Host SA, LCP and BWT (and host records): the arrays go up into device buffers of the call's own on `device`, the records come down. */
+int caps_sa_hip_cross_mums_u32(const uint32_t* SA, const uint32_t* LCP, const uint8_t* BWT, uint64_t n, uint64_t split, uint64_t min_len,
+                               void* records, uint64_t capacity, uint64_t* summary, int device);
+int caps_sa_hip_cross_mums_u64(const uint64_t* SA, const uint64_t* LCP, const uint8_t* BWT, uint64_t n, uint64_t split, uint64_t min_len,
+                               void* records, uint64_t capacity, uint64_t* summary, int device);
+int caps_sa_hip_cross_mems_u32(const uint32_t* SA, const uint32_t* LCP, const uint8_t* BWT, uint64_t n, uint64_t split, uint64_t min_len,
+                               uint32_t max_occ, void* records, uint64_t capacity, uint64_t* summary, int device);
+int caps_sa_hip_cross_mems_u64(const uint64_t* SA, const uint64_t* LCP, const uint8_t* BWT, uint64_t n, uint64_t split, uint64_t min_len,
+                               uint32_t max_occ, void* records, uint64_t capacity, uint64_t* summary, int device);
+
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
 /* merge_sort (src/Suffix_Array.cpp:112-129) of an arbitrary list of cnt distinct suffix
