@@ -79,6 +79,7 @@ class Stats(ctypes.Structure):
         ("knot_slot_splits_redone", ctypes.c_uint32),
         ("spill_entries", ctypes.c_uint64),
         ("direct_records", ctypes.c_uint32),
+        ("tile_chain", ctypes.c_uint32),
     ]
 
     def as_dict(self) -> dict:

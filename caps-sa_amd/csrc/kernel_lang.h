@@ -40,6 +40,7 @@ namespace caps { struct EmulCtx { uint32_t block_idx, grid_dim, block_dim; }; }
 #define STREAM_STORE2(p, v) (*(p) = (v))
 #define K_GRID_DIM (kctx_.grid_dim)
 #define K_BLOCK_DIM (kctx_.block_dim)
+#define ISSUE_FENCE() ((void)0)                 /* GPU: keeps the loads above it above it, see below */
 // CAPS_EMUL_RACE (tests/emul/race_rt.h): the barrier-race detector -- every PAR iteration announces its thread, every barrier
 // starts a new epoch, LDS arrays register their storage, atomics mark themselves.  Without the switch all of it expands to nothing.
 #ifdef CAPS_EMUL_RACE
@@ -156,6 +157,10 @@ static inline uint32_t caps_bswap32(uint32_t x) { return __builtin_bswap32(x); }
 #endif
 #define K_GRID_DIM (gridDim.x)
 #define K_BLOCK_DIM (blockDim.x)
+// A fence for the compiler only (no instruction, no wait): memory accesses are not moved across it.  For loads that are issued
+// early ON PURPOSE, ahead of a branch they do not depend on -- without it the compiler sinks them to their first use, behind
+// the branch and the round trip its condition waits for (tile_sort_kernel's bucket-indexed build).
+#define ISSUE_FENCE() asm volatile("" ::: "memory")
 #define PAR(tid) for (uint32_t tid = threadIdx.x, par_once_ = 1; par_once_; par_once_ = 0)
 // PAR_FRESH: the same, but the compiler is kept from knowing that this region's thread index is the one of the regions
 // before it.  What a kernel with many phases derives from the index (addresses, element numbers) is otherwise computed

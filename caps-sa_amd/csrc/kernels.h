@@ -885,30 +885,14 @@ DEV_INLINE const uint64_t* tile_src(const uint64_t* in, const uint64_t* out, boo
 DEV_INLINE const uint32_t* tile_src(const uint32_t* in, const uint64_t*, bool) { return in; }
 
 // Shared pieces of the two tile sort kernels (macros: they use the kernels' TL registers).
-#define TILE_SORT_PROLOGUE                                                                                      \
-    const uint32_t b = K_BLOCK_IDX;                                                                             \
-    if (b >= sd.tile_off[sd.G]) return;                                                                         \
-    const uint32_t g = sd.tile_rec[b].g;                                                                          \
-    const TileInfo t = tile_info(sd, b);                                                                        \
-    const uint64_t start = t.s0 + (uint64_t)t.tl * TILE_E;                                                      \
-    const uint32_t cnt = (uint32_t)(t.s1 - start < TILE_E ? t.s1 - start : TILE_E);                             \
-    /* LCPs are only needed from the sort that completes a segment: lcp_mode 0 = never,                      */ \
-    /* 1 = when the whole segment is this tile (otherwise its final merge pass emits them).                  */ \
-    const bool with_lcp = lcp_mode != 0 && (t.s1 - t.s0) <= TILE_E;                                             \
-    /* fin.sa != null: a segment completed here goes straight to the caller's SA / LCP arrays                */ \
-    /* (its head LCP is filled in by head_lcp_kernel from the boundary records).                             */ \
-    const bool direct = with_lcp && fin.sa != nullptr;                                                          \
-    /* slot_cap != 0: the input of segment (bucket) g sits in its fixed-capacity slot, see bucket_scatter_kernel.  */ \
-    /* (A bucket that outgrew its slot -- speculative split by knots -- was put together at its place in the OUTPUT */ \
-    /* arrays: TILE_OUTGROWN.  The kernels at the head of the queue chain never see such a tile: the tile table    */ \
-    /* they are launched with shows it EMPTY (hot_tiles_kernel), they pass it on as unfinished, and the builds      */ \
-    /* behind them -- launched with the true table -- read it there, tile_src below.  No code for it here: a test   */ \
-    /* in tile_sort_eq_kernel's plain build cost ten more SGPR spills and 5 % of its time.)                         */ \
-    const uint64_t in0 = slot_cap ? (uint64_t)g * slot_cap : start;
+// (The start of a tile -- which segment, where its input sits, whether it emits LCPs -- is written out in tile_sort_kernel,
+// "the start of a tile" there; the other tile kernels derive the same values for the tile they took from their queue.)
 #define TILE_OUTGROWN (slot_cap != 0 && t.s1 - t.s0 > (uint64_t)slot_cap)
 
 #define TILE_SRC_KEY in_key
 #define TILE_SRC_SA in_sa
+/* (tile_sort_kernel's bucket-indexed build has a copy of the clears of flag and hist below -- without kmm, which it never reads --    */
+/* next to its late load: a word added to the clears here is added there.)                                                       */
 #define TILE_SORT_LOAD                                                                                          \
     PAR(tid) {                                                                                                  \
         if (tid == 0) { kmm[0] = ~0ull; kmm[1] = 0; flag[0] = 0; }                                              \
@@ -942,7 +926,9 @@ DEV_INLINE const uint32_t* tile_src(const uint32_t* in, const uint64_t*, bool) {
 /* LDS, so tile_sort_eq_kernel (which keeps spilled registers in scratch and emits straight before its next tile) uses the  */
 /* LDS-scope barrier: __syncthreads() would also wait for every scratch store and every result store of the wave.           */
 #define TILE_SYNC() SYNC()
-#define TILE_SORT_RANGE                                                                                         \
+#define TILE_SORT_RANGE TILE_SORT_RANGE_(seg_map[g])
+/* MAP: the prepared bin map of segment g (tile_sort_kernel's bucket-indexed build has loaded it ahead of the barrier) */
+#define TILE_SORT_RANGE_(MAP)                                                                                   \
     const bool known_range = seg_map != nullptr;                                                                \
     if (!known_range) {                                                                                         \
         TILE_SYNC(); /* kmm initialised */                                                                      \
@@ -961,7 +947,7 @@ DEV_INLINE const uint32_t* tile_src(const uint32_t* in, const uint64_t*, bool) {
         }                                                                                                       \
     }                                                                                                           \
     TILE_SYNC();                                                                                                \
-    const BucketParams tb = known_range ? seg_map[g] : make_bucket_params(kmm[0], kmm[1], TILE_BINS); /* block-uniform */
+    const BucketParams tb = known_range ? (MAP) : make_bucket_params(kmm[0], kmm[1], TILE_BINS); /* block-uniform */
 
 // registers -> final slots TL(rd) in LDS
 #define TILE_SORT_PLACE_FINAL                                                                                   \
@@ -1020,7 +1006,16 @@ DEV_INLINE const uint32_t* tile_src(const uint32_t* in, const uint64_t*, bool) {
 // KT = uint32_t: the slots hold 32-bit keys (text.h key32_of; kshift[bucket] = the shift of the bucket's group).  Only
 // completed segments written straight to SA / LCP (`direct`) exist then; a tile this kernel cannot finish is re-sorted by the
 // kernels below from 64-bit keys cut from the text.
-template <typename idx_t, int BITS, bool FROM_TEXT, typename KT = uint64_t>
+// CHAIN != 0: the bucket-indexed build, for a sort over slots of TILE_E elements in which every bucket fits its slot (a bucket is
+// then exactly one tile, its input sits at g * slot_cap whatever the tables say): workgroup g takes bucket g, and its first
+// instructions are the loads of the slot -- a tile of the table launch starts with two dependent round trips before them (its tile
+// record, then the slot the record names).  The bucket's bounds and its bin map are fetched while those loads are in flight; an
+// empty bucket returns; lanes at or beyond the bucket's size keep whatever the (allocated) slot held, every later phase is guarded
+// by e < cnt.  All but the last of the TILE_EPT loads per thread are issued ahead of the bounds, the last once cnt is known: a
+// bucket fills 7/8 of its slot, and loading the whole slot early -- 5 GB more at 3e9 -- took back most of the gain.
+// The queue of unfinished tiles still carries tile indices (the kernels behind this one read their tiles through tile_rec):
+// tile_off[g].  grid = the slots.
+template <typename idx_t, int BITS, bool FROM_TEXT, typename KT = uint64_t, int CHAIN = 0>
 GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX SegDesc sd, const uint32_t* __restrict__ P, uint64_t n,
                                                   uint64_t text_base, uint32_t lcp_mode, uint32_t slot_cap, const KT* in_key,
                                                   const idx_t* in_sa, uint64_t* out_key, idx_t* out_sa, idx_t* out_lcp,
@@ -1030,8 +1025,52 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX Seg
     constexpr bool TILE_RUNS = false;        // ties here are shallow (suffix_less_tie_bounded), so are the LCPs
     constexpr bool K32 = sizeof(KT) == 4;
     constexpr bool TILE_KEYS_FROM_TEXT = false;
+    constexpr bool BY_BUCKET = CHAIN != 0;
+    constexpr uint32_t CHAIN_EARLY = BY_BUCKET ? TILE_EPT - 1 : 0u;
     static_assert(!K32 || !FROM_TEXT, "32-bit keys come from the slots of level B");
-    TILE_SORT_PROLOGUE
+    static_assert(!BY_BUCKET || (!FROM_TEXT && !K32 && sizeof(idx_t) == 4), "bucket-indexed: 64-bit keys and 32-bit indices in slots");
+    TL_DECL(KT, rk, TILE_EPT);
+    TL_DECL(idx_t, rs, TILE_EPT);
+    uint64_t bs0 = 0, bs1 = 0;                                              // BY_BUCKET: the bucket's bounds and its bin map, requested
+    BucketParams tb_early = BucketParams();                                 //   here and not waited for before the loads below are out
+    // BY_BUCKET REQUIRES seg_map (one prepared bin map per slot of the grid) and seg_start[0 .. grid]: the launch reads both
+    // unconditionally, and this build does not initialise kmm -- the min / max route of TILE_SORT_RANGE_ (seg_map == null) would
+    // read it unset.  segmented_sort takes this launch only with seg_map != null and grid <= G (pipeline.h, by_bucket).
+    if (BY_BUCKET) {
+        bs0 = sd.seg_start[K_BLOCK_IDX];
+        bs1 = sd.seg_start[K_BLOCK_IDX + 1];
+        tb_early = seg_map[K_BLOCK_IDX];
+        PAR(tid) {
+            const uint64_t in0e = (uint64_t)K_BLOCK_IDX * slot_cap;
+            UNROLL
+            for (uint32_t k = 0; k < CHAIN_EARLY; ++k) {
+                TL(rk, tid, k) = STREAM_LOAD(&in_key[in0e + tid + k * TILE_NT]);
+                TL(rs, tid, k) = STREAM_LOAD(&in_sa[in0e + tid + k * TILE_NT]);
+            }
+        }
+        ISSUE_FENCE();                                                        // ... and stay ahead of the branch on the bounds
+    }
+    // ---- the start of a tile ----
+    const uint32_t b = K_BLOCK_IDX;                                           // the tile, or (BY_BUCKET) the bucket
+    if (!BY_BUCKET && b >= sd.tile_off[sd.G]) return;
+    const uint32_t g = BY_BUCKET ? b : sd.tile_rec[b].g;
+    const TileInfo t = BY_BUCKET ? TileInfo{bs0, bs1, 0u, g, {0u, 0u}} : tile_info(sd, b);
+    if (BY_BUCKET && t.s1 == t.s0) return;
+    const uint64_t start = t.s0 + (uint64_t)t.tl * TILE_E;
+    const uint32_t cnt = (uint32_t)(t.s1 - start < TILE_E ? t.s1 - start : TILE_E);
+    // LCPs are only needed from the sort that completes a segment: lcp_mode 0 = never, 1 = when the whole segment is this tile
+    // (otherwise its final merge pass emits them).
+    const bool with_lcp = lcp_mode != 0 && (t.s1 - t.s0) <= TILE_E;
+    // fin.sa != null: a segment completed here goes straight to the caller's SA / LCP arrays (its head LCP is filled in by
+    // head_lcp_kernel from the boundary records).
+    const bool direct = with_lcp && fin.sa != nullptr;
+    // slot_cap != 0: the input of segment (bucket) g sits in its fixed-capacity slot, see bucket_scatter_kernel.  (A bucket that
+    // outgrew its slot -- speculative split by knots -- was put together at its place in the OUTPUT arrays: TILE_OUTGROWN.  The
+    // kernels at the head of the queue chain never see such a tile: the tile table they are launched with shows it EMPTY
+    // (hot_tiles_kernel), they pass it on as unfinished, and the builds behind them -- launched with the true table -- read it
+    // there, tile_src above.  No code for it here: a test in tile_sort_eq_kernel's plain build cost ten more SGPR spills and 5 %
+    // of its time.)
+    const uint64_t in0 = slot_cap ? (uint64_t)g * slot_cap : start;
     const uint32_t TILE_KEY_SHIFT = K32 ? kshift[g] : 0u;                                  // block-uniform
     const uint32_t tie_from = K32 ? (TILE_KEY_SHIFT + 32u) / BITS : TextTraits<BITS>::KCH;   // chars two equal keys stand for
     SHARED_ARRAY(KT, skey, TILE_E);
@@ -1049,14 +1088,27 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX Seg
     // ... and no second placement (as in tile_sort_eq_kernel): the element that knows its final position d notes perm[d] = its slot,
     // the emit phase reads keys and indices through perm -- one barrier, two LDS writes and a read per element less
     SHARED_ARRAY(uint16_t, perm, SLOT_ORDER ? TILE_E : 1);
-    TL_DECL(KT, rk, TILE_EPT);
-    TL_DECL(idx_t, rs, TILE_EPT);
     TL_DECL(uint32_t, rd, TILE_EPT);
     TL_DECL(uint32_t, rb, TILE_EPT);
 
     PHASE_T0();
-    TILE_SORT_LOAD
-    TILE_SORT_RANGE
+    if (BY_BUCKET) {
+        PAR(tid) {
+            if (tid == 0) flag[0] = 0;
+            for (uint32_t i = tid; i <= TILE_BINS; i += K_BLOCK_DIM) hist[i] = 0;
+            UNROLL
+            for (uint32_t k = CHAIN_EARLY; k < TILE_EPT; ++k) {
+                const uint32_t e = tid + k * TILE_NT;
+                if (e < cnt) {
+                    TL(rk, tid, k) = STREAM_LOAD(&in_key[in0 + e]);
+                    TL(rs, tid, k) = STREAM_LOAD(&in_sa[in0 + e]);
+                }
+            }
+        }
+    } else {
+        TILE_SORT_LOAD
+    }
+    TILE_SORT_RANGE_(BY_BUCKET ? tb_early : seg_map[g])
     PHASE_MARK(0);                                             // load (+ range)
     bool fast = cnt > 1 && tb.range > 0;
     if (fast) {
@@ -1138,7 +1190,7 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX Seg
 #endif
     // unfinished: queue the tile for tile_sort_general_kernel (redo[0] = queue length)
     if (!fast) {
-        PAR(tid) { if (tid == 0) redo[1 + FETCH_ADD_U32(&redo[0], 1u)] = b; }
+        PAR(tid) { if (tid == 0) redo[1 + FETCH_ADD_U32(&redo[0], 1u)] = BY_BUCKET ? sd.tile_off[g] : b; }
         return;
     }
     if (SLOT_ORDER && cnt > 1) {
@@ -1172,7 +1224,7 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX Seg
     PHASE_MARK(6);                                             // emit (+ LCPs); the stores themselves drain after the mark
 }
 
-// The tile table for the kernels at the head of the queue chain of a sort over slots with outgrown buckets (TILE_SORT_PROLOGUE):
+// The tile table for the kernels at the head of the queue chain of a sort over slots with outgrown buckets (tile_sort_kernel, the start of a tile):
 // a copy in which the tiles of every segment longer than slot_cap are empty.
 GLOBAL_FN LAUNCH_BOUNDS(256) hot_tiles_kernel(KCTX SegDesc sd, uint32_t slot_cap, TileInfo* __restrict__ hot)
 {
@@ -1387,7 +1439,7 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, CAPS_EQ_WAVES) tile_sort_eq_kernel(KCTX SegDes
     const uint32_t cnt = (uint32_t)(t.s1 - start < TILE_E ? t.s1 - start : TILE_E);
     const bool with_lcp = lcp_mode != 0 && (t.s1 - t.s0) <= TILE_E;
     const bool direct = with_lcp && fin.sa != nullptr;
-    // a bucket that outgrew its slot (TILE_SORT_PROLOGUE): the plain build sees its tiles empty and passes them on (`fast` below is
+    // a bucket that outgrew its slot (tile_sort_kernel, the start of a tile): the plain build sees its tiles empty and passes them on (`fast` below is
     // false for them, no flag is up: redo_deep); the VDEEP build reads them where they were put together -- at their place in the
     // output arrays -- and sorts them in place
     const bool in_slot = !VDEEP || !TILE_OUTGROWN;
@@ -1934,7 +1986,7 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_general_kernel(
     const uint32_t cnt = (uint32_t)(t.s1 - start < TILE_E ? t.s1 - start : TILE_E);
     const bool with_lcp = lcp_mode != 0 && (t.s1 - t.s0) <= TILE_E;
     const bool direct = with_lcp && fin.sa != nullptr;
-    // a bucket that outgrew its slot was put together at its place in the output arrays (TILE_SORT_PROLOGUE): sorted in place
+    // a bucket that outgrew its slot was put together at its place in the output arrays (tile_sort_kernel, the start of a tile): sorted in place
     const bool in_slot = !TILE_OUTGROWN;
     const uint64_t in0 = slot_cap != 0 && in_slot ? (uint64_t)g * slot_cap : start;
     const uint64_t* src_key = tile_src(in_key, out_key, !in_slot);

@@ -77,6 +77,9 @@ constexpr uint32_t DIRECT_SUB = CAPS_DIRECT_SUB;
 // Which hand-overs of the direct path travel as (key, index) records when CAPS_SA_RECORDS does not say (run_direct): bit 0 =
 // level A -> level B.
 constexpr uint32_t DIRECT_RECORDS_DEFAULT = 1;
+// Which stages of the shortened start of a tile the final sort of the direct path uses when CAPS_SA_TILE_CHAIN does not say: bit 0 =
+// tile_sort_kernel's bucket-indexed launch.
+constexpr uint32_t DIRECT_TILE_CHAIN_DEFAULT = 1;
 // Quantile mode of the direct path (skewed keys): mean bucket size (sampling noise on top: sigma = 1 / sqrt(QUANTILE_SPB)) and
 // samples drawn per bucket.
 #ifndef CAPS_BUCKET_Q_32NDS
@@ -500,6 +503,9 @@ struct SortOpts {
     void* final_sa = nullptr;     // non-null (with need_lcp): completed segments are written straight to the
     void* final_lcp = nullptr;    //   caller's SA / LCP arrays; boundary records in `bnd` (6 arrays of G entries)
     struct { uint64_t *first_key, *last_key; void *first_sa, *last_sa; } bnd = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t tile_chain = 0;            // stages of the shortened start of a tile (run_direct, CAPS_SA_TILE_CHAIN; 0 = the table launch):
+                                        //   bit 0 = tile_sort_kernel's bucket-indexed build where the sort qualifies (see its launch below)
+    uint32_t* tile_chain_used = nullptr;   // host word: the stages the sort's tile_sort_kernel launch really ran with
     KernelClock* tile_clock = nullptr;
     KernelClock* merge_clock = nullptr;
     KernelClock* scatter_clock = nullptr;
@@ -539,6 +545,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
     uint32_t slot_cap = 0;                           // != 0: the tile sort's input sits in fixed-capacity slots
     uint64_t* slot_key = nullptr;
     idx_t* slot_sa = nullptr;
+    uint32_t slot_grid = 0;                          // != 0: the slots of a kept linear slot split (every bucket is one tile or empty)
     if (o.bk && (max_len > TILE_E || o.seg_ends)) {      // segments in regions are always bucketed: results are written compactly
         const BucketBufs& bk = *o.bk;
         const SegDesc psd = s.desc();
@@ -844,6 +851,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
             bucket_tiles();
         } else if (!slot_cap) {
             slot_cap = TILE_E;                           // the tile sort reads the slots, writes `cur`
+            slot_grid = (uint32_t)nb_here;               // (no bucket beyond them holds anything: the scatter wrote inside the slots)
         }
 
         mark("bucket scatter");
@@ -915,6 +923,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
     const idx_t* in_sa = slot_cap ? slot_sa : (o.in_key && segs.seg_start == s.seg_start) ? static_cast<const idx_t*>(o.in_sa) : cur.sa;
     const uint8_t* no_shift = nullptr;
     r.k32 = o.k32 && slot_cap != 0;
+    std::vector<uint64_t> dbg_ss;                          // dbg, bucket-indexed launch: the bounds of its buckets
     if (from_text) {
         CAPS_LAUNCH((tile_sort_kernel<idx_t, BITS, true>), n_tiles, TILE_NT, be, sd, P, n, o.text_base, lcp_mode, 0u,
                     (const uint64_t*)nullptr, (const idx_t*)nullptr, cur.key, cur.sa, cur.lcp, fin, seg_map, redo, no_shift);
@@ -944,8 +953,47 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
             CAPS_LAUNCH_RUNS(tile_sort_general_kernel, (idx_t, BITS, false), ggrid, TILE_NT, be, sd, P, n, (uint64_t)0, lcp_mode, slot_cap,
                         in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, (const uint32_t*)redo3, 0u, bflag);
         } else {
+        // The bucket-indexed launch (kernels.h tile_sort_kernel CHAIN): 32-bit indices and 64-bit keys in two-array slots of a
+        // tile each, all kept -- a bucket is one tile at g * TILE_E, no table is needed to find it -- and nothing outgrown.
+        // Everything else (quantile mode, 64-bit indices, 32-bit keys, texts, redone splits, the waves and shards, which do not
+        // ask) keeps the table launch.  The tile tables exist either way: the queue kernels and finalize() read them.
+        bool by_bucket = false;
+        if constexpr (sizeof(idx_t) == 4)
+            by_bucket = (o.tile_chain & 1u) != 0 && !all_queued && slot_grid != 0 && slot_cap == TILE_E && max_len <= TILE_E &&
+                        seg_map != nullptr && sd_hot.tile_rec == sd.tile_rec && slot_grid <= segs.G;
+        if (o.tile_chain_used) *o.tile_chain_used = by_bucket ? 1u : 0u;
+        if (dbg && !by_bucket && (o.tile_chain & 1u) != 0)          // asked for and not taken: the stage log says why
+            std::fprintf(stderr, "[sort] table launch although the bucket-indexed one was asked for: idx bytes %u, all queued %d, slots %u of capacity %u "
+                         "(a tile: %u), longest bucket %llu, bin maps %d, second tile table %d, segments %u\n", (unsigned)sizeof(idx_t), all_queued ? 1 : 0,
+                         slot_grid, slot_cap, TILE_E, (unsigned long long)max_len, seg_map ? 1 : 0, sd_hot.tile_rec != sd.tile_rec ? 1 : 0, segs.G);
+        if (dbg && by_bucket) {
+            // The tests read this line and the "tiles queued" line below -- which of the launch's corner cases a text really has --
+            // through the patterns _LAUNCH and _QUEUED of tests/tile_chain_cases.py: change wording and patterns together.
+            dbg_ss.resize((size_t)slot_grid + 1);
+            be.d2h(dbg_ss.data(), segs.seg_start, dbg_ss.size() * sizeof(uint64_t));
+            be.sync();
+            const std::vector<uint64_t>& ss = dbg_ss;
+            uint32_t last = 0, inner = 0, small = 0, cut = 0;
+            uint64_t least = ~0ull;
+            for (uint32_t g = 0; g < slot_grid; ++g) if (ss[g + 1] > ss[g]) last = g;
+            for (uint32_t g = 0; g < last; ++g) inner += ss[g + 1] == ss[g] ? 1u : 0u;
+            for (uint32_t g = 0; g <= last; ++g) {
+                const uint64_t len = ss[g + 1] - ss[g];
+                if (!len) continue;
+                small += len < TILE_NT ? 1u : 0u;                                   // (some lanes of EVERY early load lie beyond it)
+                cut += len < (uint64_t)(TILE_EPT - 1) * TILE_NT ? 1u : 0u;           // (some lanes of the last early load do)
+                least = len < least ? len : least;
+            }
+            std::fprintf(stderr, "[sort] bucket-indexed launch: %u slots for %u tiles, %u empty slots before the last full one (slot %u, %llu elements), "
+                         "%u buckets below %u elements, %u below %u, smallest %llu\n", slot_grid, n_tiles, inner, last,
+                         (unsigned long long)(ss[last + 1] - ss[last]), small, TILE_NT, cut, (TILE_EPT - 1) * TILE_NT, (unsigned long long)least);
+        }
         if (all_queued && !per_tile) CAPS_LAUNCH(queue_all_tiles_kernel, (n_tiles + 255) / 256, 256, be, sd, redo);
-        else if (!all_queued) CAPS_LAUNCH((tile_sort_kernel<idx_t, BITS, false>), n_tiles, TILE_NT, be, sd_hot, P, n, (uint64_t)0, lcp_mode, slot_cap,
+        else if (by_bucket) {
+            if constexpr (sizeof(idx_t) == 4)
+                CAPS_LAUNCH((tile_sort_kernel<idx_t, BITS, false, uint64_t, 1>), slot_grid, TILE_NT, be, sd, P, n, (uint64_t)0, lcp_mode, slot_cap,
+                            in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, seg_map, redo, no_shift);
+        } else if (!all_queued) CAPS_LAUNCH((tile_sort_kernel<idx_t, BITS, false>), n_tiles, TILE_NT, be, sd_hot, P, n, (uint64_t)0, lcp_mode, slot_cap,
                     in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, seg_map, redo, no_shift);
         if (per_tile) {
             // (no queue: workgroup b takes tile b)
@@ -996,6 +1044,20 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
         be.d2h(&q[0], redo, 4); be.d2h(&q[1], redo2, 4); be.d2h(&q[2], redo3, 4);
         be.sync();
         std::fprintf(stderr, "[sort] queues after the tile sorts: %u %u %u of %u tiles, deferring %d\n", q[0], q[1], q[2], n_tiles, bflag ? 1 : 0);
+        if (!dbg_ss.empty()) {
+            // the bucket-indexed launch queued tile indices (tile_off[g]): the entries whose tile is not the slot of the same
+            // number (an empty slot lies before it), and the ones that name no tile or a tile of no bucket of the launch
+            std::vector<uint32_t> qe(q[0]), slot_of_tile;
+            if (q[0]) be.d2h(qe.data(), redo + 1, (size_t)q[0] * sizeof(uint32_t));
+            be.sync();
+            for (uint32_t g = 0; g + 1 < dbg_ss.size(); ++g) if (dbg_ss[g + 1] > dbg_ss[g]) slot_of_tile.push_back(g);
+            uint32_t moved = 0, bad = 0;
+            for (uint32_t t : qe) {
+                if (t >= slot_of_tile.size()) ++bad;
+                else if (slot_of_tile[t] != t) ++moved;
+            }
+            std::fprintf(stderr, "[sort] bucket-indexed launch: %u tiles queued, %u behind an empty slot, %u not tiles of the launch\n", q[0], moved, bad);
+        }
     }
     if (o.tile_clock) { o.tile_clock->spans.push_back({t0, t1}); o.tile_clock->elems.push_back(n_elems); }
     const uint32_t grid = n_tiles < be.persistent_blocks() ? n_tiles : be.persistent_blocks();
@@ -1438,7 +1500,7 @@ private:
     uint32_t passes1_ = 0, passes2_ = 0, passesS_ = 0;
     BackendEvent e2_, e3_, e4_, e5_, e6_, e7_, la0_, la1_;
     uint64_t max_part_ = 0;
-    uint32_t path_direct_ = 0, path_fallback_ = 0, direct_groups_ = 0, direct_quantile_ = 0, direct_k32_ = 0, direct_records_ = 0, run_buckets_ = 0;
+    uint32_t path_direct_ = 0, path_fallback_ = 0, direct_groups_ = 0, direct_quantile_ = 0, direct_k32_ = 0, direct_records_ = 0, tile_chain_ = 0, run_buckets_ = 0;
     uint64_t direct_max_group_ = 0;
     uint64_t tie_groups_ = 0, tie_elems_ = 0;
     uint32_t tie_levels_ = 0;
@@ -1761,6 +1823,11 @@ private:
         const uint32_t rec_want = rec_env ? (uint32_t)std::atoi(rec_env) : DIRECT_RECORDS_DEFAULT;
         const bool rec_a = (rec_want & 1u) != 0 && sizeof(idx_t) == 4 && !k32 && big_tiles;
         direct_records_ = rec_a ? 1u : 0u;
+        // The start of a tile of the final sort (kernels.h tile_sort_kernel CHAIN; CAPS_SA_TILE_CHAIN, a mask read here, once per
+        // build: bit 0 = the bucket-indexed launch, 0 = the table launch everywhere).  What the sort really ran with: tile_chain_.
+        const char* chain_env = std::getenv("CAPS_SA_TILE_CHAIN");
+        const uint32_t chain_want = chain_env ? (uint32_t)std::atoi(chain_env) : DIRECT_TILE_CHAIN_DEFAULT;
+        tile_chain_ = 0;
         if (k32) CAPS_LAUNCH(group_shift_kernel, (K1 + 255) / 256, 256, be_, (const uint64_t*)pl_.gkey, K1, pl_.gshift);
         if (quantile) {
             // more samples, sorted in the (still idle) big buffers; their quantiles are the bucket boundaries and, every KPG-th, the group keys
@@ -1942,6 +2009,7 @@ private:
                 if (quantile) { ow.knots = pl_.knots + (size_t)g0 * KPG; ow.knots_have_prev = g0 > 0; }
             }
             set_final(ow, dSA + base, dLCP + base);
+            if (W == 1) { ow.tile_chain = chain_want; ow.tile_chain_used = &tile_chain_; }       // (one sort: the last word stands)
             if (elems_w) {
                 SortResult<idx_t> r2 = seg_sort<BITS>(gw, n_tiles_w, max_len_w, W > 1 ? wave_scratch_ : pl_.A, pl_.B, elems_w, ow, true);
                 if (r2.failed) {                                                                // a slot overflowed under 32-bit keys: again with 64
@@ -2058,6 +2126,7 @@ private:
             st->n_devices = 1;
             st->direct_key_bits = path_direct_ && direct_k32_ ? 32u : 64u;
             st->direct_records = path_direct_ ? direct_records_ : 0u;
+            st->tile_chain = path_direct_ ? tile_chain_ : 0u;
             st->direct_max_group = direct_max_group_;
             st->level_a_ms = direct_groups_ ? be_.elapsed_ms(la0_, la1_) : 0.0;
             st->slot_splits = slot_stats_[0];

@@ -109,6 +109,11 @@ typedef struct caps_sa_stats {
      * variable CAPS_SA_RECORDS chooses, 0 = none; always 0 with 64-bit indices, with 32-bit keys, and for a build that did not take
      * the direct path */
     uint32_t direct_records;
+    /* direct path: the stages of the shortened start of a tile that the final sort's tile_sort_kernel launch ran with -- a mask, bit 0 =
+     * the bucket-indexed launch (workgroup g sorts bucket g and loads its slot before anything else; csrc/kernels.h).  The environment
+     * variable CAPS_SA_TILE_CHAIN chooses, 0 = the launch over the tile table; always 0 in quantile mode, with 64-bit indices, with
+     * 32-bit keys, when a slot overflowed and the split was redone, for a build that leaves in waves, and off the direct path */
+    uint32_t tile_chain;
 } caps_sa_stats;
 
 /* sizeof(caps_sa_stats) / sizeof(caps_sa_shard_info) of THIS library.  Both structs grow at their end from release to release and
