@@ -80,6 +80,7 @@ class Stats(ctypes.Structure):
         ("spill_entries", ctypes.c_uint64),
         ("direct_records", ctypes.c_uint32),
         ("tile_chain", ctypes.c_uint32),
+        ("scatter_issue", ctypes.c_uint32),
     ]
 
     def as_dict(self) -> dict:

@@ -41,6 +41,7 @@ namespace caps { struct EmulCtx { uint32_t block_idx, grid_dim, block_dim; }; }
 #define K_GRID_DIM (kctx_.grid_dim)
 #define K_BLOCK_DIM (kctx_.block_dim)
 #define ISSUE_FENCE() ((void)0)                 /* GPU: keeps the loads above it above it, see below */
+#define DRAIN_GLOBAL() ((void)0)                /* GPU: waits for the wave's outstanding global accesses, see below */
 // CAPS_EMUL_RACE (tests/emul/race_rt.h): the barrier-race detector -- every PAR iteration announces its thread, every barrier
 // starts a new epoch, LDS arrays register their storage, atomics mark themselves.  Without the switch all of it expands to nothing.
 #ifdef CAPS_EMUL_RACE
@@ -161,6 +162,12 @@ static inline uint32_t caps_bswap32(uint32_t x) { return __builtin_bswap32(x); }
 // early ON PURPOSE, ahead of a branch they do not depend on -- without it the compiler sinks them to their first use, behind
 // the branch and the round trip its condition waits for (tile_sort_kernel's bucket-indexed build).
 #define ISSUE_FENCE() asm volatile("" ::: "memory")
+// s_waitcnt vmcnt(0): the wave's global loads, stores and returning atomics have all completed.  For points where nothing is
+// outstanding when the kernel RUNS but the compiler cannot know it: it counts an access issued on one side of a branch as pending
+// on the other side too, behind the join, and then waits for everything in flight where a register of such an access is
+// written again -- between the loads or stores that a kernel wants to issue back to back.  The barriers do not do it:
+// __syncthreads() on gfx950 waits for LDS traffic only, like SYNC_LDS() (bucket_scatter_kernel's ISSUE build uses this).
+#define DRAIN_GLOBAL() __builtin_amdgcn_s_waitcnt(0x0F70)     /* vmcnt 0; expcnt 7 and lgkmcnt 15: not waited for */
 #define PAR(tid) for (uint32_t tid = threadIdx.x, par_once_ = 1; par_once_; par_once_ = 0)
 // PAR_FRESH: the same, but the compiler is kept from knowing that this region's thread index is the one of the regions
 // before it.  What a kernel with many phases derives from the index (addresses, element numbers) is otherwise computed

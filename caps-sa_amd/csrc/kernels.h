@@ -3030,7 +3030,20 @@ constexpr uint32_t SPILL_CHUNK = TILE_E / 128 ? TILE_E / 128 : 1;   // a tile of
 
 // REC_IN (SRC_ARRAYS, 64-bit keys, 32-bit indices): the elements come in as KeySaRec records (in_key points at them, in_sa is
 // unused) -- the stream of level A of the direct path; they leave in two arrays as before.
-template <typename idx_t, int BITS, int SRC, int MAP, typename KT = uint64_t, bool SPILL = false, bool REC_IN = false>
+// ISSUE (REC_IN, MAP_LINEAR: level B of the direct path in linear mode): a tile's memory traffic is ISSUED together.  The plain
+// build loads an element, waits for it, classifies it and bumps the histogram before it asks for the next one -- TILE_EPT
+// dependent trips to HBM per thread, the first of them behind the trip for the bucket map of the tile's segment and the barrier
+// behind the zeroed histogram.  Here all TILE_EPT loads of a thread go out as soon as the tile record gives `start` and `cnt`;
+// the bucket map is asked for behind them, the histogram is zeroed and handed over while they travel, and the elements are
+// classified from the registers.  The other route (one bucket, or more than the histogram holds) is a block of its own that
+// returns: its global atomics are not in the element loop of the route that bumps the LDS histogram.  DRAIN_GLOBAL() stands
+// where the compiler's count of outstanding accesses is wrong and costs waits (kernel_lang.h): behind the other route (its exit
+// is joined with this route, and the first element would wait for all loads instead of its own), behind the classification
+// (a lane that skipped an element still counts its load: the re-ordering would wait for the cursor bumps that are meant to
+// travel meanwhile) and in front of the emit (a lane without a bucket to bump still counts the bump: every store pair waited
+// for the pair before it).  At none of the three is anything outstanding when the kernel runs, but the unused load of a wave
+// that lies beyond the end of a last tile.
+template <typename idx_t, int BITS, int SRC, int MAP, typename KT = uint64_t, bool SPILL = false, bool REC_IN = false, bool ISSUE = false>
 GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const uint32_t* __restrict__ P, uint64_t n_words,
                                                        uint64_t text_base, const KT* __restrict__ in_key,
                                                        const idx_t* __restrict__ in_sa, RunSrc<idx_t> rsrc,
@@ -3070,6 +3083,23 @@ GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const ui
     const TileInfo t = tile_info(sd, b);
     const uint64_t start = t.s0 + (uint64_t)t.tl * TILE_E;
     const uint32_t cnt = (uint32_t)(t.s1 - start < TILE_E ? t.s1 - start : TILE_E);
+    static_assert(!ISSUE || (REC_IN && MAP == MAP_LINEAR && !SPILL), "loads first: the records of level A under the linear map");
+    TL_DECL(KT, rk, TILE_EPT);
+    TL_DECL(idx_t, rs, TILE_EPT);
+    if (ISSUE) {
+        // No branch around a load: a lane at or beyond cnt reads the tile's last element again and never uses it.  (Under
+        // `if (e < cnt)` a wave can skip a load, so the compiler must wait for ALL loads before the first element is used: the
+        // count of the loads behind the one it needs is not known.  Unguarded, the waits are for one load each, in turn.)
+        if (cnt == 0) return;                                            // (no tile is empty; the index below needs an element)
+        PAR(tid) {
+            UNROLL
+            for (uint32_t k = 0; k < TILE_EPT; ++k) {
+                const uint32_t e = tid + k * TILE_NT;
+                load_elem<REC_IN, true>(in_key, in_sa, start + (e < cnt ? e : cnt - 1), TL(rk, tid, k), TL(rs, tid, k));
+            }
+        }
+        ISSUE_FENCE();                                                   // ... ahead of the trip for the bucket map
+    }
     const BucketParams bp = bps[g];
     const uint64_t b0 = bstart[g];
     const bool grouped = GROUPED && bp.B > 1 && bp.B <= BUCKET_LDS;      // GROUPED: a build of its own, the plain scatter is hot
@@ -3089,8 +3119,6 @@ GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const ui
     SHARED_ARRAY(uint32_t, lr_b, SPILL ? SPILL_LONG_CAP : 1);
     SHARED_ARRAY(uint32_t, nlong, 2);     // [1]: entries of the tile's own chunk taken so far
     static_assert(!SPILL || (MAP == MAP_SPLIT && sizeof(KT) == 8), "the spill stream: splits by knots, 64-bit keys");
-    TL_DECL(KT, rk, TILE_EPT);
-    TL_DECL(idx_t, rs, TILE_EPT);
     TL_DECL(uint32_t, rb, TILE_EPT);      // bucket
     TL_DECL(idx_t, rr, TILE_EPT);         // rank inside (tile, bucket) or inside the bucket (idx_t: a bucket of a
                                           // degenerate text can hold more than 2^32 suffixes at 64-bit indices)
@@ -3114,6 +3142,47 @@ GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const ui
     const uint32_t n_split = MAP == MAP_SPLIT && bp.B > 1 ? bp.B - 1 : 0u;
     const uint64_t* tab = MAP == MAP_SPLIT ? split + (uint64_t)(g / in_sub) * split_stride : nullptr;
     RUNS_TILE_SETUP
+    if (ISSUE) {
+        if (!lds) {
+            // one bucket, or too many for the LDS histogram: the route at the end of the plain build's classification, whole and on
+            // its own here -- its global atomics and its exit stay out of the control flow of the route below
+            PAR(tid) {
+                UNROLL
+                for (uint32_t k = 0; k < TILE_EPT; ++k) {
+                    const uint32_t e = tid + k * TILE_NT;
+                    if (e < cnt) {
+                        const uint64_t bi = (b0 + (bp.B == 1 ? 0u : bucket_of(bp, (uint64_t)TL(rk, tid, k)))) * (spec ? sub : 1u) + sx;
+                        const uint64_t off = bp.B == 1 ? (start - t.s0) + e : (uint64_t)caps_fetch_add(&cursor[bi], (idx_t)1);
+                        if (!spec || off < slot_cap) {
+                            const uint64_t dst = (spec ? bi * slot_cap : sub_start[bi]) + off;
+                            out_key[dst] = TL(rk, tid, k);
+                            out_sa[dst] = TL(rs, tid, k);
+                        }
+                    }
+                }
+                if (spec && bp.B == 1 && tid == 0) caps_fetch_add(&cursor[b0 * sub + sx], (idx_t)cnt);
+            }
+            DRAIN_GLOBAL();              // (the compiler joins this route's exit with the route below: nothing of it pending there)
+            return;
+        }
+        PAR(tid) {
+            for (uint32_t i = tid; i <= TILE_BINS; i += K_BLOCK_DIM) hist[i] = 0;
+        }
+        // only LDS is handed over here (the zeroed histogram): a barrier of LDS scope, the loads above stay in flight across it
+        SYNC_LDS();
+        PAR(tid) {
+            UNROLL
+            for (uint32_t k = 0; k < TILE_EPT; ++k) {
+                const uint32_t e = tid + k * TILE_NT;
+                if (e < cnt) {
+                    const uint32_t bk = bucket_of(bp, (uint64_t)TL(rk, tid, k));
+                    TL(rb, tid, k) = bk;
+                    TL(rr, tid, k) = FETCH_ADD_U32(&hist[bk], 1u);
+                }
+            }
+        }
+        DRAIN_GLOBAL();                  // every load has been waited for where it was used (or is a wave's unused one): said for all lanes
+    } else {
     if (lds || FROM_TEXT || FROM_RUNS) {
         PAR(tid) {
             if (lds) for (uint32_t i = tid; i <= TILE_BINS; i += K_BLOCK_DIM) hist[i] = 0;
@@ -3241,6 +3310,7 @@ GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const ui
         }
         return;
     }
+    }
     SYNC();
     // One global cursor bump per (tile, non-empty bucket).  The returning atomics are only ISSUED here; their results are
     // needed for the output addresses alone, so they travel while the tile is scanned and re-ordered in LDS (barriers of
@@ -3312,7 +3382,8 @@ GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const ui
             }
         }
     }
-    SYNC_LDS();
+    if (ISSUE) DRAIN_GLOBAL();           // the cursor bumps, once for every thread (see ISSUE at the head of the kernel): a thread
+    SYNC_LDS();                          //   that bumped has waited for its own above, the others had none to wait for
     PAR(tid) {
         UNROLL
         for (uint32_t k = 0; k < TILE_EPT; ++k) {

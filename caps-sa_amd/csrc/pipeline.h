@@ -80,6 +80,11 @@ constexpr uint32_t DIRECT_RECORDS_DEFAULT = 1;
 // Which stages of the shortened start of a tile the final sort of the direct path uses when CAPS_SA_TILE_CHAIN does not say: bit 0 =
 // tile_sort_kernel's bucket-indexed launch.
 constexpr uint32_t DIRECT_TILE_CHAIN_DEFAULT = 1;
+// Which of the scatter kernels of the direct path issue a tile's memory traffic together when CAPS_SA_SCATTER_ISSUE does not say
+// (kernels.h ISSUE): bit 0 = level B (bucket_scatter_kernel on records under the linear map); 0 = the plain builds.  Bit 1 was
+// level A (group_scatter_kernel's tables staged together): measured slower and not built (DESIGN 5.3,
+// docs/r08_level_a_staging.patch); the bit is read and ignored.  Linear mode with 32-bit indices, records and one wave only.
+constexpr uint32_t DIRECT_SCATTER_ISSUE_DEFAULT = 1;
 // Quantile mode of the direct path (skewed keys): mean bucket size (sampling noise on top: sigma = 1 / sqrt(QUANTILE_SPB)) and
 // samples drawn per bucket.
 #ifndef CAPS_BUCKET_Q_32NDS
@@ -506,6 +511,8 @@ struct SortOpts {
     uint32_t tile_chain = 0;            // stages of the shortened start of a tile (run_direct, CAPS_SA_TILE_CHAIN; 0 = the table launch):
                                         //   bit 0 = tile_sort_kernel's bucket-indexed build where the sort qualifies (see its launch below)
     uint32_t* tile_chain_used = nullptr;   // host word: the stages the sort's tile_sort_kernel launch really ran with
+    uint32_t scatter_issue = 0;         // bit 0: the scatter of records under the linear map runs bucket_scatter_kernel's ISSUE build
+    uint32_t* scatter_issue_used = nullptr;   // host word: bit 0 is set when such a launch was made
     KernelClock* tile_clock = nullptr;
     KernelClock* merge_clock = nullptr;
     KernelClock* scatter_clock = nullptr;
@@ -607,7 +614,13 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
                 if constexpr (sizeof(idx_t) == 4) {
                     if (by_knots) CAPS_SCATTER_LAUNCH_REC(MAP_SPLIT);
                     else if (grouped) CAPS_SCATTER_LAUNCH_REC(MAP_GROUPED);
-                    else CAPS_SCATTER_LAUNCH_REC(MAP_LINEAR);
+                    else if (o.scatter_issue & 1u) {
+                        CAPS_LAUNCH((bucket_scatter_kernel<idx_t, BITS, SRC_ARRAYS, MAP_LINEAR, uint64_t, false, true, true>), n_tiles, TILE_NT, be, psd,
+                                    P, n_words, tbase, src_key, src_sa, rsrc, (const BucketParams*)bk.params, (const uint64_t*)bk.bstart, sub_start,
+                                    (uint64_t)cap, static_cast<idx_t*>(bk.cursor), okey, osa, fbps, gfirst, o.knots, (const uint16_t*)nullptr,
+                                    (const uint32_t*)nullptr, 1u, o.knots_per_parent, o.sub, (const uint16_t*)bid, Spill<idx_t>());
+                        if (o.scatter_issue_used) *o.scatter_issue_used |= 1u;
+                    } else CAPS_SCATTER_LAUNCH_REC(MAP_LINEAR);
                 }
             } else
             if (from_text) { if (grouped) CAPS_SCATTER_LAUNCH(SRC_TEXT, MAP_GROUPED, nokey, nosa); else CAPS_SCATTER_LAUNCH(SRC_TEXT, MAP_LINEAR, nokey, nosa); }
@@ -1500,7 +1513,7 @@ private:
     uint32_t passes1_ = 0, passes2_ = 0, passesS_ = 0;
     BackendEvent e2_, e3_, e4_, e5_, e6_, e7_, la0_, la1_;
     uint64_t max_part_ = 0;
-    uint32_t path_direct_ = 0, path_fallback_ = 0, direct_groups_ = 0, direct_quantile_ = 0, direct_k32_ = 0, direct_records_ = 0, tile_chain_ = 0, run_buckets_ = 0;
+    uint32_t path_direct_ = 0, path_fallback_ = 0, direct_groups_ = 0, direct_quantile_ = 0, direct_k32_ = 0, direct_records_ = 0, tile_chain_ = 0, scatter_issue_ = 0, run_buckets_ = 0;
     uint64_t direct_max_group_ = 0;
     uint64_t tie_groups_ = 0, tie_elems_ = 0;
     uint32_t tie_levels_ = 0;
@@ -1828,6 +1841,13 @@ private:
         const char* chain_env = std::getenv("CAPS_SA_TILE_CHAIN");
         const uint32_t chain_want = chain_env ? (uint32_t)std::atoi(chain_env) : DIRECT_TILE_CHAIN_DEFAULT;
         tile_chain_ = 0;
+        // The scatters that issue a tile's memory traffic together (kernels.h ISSUE; CAPS_SA_SCATTER_ISSUE, a mask read here, once
+        // per build: bit 0 = level B, 0 = the plain builds; bit 1, level A, is not built).  Linear mode on records, results in one
+        // wave; what the build really launched: scatter_issue_.
+        const char* issue_env = std::getenv("CAPS_SA_SCATTER_ISSUE");
+        const bool may_wave = !(k32 || waves_ < 2 || !wave_scratch_.key);
+        const uint32_t issue_want = rec_a && !quantile && !may_wave ? (issue_env ? (uint32_t)std::atoi(issue_env) : DIRECT_SCATTER_ISSUE_DEFAULT) & 1u : 0u;
+        scatter_issue_ = 0;
         if (k32) CAPS_LAUNCH(group_shift_kernel, (K1 + 255) / 256, 256, be_, (const uint64_t*)pl_.gkey, K1, pl_.gshift);
         if (quantile) {
             // more samples, sorted in the (still idle) big buffers; their quantiles are the bucket boundaries and, every KPG-th, the group keys
@@ -1927,6 +1947,25 @@ private:
         direct_max_group_ = dstat[1] ? dstat[1] : out2[1];
         if (dstat[1] != 0 || dstat[0] != n) { path_fallback_ = CAPS_SA_FB_GROUP_OVERFLOW; return false; }
         max_part_ = out2[1];
+        if (std::getenv("CAPS_SA_DEBUG")) {
+            // the tiles level B will see: every stream is cut into tiles of TILE_E, its last tile ends inside the k-th of the TILE_EPT
+            // loads of a thread (or is full).  THE WORDING IS AN INTERFACE: tests/scatter_issue_cases.py parses this line.
+            std::vector<idx_t> sz(n_streams);
+            be_.d2h(sz.data(), pl_.dcur, (size_t)n_streams * sizeof(idx_t));
+            be_.sync();
+            uint64_t full = 0, used = 0, tail[TILE_EPT + 1] = {};
+            for (uint32_t s = 0; s < n_streams; ++s) {
+                const uint64_t z = (uint64_t)sz[s];
+                if (!z) continue;
+                ++used;
+                full += z / TILE_E;
+                if (z % TILE_E) ++tail[(z % TILE_E - 1) / TILE_NT];
+            }
+            std::fprintf(stderr, "[direct] level B input: %llu streams, %llu full tiles, last tiles that end in load", (unsigned long long)used,
+                         (unsigned long long)full);
+            for (uint32_t k = 0; k < TILE_EPT; ++k) std::fprintf(stderr, " %u: %llu", k + 1, (unsigned long long)tail[k]);
+            std::fprintf(stderr, " (tiles of %u, %u threads)\n", TILE_E, TILE_NT);
+        }
         e2_ = e1;                                     // no sort_subarrays, no locate_pivots
         e4_ = e3_;
         e5_ = be_.record();
@@ -2010,6 +2049,8 @@ private:
             }
             set_final(ow, dSA + base, dLCP + base);
             if (W == 1) { ow.tile_chain = chain_want; ow.tile_chain_used = &tile_chain_; }       // (one sort: the last word stands)
+            ow.scatter_issue = issue_want;
+            ow.scatter_issue_used = &scatter_issue_;
             if (elems_w) {
                 SortResult<idx_t> r2 = seg_sort<BITS>(gw, n_tiles_w, max_len_w, W > 1 ? wave_scratch_ : pl_.A, pl_.B, elems_w, ow, true);
                 if (r2.failed) {                                                                // a slot overflowed under 32-bit keys: again with 64
@@ -2127,6 +2168,7 @@ private:
             st->direct_key_bits = path_direct_ && direct_k32_ ? 32u : 64u;
             st->direct_records = path_direct_ ? direct_records_ : 0u;
             st->tile_chain = path_direct_ ? tile_chain_ : 0u;
+            st->scatter_issue = path_direct_ ? scatter_issue_ : 0u;
             st->direct_max_group = direct_max_group_;
             st->level_a_ms = direct_groups_ ? be_.elapsed_ms(la0_, la1_) : 0.0;
             st->slot_splits = slot_stats_[0];

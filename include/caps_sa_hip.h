@@ -114,6 +114,11 @@ typedef struct caps_sa_stats {
      * variable CAPS_SA_TILE_CHAIN chooses, 0 = the launch over the tile table; always 0 in quantile mode, with 64-bit indices, with
      * 32-bit keys, when a slot overflowed and the split was redone, for a build that leaves in waves, and off the direct path */
     uint32_t tile_chain;
+    /* direct path: which scatter kernels issued a tile's memory traffic together (csrc/kernels.h ISSUE) -- a mask, bit 0 = level B
+     * (all loads of a tile ahead of its bucket map, the emit's stores back to back; the only stage built so, the other bits are 0).
+     * The environment variable CAPS_SA_SCATTER_ISSUE chooses, 0 = the plain kernels; always 0 in quantile mode, with
+     * 64-bit indices, with 32-bit keys, without records, for a build that leaves in waves, and off the direct path */
+    uint32_t scatter_issue;
 } caps_sa_stats;
 
 /* sizeof(caps_sa_stats) / sizeof(caps_sa_shard_info) of THIS library.  Both structs grow at their end from release to release and
