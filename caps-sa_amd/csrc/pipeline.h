@@ -1255,9 +1255,30 @@ bool msd_refine(Backend& be, const uint32_t* P, uint64_t n, const SortResult<idx
         if (n_edges) CAPS_LAUNCH((msd_fix_edges_kernel<idx_t, BITS>), (uint32_t)((n_edges + 255) / 256), 256, be, P, n, (const uint64_t*)edges, n_edges,
                                  r.total, (const idx_t*)SA, LCP);
     };
+    // The tests read the two "[msd]" lines of a generation -- which routes a text's groups really took -- through the patterns
+    // _LEVEL and _SIZES of tests/deferred_tie_cases.py: change wording and patterns together.
+    // (dbg: the member counts of a generation's groups, "size x groups" in ascending order, and the depths its groups stand at)
+    auto log_sizes = [&](uint32_t level, const uint64_t* seg_d, const uint64_t* gdep_d, uint64_t G_, const uint64_t* nq) {
+        std::vector<uint64_t> ss((size_t)G_ + 1), dd((size_t)G_);
+        be.d2h(ss.data(), seg_d, ss.size() * sizeof(uint64_t));
+        if (G_) be.d2h(dd.data(), gdep_d, dd.size() * sizeof(uint64_t));
+        be.sync();
+        for (size_t g = 0; g < (size_t)G_; ++g) ss[g] = ss[g + 1] - ss[g];
+        ss.pop_back();
+        std::sort(ss.begin(), ss.end());
+        std::sort(dd.begin(), dd.end());
+        std::fprintf(stderr, "[msd] generation %u: quick classes %llu %llu %llu, depths %llu to %llu, sizes", level, (unsigned long long)nq[0], (unsigned long long)nq[1],
+                     (unsigned long long)nq[2], (unsigned long long)(G_ ? dd.front() : 0), (unsigned long long)(G_ ? dd.back() : 0));
+        for (size_t a = 0, b; a < ss.size(); a = b) {
+            for (b = a; b < ss.size() && ss[b] == ss[a]; ++b) {}
+            std::fprintf(stderr, " %llux%llu", (unsigned long long)ss[a], (unsigned long long)(b - a));
+        }
+        std::fprintf(stderr, "\n");
+    };
     if (dbg) std::fprintf(stderr, "[msd] level 0: %llu flagged tiles, %llu elements in them, %llu groups of %llu members, %llu above %u finished in LDS, %llu above %u (largest %llu)\n",
                           (unsigned long long)NF, (unsigned long long)M0, (unsigned long long)G, (unsigned long long)m, (unsigned long long)(h3[6] + h3[7] + h3[8]), MSD_FIN_MAX,
                           (unsigned long long)nopen, MSD_QK_MAX, (unsigned long long)gmax);
+    if (dbg) log_sizes(0, segX, gdepX, G, h3 + 6);
     if (nopen == 0) { fix_edges(); return true; }
     // ---- the levels: work arrays for m members in at most m / 2 groups; level 0's outputs stay where they are (chunk tails)
     ar.lo[0] = reinterpret_cast<char*>(r.buf[0].key);                   // (flags0 / offs0 / stmp are dead)
@@ -1350,6 +1371,7 @@ bool msd_refine(Backend& be, const uint32_t* P, uint64_t n, const SortResult<idx
         if (dbg) std::fprintf(stderr, "[msd] depth %llu: %llu groups of %llu members, %llu above %u finished in LDS, %llu above %u (largest %llu)\n", (unsigned long long)D,
                               (unsigned long long)G, (unsigned long long)m, (unsigned long long)(h3[6] + h3[7] + h3[8]), MSD_FIN_MAX, (unsigned long long)nopen,
                               MSD_QK_MAX, (unsigned long long)gmax);
+        if (dbg && G <= Gm - 1) log_sizes(r.msd_levels, seg, gdep, G, h3 + 6);
         if (G > Gm - 1 || m > cap2 - 2) return false;                   // (cannot happen: both only shrink)
     }
     fix_edges();
