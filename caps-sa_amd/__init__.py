@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from ._binding import CapsLib, CapsSaError, Stats, Shard, ShardInfo, EXPORTS, MEM_DTYPE, KMER_DTYPE, LZ_DTYPE, LZ_LITERAL, CROSS_DTYPE, CROSS_MAX_OCC  # noqa: F401
+from ._binding import CapsLib, CapsSaError, Stats, Shard, ShardInfo, EXPORTS, MEM_DTYPE, KMER_DTYPE, LZ_DTYPE, LZ_LITERAL, CROSS_DTYPE, CROSS_MAX_OCC, COLL_DTYPE, COLL_MAX_DOCS  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CAPS_SA_LIB selects a tuning variant built by `make variant` (benchmarking only).
@@ -68,6 +68,30 @@ def kmer_census(SA, LCP, max_k: int, device: int = 0, _lib: CapsLib | None = Non
     """(distinct, unique), np.uint64[max_k + 1] each: for every k in 1 .. max_k the number of distinct k-mers and of those that
     occur once, from one pass."""
     return (_lib or lib()).kmer_census(SA, LCP, max_k, device=device)
+
+
+def collection_kmers(SA, LCP, k: int, docs, min_docs: int = 1, max_docs: int = 0, all_of: int = 0, none_of: int = 0, device: int = 0,
+                     _lib: CapsLib | None = None) -> np.ndarray:
+    """The k-mers of a collection of sequences inside one text (include/caps_sa_hip.h "k-mers across a collection"): ``docs`` is a
+    sequence of up to 64 ascending, disjoint ``(start, length)``.  A structured array (COLL_DTYPE: first, count, occ, docs) in the
+    library's byte order of the k-mers that occur inside a document and whose set of documents -- the bit mask ``docs`` -- has
+    min_docs .. max_docs members (max_docs = 0: no upper bound), all of ``all_of`` and none of ``none_of``.  ``min_docs=m`` gives the
+    core k-mers, ``max_docs=1`` the private ones."""
+    return (_lib or lib()).coll_kmers(SA, LCP, k, docs, min_docs, max_docs, all_of, none_of, device=device)
+
+
+def kmer_sharing(SA, LCP, k: int, docs, device: int = 0, _lib: CapsLib | None = None):
+    """(freq, shared) over every k-mer of the collection: freq (np.uint64[65]) counts the k-mers by the number of documents that hold
+    them, shared (np.uint64[m, m]) those that documents a and b both hold; the diagonal is a document's number of distinct k-mers."""
+    return (_lib or lib()).coll_sharing(SA, LCP, k, docs, device=device)
+
+
+def jaccard_from_shared(shared) -> np.ndarray:
+    """Jaccard(a, b) = S_ab / (S_aa + S_bb - S_ab) as a float matrix, 0 where both documents have no k-mer."""
+    s = np.asarray(shared, dtype=np.float64)
+    d = np.diag(s)
+    union = d[:, None] + d[None, :] - s
+    return np.divide(s, union, out=np.zeros_like(s), where=union > 0)
 
 
 def lpf(SA, LCP, device: int = 0, _lib: CapsLib | None = None):
@@ -203,6 +227,21 @@ class SuffixArray:
         """(distinct, unique), np.uint64[max_k + 1] each: the number of distinct k-mers and of those that occur once, k = 1 .. max_k."""
         SA, LCP = self._kmer_arrays()
         return lib().kmer_census(SA, LCP, max_k, self._bits, self._device)
+
+    def collection_kmers(self, k: int, docs, min_docs: int = 1, max_docs: int = 0, all_of: int = 0, none_of: int = 0) -> np.ndarray:
+        """The k-mers of the documents ``docs`` (up to 64 ascending, disjoint ``(start, length)`` in T()) as a structured array
+        (COLL_DTYPE: first, count, occ, docs), filtered by the number of documents and the masks: see ``collection_kmers``."""
+        SA, LCP = self._kmer_arrays("collection k-mers")
+        return lib().coll_kmers(SA, LCP, k, docs, min_docs, max_docs, all_of, none_of, self._bits, self._device)
+
+    def kmer_sharing(self, k: int, docs):
+        """(freq, shared): see ``kmer_sharing``."""
+        SA, LCP = self._kmer_arrays("collection k-mers")
+        return lib().coll_sharing(SA, LCP, k, docs, self._bits, self._device)
+
+    def kmer_jaccard(self, k: int, docs) -> np.ndarray:
+        """The exact k-mer Jaccard index of every pair of documents as a float matrix (0 where both have no k-mer)."""
+        return jaccard_from_shared(self.kmer_sharing(k, docs)[1])
 
     def lpf(self):
         """(LPF, Prev) in text order: LPF[i] = the longest prefix of T()[i:] that also starts at some j < i, Prev[i] = such a j (all

@@ -127,7 +127,7 @@ EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_b
            "inverse_bwt_workspace_bytes", "fm_index_bytes", "fm_from_bwt_workspace_bytes", "fm_count", "fm_locate", "fm_count_device", "fm_locate_device",
            "fm_index_bytes_ex", "fm_add_text_samples", "fm_add_text_samples_device", "fm_extract_workspace_bytes", "fm_extract", "fm_extract_device",
            "fm_match", "fm_match_device", "fm_mems_workspace_bytes", "fm_mems", "fm_mems_device", "fm_wide_index_bytes",
-           "fm_wide_workspace_bytes", "kmer_workspace_bytes", "cross_workspace_bytes", "lpf_workspace_bytes", "lz77_workspace_bytes", "lce_index_bytes",
+           "fm_wide_workspace_bytes", "kmer_workspace_bytes", "cross_workspace_bytes", "coll_workspace_bytes", "lpf_workspace_bytes", "lz77_workspace_bytes", "lce_index_bytes",
            "lce_range_min", "lce_range_min_device", "lce", "lce_device"] + SHARD_EXPORTS + [
     f"{name}_{sfx}"
     for sfx in ("u32", "u64")
@@ -136,7 +136,8 @@ EXPORTS = ["device_count", "last_error", "version", "stats_bytes", "shard_info_b
                  "fm_build_from_bwt", "fm_build_from_bwt_device", "fm_build_wide", "fm_build_wide_device",
                  "kmers", "kmers_device", "kmer_spectrum", "kmer_spectrum_device", "kmer_census", "kmer_census_device",
                  "lpf", "lpf_device", "lz77", "lz77_device", "isa", "isa_device", "lce_build", "lce_build_device",
-                 "cross_mums", "cross_mums_device", "cross_mems", "cross_mems_device")
+                 "cross_mums", "cross_mums_device", "cross_mems", "cross_mems_device",
+                 "coll_kmers", "coll_kmers_device", "coll_sharing", "coll_sharing_device")
 ]
 
 
@@ -149,6 +150,10 @@ KMER_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("pos", "<u8")])
 # a record of cross_mums / cross_mems (include/caps_sa_hip.h "MUMs and MEMs between two texts"): 24 bytes, little-endian
 CROSS_DTYPE = np.dtype([("a", "<u8"), ("b", "<u8"), ("len", "<u8")])
 CROSS_MAX_OCC = 64
+
+# a record of coll_kmers (include/caps_sa_hip.h "k-mers across a collection"): 32 bytes, little-endian
+COLL_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("occ", "<u8"), ("docs", "<u8")])
+COLL_MAX_DOCS = 64
 
 # a phrase of lz77 (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP"): 24 bytes, little-endian; src = LZ_LITERAL: one byte
 LZ_DTYPE = np.dtype([("pos", "<u8"), ("len", "<u8"), ("src", "<u8")])
@@ -239,6 +244,8 @@ class CapsLib:
         f("kmer_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
         f("cross_workspace_bytes").restype = _ci
         f("cross_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
+        f("coll_workspace_bytes").restype = _ci
+        f("coll_workspace_bytes").argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
         for name in ("lpf_workspace_bytes", "lz77_workspace_bytes"):
             f(name).restype = _ci
             f(name).argtypes = [_u64, _ci, ctypes.POINTER(_u64)]
@@ -277,6 +284,15 @@ class CapsLib:
             f(f"cross_mums_device_{sfx}").argtypes = [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp]
             f(f"cross_mems_device_{sfx}").restype = _ci
             f(f"cross_mems_device_{sfx}").argtypes = [_vp, _vp, _vp, _u64, _u64, _u64, ctypes.c_uint32, _vp, _u64, _vp, _vp, _u64, _vp]
+            _docs = [_vp, _vp, ctypes.c_uint32]
+            f(f"coll_kmers_{sfx}").restype = _ci
+            f(f"coll_kmers_{sfx}").argtypes = [_vp, _vp, _u64, _u64] + _docs + [_u64, _u64, _u64, _u64, _vp, _u64, _vp, _ci]
+            f(f"coll_kmers_device_{sfx}").restype = _ci
+            f(f"coll_kmers_device_{sfx}").argtypes = [_vp, _vp, _u64, _u64] + _docs + [_u64, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp]
+            f(f"coll_sharing_{sfx}").restype = _ci
+            f(f"coll_sharing_{sfx}").argtypes = [_vp, _vp, _u64, _u64] + _docs + [_vp, _vp, _ci]
+            f(f"coll_sharing_device_{sfx}").restype = _ci
+            f(f"coll_sharing_device_{sfx}").argtypes = [_vp, _vp, _u64, _u64] + _docs + [_vp, _vp, _vp, _u64, _vp]
             f(f"kmers_{sfx}").restype = _ci
             f(f"kmers_{sfx}").argtypes = [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _u64, ctypes.POINTER(_u64), _ci]
             f(f"kmers_device_{sfx}").restype = _ci
@@ -903,6 +919,71 @@ class CapsLib:
             err.summary = summary
             raise err
         return summary
+
+    # ------------------------------------------------------------------ k-mers across a collection (include/caps_sa_hip.h)
+    def coll_workspace_bytes(self, n: int, idx_bits: int = 32) -> int:
+        out = _u64(0)
+        self._check(self._f("coll_workspace_bytes")(n, idx_bits // 8, ctypes.byref(out)))
+        return out.value
+
+    @staticmethod
+    def coll_docs(docs):
+        """A sequence of (start, length) -> (starts, lengths, m): two np.uint64 arrays for the doc_start / doc_len arguments."""
+        d = np.asarray(list(docs), dtype=np.uint64).reshape(-1, 2)
+        return np.ascontiguousarray(d[:, 0]), np.ascontiguousarray(d[:, 1]), int(d.shape[0])
+
+    def coll_kmers(self, SA, LCP, k: int, docs, min_docs: int = 1, max_docs: int = 0, all_of: int = 0, none_of: int = 0,
+                   idx_bits: int | None = None, device: int = 0) -> np.ndarray:
+        """The collection k-mers that pass the filter as a structured array (COLL_DTYPE: first, count, occ, docs) in the library's byte
+        order; docs: a sequence of (start, length).  The counting call, then the writing call."""
+        SA, LCP, n, sfx = self._sa_lcp(SA, LCP, idx_bits)
+        st, ln, m = self.coll_docs(docs)
+        found = _u64(0)
+        args = (SA.ctypes.data if n else None, LCP.ctypes.data if n else None, n, k, st.ctypes.data, ln.ctypes.data, m, min_docs, max_docs,
+                all_of, none_of)
+        self._check(self._f(f"coll_kmers_{sfx}")(*args, None, 0, ctypes.byref(found), device))
+        rec = np.zeros(found.value, dtype=COLL_DTYPE)
+        if rec.size:
+            self._check(self._f(f"coll_kmers_{sfx}")(*args, rec.ctypes.data, rec.size, ctypes.byref(found), device))
+        return rec
+
+    def coll_sharing(self, SA, LCP, k: int, docs, idx_bits: int | None = None, device: int = 0):
+        """(freq, shared): np.uint64[65] and np.uint64[m, m] -- freq[c] = the collection k-mers in exactly c documents, shared[a, b] =
+        those in both a and b."""
+        SA, LCP, n, sfx = self._sa_lcp(SA, LCP, idx_bits)
+        st, ln, m = self.coll_docs(docs)
+        freq = np.zeros(COLL_MAX_DOCS + 1, dtype=np.uint64)
+        shared = np.zeros((max(m, 1), max(m, 1)), dtype=np.uint64)
+        self._check(self._f(f"coll_sharing_{sfx}")(SA.ctypes.data if n else None, LCP.ctypes.data if n else None, n, k, st.ctypes.data,
+                                                   ln.ctypes.data, m, freq.ctypes.data, shared.ctypes.data, device))
+        return freq, shared
+
+    def coll_kmers_device(self, dSA_ptr: int, dLCP_ptr: int, n: int, k: int, docs, min_docs: int = 1, max_docs: int = 0, all_of: int = 0,
+                          none_of: int = 0, dRecords_ptr: int = 0, capacity: int = 0, dWS_ptr: int = 0, ws_bytes: int = 0, idx_bits: int = 32,
+                          stream: int = 0) -> int:
+        """Device arrays -> the number of records; dRecords_ptr 0: the counting call, else `capacity` 32-byte records may be written
+        there.  More records than capacity: CapsSaError (code -1) whose n_records attribute holds their number."""
+        sfx, _ = _sfx(idx_bits)
+        st, ln, m = self.coll_docs(docs)
+        found = _u64(0)
+        rc = self._f(f"coll_kmers_device_{sfx}")(dSA_ptr or None, dLCP_ptr or None, n, k, st.ctypes.data, ln.ctypes.data, m, min_docs, max_docs,
+                                                 all_of, none_of, dRecords_ptr or None, capacity, ctypes.byref(found), dWS_ptr or None, ws_bytes,
+                                                 stream or None)
+        if rc != 0:
+            err = CapsSaError(rc, self._f("last_error")().decode(errors="replace"))
+            err.n_records = found.value
+            raise err
+        return found.value
+
+    def coll_sharing_device(self, dSA_ptr: int, dLCP_ptr: int, n: int, k: int, docs, dWS_ptr: int = 0, ws_bytes: int = 0, idx_bits: int = 32,
+                            stream: int = 0):
+        sfx, _ = _sfx(idx_bits)
+        st, ln, m = self.coll_docs(docs)
+        freq = np.zeros(COLL_MAX_DOCS + 1, dtype=np.uint64)
+        shared = np.zeros((max(m, 1), max(m, 1)), dtype=np.uint64)
+        self._check(self._f(f"coll_sharing_device_{sfx}")(dSA_ptr or None, dLCP_ptr or None, n, k, st.ctypes.data, ln.ctypes.data, m,
+                                                          freq.ctypes.data, shared.ctypes.data, dWS_ptr or None, ws_bytes, stream or None))
+        return freq, shared
 
     # ------------------------------------------------------------------ LPF and LZ77 (include/caps_sa_hip.h "LPF and LZ77 from SA and LCP")
     def lpf_workspace_bytes(self, n: int, idx_bits: int = 32) -> int:

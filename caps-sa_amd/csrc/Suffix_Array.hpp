@@ -27,6 +27,8 @@
 //  * cross_mums() / cross_mems() / longest_common_substring() (not in the reference): the maximal unique matches, the rare maximal exact
 //    matches and the longest common substring between T()[0 .. split) and T()[split .. n), from SA(), LCP() and the BWT after a
 //    full-context construct() / construct_bwt() (include/caps_sa_hip.h "MUMs and MEMs between two texts").
+//  * collection_kmers() / kmer_sharing() (not in the reference): the k-mers of up to 64 documents inside T() with the set of documents
+//    that hold each, and how many every pair of documents shares (include/caps_sa_hip.h "k-mers across a collection").
 //  * the free function inverse_bwt() (not in the reference): the text back from (BWT, primary).
 //  * the class FM_Index (not in the reference either): count, locate, matching statistics, MEMs and extract over (BWT, primary) and a sample of the SA.
 #ifndef CAPS_SA_AMD_SUFFIX_ARRAY_HPP
@@ -174,6 +176,46 @@ public:
             ? caps_sa_hip_kmer_census_u32(reinterpret_cast<const uint32_t*>(SA_), reinterpret_cast<const uint32_t*>(LCP_), n_, max_k, distinct.data(), unique.data(), devices_[0])
             : caps_sa_hip_kmer_census_u64(reinterpret_cast<const uint64_t*>(SA_), reinterpret_cast<const uint64_t*>(LCP_), n_, max_k, distinct.data(), unique.data(), devices_[0]);
         if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_kmer_census: ") + caps_sa_hip_last_error());
+    }
+
+    // ---- k-mers across a collection (include/caps_sa_hip.h; not in the reference).  docs: up to 64 ascending, disjoint (start, length)
+    // in T().  After a full-context construct() / construct_bwt(); with max_context set these throw std::invalid_argument.  On devices()[0].
+    struct Coll_Kmer { uint64_t first, count, occ, docs; };    // the ABI's 32-byte record: T()[SA()[first] .. + k), in the documents of the mask `docs`
+    typedef std::vector<std::pair<uint64_t, uint64_t>> Documents;
+    // the k-mers inside a document whose set of documents has min_docs .. max_docs members (0: no upper bound), all of all_of, none of none_of
+    std::vector<Coll_Kmer> collection_kmers(uint64_t k, const Documents& docs, uint64_t min_docs = 1, uint64_t max_docs = 0, uint64_t all_of = 0,
+                                            uint64_t none_of = 0) const
+    {
+        kmer_arrays_ok("collection_kmers");
+        static_assert(sizeof(Coll_Kmer) == 32, "the ABI's record");
+        std::vector<uint64_t> st, ln;
+        for (const auto& d : docs) { st.push_back(d.first); ln.push_back(d.second); }
+        const uint32_t m = static_cast<uint32_t>(docs.size());
+        auto call = [&](void* records, uint64_t capacity, uint64_t* found) {
+            const int rc = std::is_same<idx_t, uint32_t>::value
+                ? caps_sa_hip_coll_kmers_u32(reinterpret_cast<const uint32_t*>(SA_), reinterpret_cast<const uint32_t*>(LCP_), n_, k, st.data(), ln.data(), m, min_docs, max_docs, all_of, none_of, records, capacity, found, devices_[0])
+                : caps_sa_hip_coll_kmers_u64(reinterpret_cast<const uint64_t*>(SA_), reinterpret_cast<const uint64_t*>(LCP_), n_, k, st.data(), ln.data(), m, min_docs, max_docs, all_of, none_of, records, capacity, found, devices_[0]);
+            if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_coll_kmers: ") + caps_sa_hip_last_error());
+        };
+        uint64_t found = 0;
+        call(nullptr, 0, &found);                                                // the counting call
+        std::vector<Coll_Kmer> out(static_cast<std::size_t>(found));
+        if (found) call(out.data(), found, &found);
+        return out;
+    }
+    // freq[c], c = 0 .. 64: the k-mers of the collection in exactly c documents; shared[a * m + b]: those in both a and b
+    void kmer_sharing(uint64_t k, const Documents& docs, std::vector<uint64_t>& freq, std::vector<uint64_t>& shared) const
+    {
+        kmer_arrays_ok("kmer_sharing");
+        std::vector<uint64_t> st, ln;
+        for (const auto& d : docs) { st.push_back(d.first); ln.push_back(d.second); }
+        const uint32_t m = static_cast<uint32_t>(docs.size());
+        freq.assign(65, 0);
+        shared.assign(static_cast<std::size_t>(m) * m, 0);
+        const int rc = std::is_same<idx_t, uint32_t>::value
+            ? caps_sa_hip_coll_sharing_u32(reinterpret_cast<const uint32_t*>(SA_), reinterpret_cast<const uint32_t*>(LCP_), n_, k, st.data(), ln.data(), m, freq.data(), shared.data(), devices_[0])
+            : caps_sa_hip_coll_sharing_u64(reinterpret_cast<const uint64_t*>(SA_), reinterpret_cast<const uint64_t*>(LCP_), n_, k, st.data(), ln.data(), m, freq.data(), shared.data(), devices_[0]);
+        if (rc != CAPS_SA_OK) throw std::runtime_error(std::string("caps_sa_hip_coll_sharing: ") + caps_sa_hip_last_error());
     }
 
     // ---- LPF and LZ77 from SA and LCP (include/caps_sa_hip.h; not in the reference).  After a full-context construct() / construct_bwt():

@@ -2954,6 +2954,249 @@ int kmer_census_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint32_t max
     });
 }
 
+// ---- k-mers across a collection (include/caps_sa_hip.h "k-mers across a collection"; kernels.h ck_*) -----------------------------------
+// Workspace: next[n_tiles + 1] | cnt[n_tiles + 1] | front docs, front occ, carry docs, carry occ [n_tiles] each | the document table[128] |
+// totals[CK_COLS] | per-workgroup rows[grid][CK_COLS], 64-bit words.
+struct CollPlan {
+    uint64_t n_tiles = 0;
+    uint32_t grid = 1;                         // workgroups of the sharing kernel (= the length of a column)
+    size_t off_next = 0, off_cnt = 0, off_pd = 0, off_po = 0, off_cd = 0, off_co = 0, off_tab = 0, off_tot = 0, off_hist = 0, bytes = 0;
+};
+inline CollPlan coll_plan(uint64_t n)
+{
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    CollPlan p;
+    p.n_tiles = (n + KMER_TILE - 1) / KMER_TILE;
+    p.grid = capped_grid(std::min<uint64_t>(p.n_tiles, 1024), FM_NT);     // (the kernel flushes its 32-bit counters itself)
+    const size_t col = up((p.n_tiles + 1) * 8);
+    p.off_next = 0;
+    p.off_cnt = p.off_next + col;
+    p.off_pd = p.off_cnt + col;
+    p.off_po = p.off_pd + col;
+    p.off_cd = p.off_po + col;
+    p.off_co = p.off_cd + col;
+    p.off_tab = p.off_co + col;
+    p.off_tot = p.off_tab + up(2 * CK_MAX_DOCS * 8);
+    p.off_hist = p.off_tot + up((size_t)CK_COLS * 8);
+    p.bytes = p.off_hist + up((size_t)CK_COLS * p.grid * 8);
+    return p;
+}
+inline int coll_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
+{
+    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
+    *bytes = coll_plan(n).bytes + 256;
+    return CAPS_SA_OK;
+}
+struct CollWs {
+    char* base = nullptr;
+    CollPlan p;
+    uint64_t* at(size_t off) const { return reinterpret_cast<uint64_t*>(base + off); }
+};
+inline CollWs coll_ws(DevAllocs& da, void* workspace, uint64_t workspace_bytes, uint64_t n)
+{
+    CollWs w;
+    w.p = coll_plan(n);
+    uint64_t usable = 0;
+    if (workspace) w.base = kmer_align_ws(workspace, workspace_bytes, usable);
+    else w.base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(da.get<char>(w.p.bytes + 256)) + 255) & ~uintptr_t(255));
+    return w;
+}
+struct CollDocs { const uint64_t* start; const uint64_t* len; uint32_t m; };
+
+// everything but the outputs: the arrays, k, the documents, the workspace
+template <typename idx_t>
+int coll_check(const void* SA, const void* LCP, uint64_t n, uint64_t k, const CollDocs& dc, void* workspace, uint64_t workspace_bytes)
+{
+    if (int rc = kmer_check_arrays<idx_t>(SA, LCP, n)) return rc;
+    if (k == 0) return fail(CAPS_SA_EINVAL, "k must be at least 1");
+    if (dc.m < 1 || dc.m > CK_MAX_DOCS) return fail(CAPS_SA_EINVAL, "m must be in 1 .. 64");
+    if (!dc.start || !dc.len) return fail(CAPS_SA_EINVAL, "null pointer");
+    uint64_t prev_end = 0;
+    for (uint32_t d = 0; d < dc.m; ++d) {
+        if (dc.len[d] > n || dc.start[d] > n - dc.len[d]) return fail(CAPS_SA_EINVAL, "a document passes the end of the text");
+        if (dc.start[d] < prev_end) return fail(CAPS_SA_EINVAL, "the documents must be ascending and disjoint");
+        prev_end = dc.start[d] + dc.len[d];
+    }
+    if (workspace) {
+        uint64_t usable = 0;
+        kmer_align_ws(workspace, workspace_bytes, usable);
+        if (usable < coll_plan(n).bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_coll_workspace_bytes)");
+    }
+    return CAPS_SA_OK;
+}
+inline int coll_check_filter(const CollDocs& dc, const CkFilter& q)
+{
+    if (q.max_docs && q.min_docs > q.max_docs) return fail(CAPS_SA_EINVAL, "min_docs > max_docs");
+    if (q.all_of & q.none_of) return fail(CAPS_SA_EINVAL, "all_of and none_of share a document");
+    if (dc.m < 64 && ((q.all_of | q.none_of) >> dc.m)) return fail(CAPS_SA_EINVAL, "a mask names a document at or above m");
+    return CAPS_SA_OK;
+}
+
+// the table up, then front parts, carries and next[] (1 <= k <= n); `tab` must live until the stream has been synchronised
+struct CollTable { uint64_t v[2 * CK_MAX_DOCS]; uint32_t top = 1; };
+template <typename idx_t>
+void run_coll_edges(Backend& be, const idx_t* dSA, const idx_t* dLCP, uint64_t n, uint64_t k, const CollDocs& dc, CollTable& tab, const CollWs& w)
+{
+    for (uint32_t d = 0; d < CK_MAX_DOCS; ++d) {
+        tab.v[d] = d < dc.m ? dc.start[d] : ~0ull;
+        tab.v[CK_MAX_DOCS + d] = d < dc.m ? dc.start[d] + dc.len[d] : 0;
+    }
+    tab.top = 1;
+    while (tab.top < dc.m) tab.top <<= 1;
+    be.h2d(w.at(w.p.off_tab), tab.v, sizeof(tab.v));
+    const uint32_t tg = capped_grid(std::min<uint64_t>(w.p.n_tiles, 1u << 20), FM_NT);
+    CAPS_LAUNCH((ck_edge_kernel<idx_t>), tg, FM_NT, be, dSA, dLCP, n, k, w.p.n_tiles, (const uint64_t*)w.at(w.p.off_tab), tab.top, w.at(w.p.off_next),
+                w.at(w.p.off_pd), w.at(w.p.off_po));
+    CAPS_LAUNCH(ck_close_kernel, 1, FM_NT, be, (const uint64_t*)w.at(w.p.off_next), (const uint64_t*)w.at(w.p.off_pd),
+                (const uint64_t*)w.at(w.p.off_po), w.at(w.p.off_cd), w.at(w.p.off_co), w.p.n_tiles, n);
+    CAPS_LAUNCH(kmer_next_kernel, 1, FM_NT, be, w.at(w.p.off_next), w.p.n_tiles, n);
+}
+template <typename idx_t, int MODE>
+void launch_coll_run(Backend& be, uint32_t grid, const idx_t* dSA, const idx_t* dLCP, uint64_t n, uint64_t k, const CollDocs& dc, const CollTable& tab,
+                     const CkFilter& q, uint64_t* dRec, uint64_t cap, const CollWs& w)
+{
+    CAPS_LAUNCH((ck_run_kernel<idx_t, MODE>), grid, FM_NT, be, dSA, dLCP, n, k, w.p.n_tiles, (const uint64_t*)w.at(w.p.off_tab), tab.top, dc.m,
+                (const uint64_t*)w.at(w.p.off_next), (const uint64_t*)w.at(w.p.off_cd), (const uint64_t*)w.at(w.p.off_co), q, w.at(w.p.off_cnt),
+                dRec, cap, w.at(w.p.off_hist));
+}
+
+// the counting call: cnt[] scanned, *found down (1 <= k <= n)
+template <typename idx_t>
+void run_coll_count(Backend& be, const idx_t* dSA, const idx_t* dLCP, uint64_t n, uint64_t k, const CollDocs& dc, CollTable& tab, const CkFilter& q,
+                    uint64_t* found, const CollWs& w)
+{
+    run_coll_edges<idx_t>(be, dSA, dLCP, n, k, dc, tab, w);
+    const uint32_t tg = capped_grid(std::min<uint64_t>(w.p.n_tiles, 1u << 20), FM_NT);
+    launch_coll_run<idx_t, CK_COUNT>(be, tg, dSA, dLCP, n, k, dc, tab, q, nullptr, 0, w);
+    CAPS_LAUNCH(fm_scan_kernel, 1, FM_NT, be, w.at(w.p.off_cnt), w.p.n_tiles, 0u, 1u, w.at(w.p.off_tot));
+    be.d2h(found, w.at(w.p.off_tot), sizeof(uint64_t));
+    be.sync();
+}
+// the writing call, behind run_coll_count on the same workspace
+template <typename idx_t>
+void run_coll_write(Backend& be, const idx_t* dSA, const idx_t* dLCP, uint64_t n, uint64_t k, const CollDocs& dc, const CollTable& tab,
+                    const CkFilter& q, void* dRec, uint64_t capacity, const CollWs& w)
+{
+    const uint32_t tg = capped_grid(std::min<uint64_t>(w.p.n_tiles, 1u << 20), FM_NT);
+    launch_coll_run<idx_t, CK_WRITE>(be, tg, dSA, dLCP, n, k, dc, tab, q, static_cast<uint64_t*>(dRec), capacity, w);
+    be.sync();
+}
+inline void coll_zero_summary(uint64_t* freq, uint64_t* shared, uint32_t m)
+{
+    std::memset(freq, 0, (CK_MAX_DOCS + 1) * sizeof(uint64_t));
+    std::memset(shared, 0, (size_t)m * m * sizeof(uint64_t));
+}
+template <typename idx_t>
+void run_coll_sharing(Backend& be, const idx_t* dSA, const idx_t* dLCP, uint64_t n, uint64_t k, const CollDocs& dc, uint64_t* freq, uint64_t* shared,
+                      const CollWs& w)
+{
+    CollTable tab;
+    run_coll_edges<idx_t>(be, dSA, dLCP, n, k, dc, tab, w);
+    launch_coll_run<idx_t, CK_SHARING>(be, w.p.grid, dSA, dLCP, n, k, dc, tab, CkFilter{1, 0, 0, 0}, nullptr, 0, w);
+    CAPS_LAUNCH(ck_sum_kernel, (CK_COLS + FM_NT - 1) / FM_NT, FM_NT, be, (const uint64_t*)w.at(w.p.off_hist), w.p.grid, w.at(w.p.off_tot));
+    std::vector<uint64_t> t(CK_COLS);
+    be.d2h(t.data(), w.at(w.p.off_tot), t.size() * sizeof(uint64_t));
+    be.sync();
+    const uint32_t m = dc.m;
+    coll_zero_summary(freq, shared, m);
+    for (uint32_t c = 1; c <= m; ++c) freq[c] = t[CK_FREQ + c];
+    freq[m] += t[CK_FULL];
+    for (uint32_t a = 0; a < m; ++a)
+        for (uint32_t b = a; b < m; ++b) shared[(size_t)a * m + b] = shared[(size_t)b * m + a] = t[(size_t)a * CK_MAX_DOCS + b] + t[CK_FULL];
+}
+
+template <typename idx_t>
+int coll_kmers_device(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, const CollDocs& dc, const CkFilter& q0, void* dRec, uint64_t capacity,
+                      uint64_t* n_records, void* workspace, uint64_t workspace_bytes, void* stream)
+{
+    if (int rc = coll_check<idx_t>(dSA, dLCP, n, k, dc, workspace, workspace_bytes)) return rc;
+    if (int rc = coll_check_filter(dc, q0)) return rc;
+    if (!n_records) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (reinterpret_cast<uintptr_t>(dRec) & 7u) return fail(CAPS_SA_EINVAL, "dRecords must be 8-byte aligned");
+    CkFilter q = q0;
+    if (q.min_docs == 0) q.min_docs = 1;
+    *n_records = 0;
+    if (n == 0 || k > n) return CAPS_SA_OK;
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);
+        const CollWs w = coll_ws(da, workspace, workspace_bytes, n);
+        const idx_t* sa = static_cast<const idx_t*>(dSA);
+        const idx_t* lcp = static_cast<const idx_t*>(dLCP);
+        CollTable tab;
+        run_coll_count<idx_t>(be, sa, lcp, n, k, dc, tab, q, n_records, w);
+        if (!dRec) return CAPS_SA_OK;
+        if (*n_records > capacity) return fail(CAPS_SA_EINVAL, "capacity is smaller than the number of records (*n_records; a call with dRecords = NULL counts them)");
+        if (*n_records) run_coll_write<idx_t>(be, sa, lcp, n, k, dc, tab, q, dRec, capacity, w);
+        return CAPS_SA_OK;
+    });
+}
+template <typename idx_t>
+int coll_sharing_device(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, const CollDocs& dc, uint64_t* freq, uint64_t* shared,
+                        void* workspace, uint64_t workspace_bytes, void* stream)
+{
+    if (int rc = coll_check<idx_t>(dSA, dLCP, n, k, dc, workspace, workspace_bytes)) return rc;
+    if (!freq || !shared) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (n == 0 || k > n) { coll_zero_summary(freq, shared, dc.m); return CAPS_SA_OK; }
+    return guarded([&]() -> int {
+        Backend be(static_cast<decltype(Backend::stream)>(stream));
+        DevAllocs da(be);
+        const CollWs w = coll_ws(da, workspace, workspace_bytes, n);
+        run_coll_sharing<idx_t>(be, static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), n, k, dc, freq, shared, w);
+        return CAPS_SA_OK;
+    });
+}
+template <typename idx_t>
+int coll_kmers_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint64_t k, const CollDocs& dc, const CkFilter& q0, void* records, uint64_t capacity,
+                    uint64_t* n_records, int device)
+{
+    if (int rc = coll_check<idx_t>(SA, LCP, n, k, dc, nullptr, 0)) return rc;
+    if (int rc = coll_check_filter(dc, q0)) return rc;
+    if (!n_records) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (reinterpret_cast<uintptr_t>(records) & 7u) return fail(CAPS_SA_EINVAL, "records must be 8-byte aligned");
+    CkFilter q = q0;
+    if (q.min_docs == 0) q.min_docs = 1;
+    *n_records = 0;
+    if (n == 0 || k > n) return CAPS_SA_OK;
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        Backend be(nullptr);
+        DevAllocs da(be);
+        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
+        const CollWs w = coll_ws(da, nullptr, 0, n);
+        CollTable tab;
+        run_coll_count<idx_t>(be, a.sa, a.lcp, n, k, dc, tab, q, n_records, w);
+        if (!records) return CAPS_SA_OK;
+        if (*n_records > capacity) return fail(CAPS_SA_EINVAL, "capacity is smaller than the number of records (*n_records; a call with records = NULL counts them)");
+        if (*n_records == 0) return CAPS_SA_OK;
+        const uint64_t found = *n_records;
+        uint64_t* dRec = da.get<uint64_t>(4 * found);
+        run_coll_write<idx_t>(be, a.sa, a.lcp, n, k, dc, tab, q, dRec, found, w);
+        be.d2h(records, dRec, found * 32);
+        be.sync();
+        return CAPS_SA_OK;
+    });
+}
+template <typename idx_t>
+int coll_sharing_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint64_t k, const CollDocs& dc, uint64_t* freq, uint64_t* shared, int device)
+{
+    if (int rc = coll_check<idx_t>(SA, LCP, n, k, dc, nullptr, 0)) return rc;
+    if (!freq || !shared) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (n == 0 || k > n) { coll_zero_summary(freq, shared, dc.m); return CAPS_SA_OK; }
+    DeviceScope restore_device_;
+    if (int rc = set_device(device)) return rc;
+    return guarded([&]() -> int {
+        Backend be(nullptr);
+        DevAllocs da(be);
+        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
+        run_coll_sharing<idx_t>(be, a.sa, a.lcp, n, k, dc, freq, shared, coll_ws(da, nullptr, 0, n));
+        return CAPS_SA_OK;
+    });
+}
+
 // ---- MUMs and MEMs between two texts (include/caps_sa_hip.h "MUMs and MEMs between two texts"; kernels.h xm_*) ----------------------------
 // Workspace: cnt[XM_KEYS][n_tiles] | tot[XM_KEYS] | lcs[2 * grid] | out[8], 64-bit words.
 struct CrossPlan {
@@ -4140,6 +4383,29 @@ int CAPS_API(cross_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) 
 CAPS_DEFINE_CROSS(u32, uint32_t)
 CAPS_DEFINE_CROSS(u64, uint64_t)
 #undef CAPS_DEFINE_CROSS
+int CAPS_API(coll_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::coll_workspace_bytes(n, idx_bytes, bytes); }
+#define CAPS_DEFINE_COLL(SFX, IDX)                                                                                          \
+    int CAPS_API(coll_kmers_device_##SFX)(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, const uint64_t* doc_start, \
+                                          const uint64_t* doc_len, uint32_t m, uint64_t min_docs, uint64_t max_docs,        \
+                                          uint64_t all_of, uint64_t none_of, void* dRecords, uint64_t capacity,             \
+                                          uint64_t* n_records, void* ws, uint64_t ws_bytes, void* stream)                   \
+    { return caps::coll_kmers_device<IDX>(dSA, dLCP, n, k, caps::CollDocs{doc_start, doc_len, m},                           \
+                                          caps::CkFilter{min_docs, max_docs, all_of, none_of}, dRecords, capacity, n_records, ws, ws_bytes, stream); } \
+    int CAPS_API(coll_sharing_device_##SFX)(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, const uint64_t* doc_start, \
+                                            const uint64_t* doc_len, uint32_t m, uint64_t* freq, uint64_t* shared, void* ws, \
+                                            uint64_t ws_bytes, void* stream)                                                \
+    { return caps::coll_sharing_device<IDX>(dSA, dLCP, n, k, caps::CollDocs{doc_start, doc_len, m}, freq, shared, ws, ws_bytes, stream); } \
+    int CAPS_API(coll_kmers_##SFX)(const IDX* SA, const IDX* LCP, uint64_t n, uint64_t k, const uint64_t* doc_start,        \
+                                   const uint64_t* doc_len, uint32_t m, uint64_t min_docs, uint64_t max_docs, uint64_t all_of, \
+                                   uint64_t none_of, void* records, uint64_t capacity, uint64_t* n_records, int device)     \
+    { return caps::coll_kmers_host<IDX>(SA, LCP, n, k, caps::CollDocs{doc_start, doc_len, m},                               \
+                                        caps::CkFilter{min_docs, max_docs, all_of, none_of}, records, capacity, n_records, device); } \
+    int CAPS_API(coll_sharing_##SFX)(const IDX* SA, const IDX* LCP, uint64_t n, uint64_t k, const uint64_t* doc_start,      \
+                                     const uint64_t* doc_len, uint32_t m, uint64_t* freq, uint64_t* shared, int device)     \
+    { return caps::coll_sharing_host<IDX>(SA, LCP, n, k, caps::CollDocs{doc_start, doc_len, m}, freq, shared, device); }
+CAPS_DEFINE_COLL(u32, uint32_t)
+CAPS_DEFINE_COLL(u64, uint64_t)
+#undef CAPS_DEFINE_COLL
 int CAPS_API(lpf_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::lpf_workspace_bytes(n, idx_bytes, bytes); }
 int CAPS_API(lz77_workspace_bytes)(uint64_t n, int idx_bytes, uint64_t* bytes) { return caps::lz77_workspace_bytes(n, idx_bytes, bytes); }
 #define CAPS_DEFINE_LZ(SFX, IDX)                                                                                            \

@@ -32,6 +32,12 @@
 //   over LCP without the text or the arrays.  Refused with a bounded context;
 // * --lce INDEX PAIRS [--mismatches K] (not in the reference): one pair of text positions "i j" per line of PAIRS; per pair one line
 //   on stdout, the length of the longest common extension of T[i ..) and T[j ..) with at most K (0 .. 1024, default 0) mismatches;
+// * --docs FILE with --kmer-sharing K PATH and / or --coll-kmers K PATH [--min-docs A] [--max-docs B] (not in the reference; on the build
+//   line): FILE holds one `start length` per line, up to 64 ascending, disjoint documents inside the text.  --kmer-sharing writes
+//   `S<TAB>a<TAB>b<TAB>count` for a <= b (the k-mers documents a and b share), then `F<TAB>c<TAB>count` for c = 1 .. m (the k-mers in
+//   exactly c documents); it works with --raw.  --coll-kmers writes `kmer<TAB>occ<TAB>docs as 16 hex digits` per k-mer in min-docs ..
+//   max-docs documents and is refused with --raw for the reason --kmers is.  Either without --docs, a malformed or overlapping FILE,
+//   --min-docs / --max-docs without --coll-kmers and a bounded context are refused before anything is written.
 // * --cross-mums SPLIT PATH [--min-len L] and --cross-mems SPLIT PATH [--min-len L] [--max-occ C] (not in the reference; on the build
 //   line): the text as built (remapped, or with --raw the file's own bytes) is A . sep . B with the separator at SPLIT - 1; after the
 //   SA / LCP output, the maximal unique matches, or the maximal exact matches whose first L bytes occur at most C (2 .. 64, default
@@ -113,6 +119,11 @@
 #define CAPS_CLI_NO_CROSS 1
 #endif
 
+// ... and for one that predates the collection k-mer entry points: the CLI without --kmer-sharing and --coll-kmers.
+#if defined(caps_sa_hip_build_multi_u32) && !defined(caps_sa_hip_coll_kmers_u32)
+#define CAPS_CLI_NO_COLL 1
+#endif
+
 static bool read_input(const std::string& path, std::string& text)
 {
     std::ifstream in(path, std::ios::binary | std::ios::ate);
@@ -150,11 +161,52 @@ struct CrossJob {
     bool any() const { return !mums_path.empty() || !mems_path.empty(); }
 };
 
+// what --docs / --kmer-sharing / --coll-kmers ask for (k = 0: not asked for)
+struct CollJob {
+    std::vector<std::pair<uint64_t, uint64_t>> docs;
+    size_t sharing_k = 0, kmers_k = 0, min_docs = 1, max_docs = 0;
+    std::string sharing_path, kmers_path;
+    bool any() const { return sharing_k || kmers_k; }
+};
+
+// a --docs file: one `start length` per line, 1 .. 64 lines, ascending and disjoint inside a text of n bytes
+static bool read_docs(const std::string& path, size_t n, std::vector<std::pair<uint64_t, uint64_t>>& docs, std::string& why)
+{
+    std::string lines;
+    {
+        std::ifstream in(path, std::ios::binary);
+        if (!in) { why = "cannot open " + path; return false; }
+        lines.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+    }
+    size_t prev_end = 0;
+    for (size_t a = 0; a < lines.size();) {
+        size_t b = lines.find('\n', a);
+        if (b == std::string::npos) b = lines.size();
+        std::string line = lines.substr(a, b - a);
+        a = b + 1;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        const size_t sp = line.find_first_of(" \t");
+        size_t start = 0, len = 0;
+        if (sp == std::string::npos || !parse_count(line.substr(0, sp), start) || !parse_count(line.substr(line.find_first_not_of(" \t", sp)), len)) {
+            why = "line " + std::to_string(docs.size() + 1) + " is not `start length`: " + line;
+            return false;
+        }
+        if (len > n || start > n - len) { why = "document " + std::to_string(docs.size()) + " passes the end of the text (n = " + std::to_string(n) + ")"; return false; }
+        if (start < prev_end) { why = "document " + std::to_string(docs.size()) + " overlaps or precedes the one before it"; return false; }
+        prev_end = start + len;
+        docs.emplace_back(start, len);
+        if (docs.size() > 64) { why = "more than 64 documents"; return false; }
+    }
+    if (docs.empty()) { why = "no document in " + path; return false; }
+    return true;
+}
+
 template <typename idx_t>
 static int run(const std::string& text, const std::string& out_path, size_t p, size_t ctx, bool pretty, const std::vector<int>& devices,
                const std::string& bwt_path, const std::string& fm_path = std::string(), uint32_t fm_sample = 32, uint32_t fm_text_sample = 0, bool raw = false,
                const KmerJob& km = KmerJob(), const std::string& lz_path = std::string(), const std::string& lce_path = std::string(),
-               const CrossJob& cross = CrossJob())
+               const CrossJob& cross = CrossJob(), const CollJob& coll = CollJob())
 {
     if (p > std::numeric_limits<idx_t>::max()) { std::cerr << "subproblem-count does not fit the index type\n"; return EXIT_FAILURE; }
     // the bounded-context mode replays the reference's merge history, one GPU thread per merge node -- the top levels
@@ -253,6 +305,34 @@ static int run(const std::string& text, const std::string& out_path, size_t p, s
         if (!out) return EXIT_FAILURE;
         std::cerr << (mems ? "cross-mems: " : "cross-mums: ") << s.records << " records, " << s.skipped_runs << " skipped runs, longest common substring "
                   << s.lcs_len << " at " << s.lcs_a << " and " << s.lcs_b << ".\n";
+    }
+#endif
+#ifndef CAPS_CLI_NO_COLL
+    if (coll.sharing_k) {
+        std::vector<uint64_t> freq, shared;
+        suf_arr.kmer_sharing(coll.sharing_k, coll.docs, freq, shared);
+        const size_t m = coll.docs.size();
+        std::ofstream out(coll.sharing_path, std::ios::binary);
+        if (!out) { std::cerr << coll.sharing_path << " : cannot open for writing\n"; return EXIT_FAILURE; }
+        for (size_t a = 0; a < m; ++a)
+            for (size_t b = a; b < m; ++b) out << "S\t" << a << '\t' << b << '\t' << shared[a * m + b] << '\n';
+        uint64_t total = 0;
+        for (size_t c = 1; c <= m; ++c) { out << "F\t" << c << '\t' << freq[c] << '\n'; total += freq[c]; }
+        if (!out) return EXIT_FAILURE;
+        std::cerr << "k-mer sharing: " << total << " distinct " << coll.sharing_k << "-mers in " << m << " documents, " << freq[m] << " in all of them.\n";
+    }
+    if (coll.kmers_k) {
+        const auto table = suf_arr.collection_kmers(coll.kmers_k, coll.docs, coll.min_docs, coll.max_docs);
+        std::ofstream out(coll.kmers_path, std::ios::binary);
+        if (!out) { std::cerr << coll.kmers_path << " : cannot open for writing\n"; return EXIT_FAILURE; }
+        char hex[17];
+        for (const auto& r : table) {
+            out.write(text.data() + suf_arr.SA()[r.first], static_cast<std::streamsize>(coll.kmers_k));
+            std::snprintf(hex, sizeof hex, "%016llx", static_cast<unsigned long long>(r.docs));
+            out << '\t' << r.occ << '\t' << hex << '\n';
+        }
+        if (!out) return EXIT_FAILURE;
+        std::cerr << "collection k-mers: " << table.size() << " " << coll.kmers_k << "-mers written.\n";
     }
 #endif
     return 0;
@@ -587,8 +667,38 @@ int main(int argc, char* argv[])
     bool kmers = false, spectrum = false, min_count_given = false, max_count_given = false, lz = false;
     CrossJob cross;                                        // --cross-mums / --cross-mems
     bool min_len_given = false, max_occ_given = false;
+    CollJob coll;                                          // --docs / --kmer-sharing / --coll-kmers
+    std::string docs_path;
+    bool docs_given = false, min_docs_given = false, max_docs_given = false;
     for (int i = 1; i < argc; ++i) {
         if (std::strcmp(argv[i], "--pretty-print") == 0) pretty = true;
+        else if (std::strcmp(argv[i], "--docs") == 0) {
+            if (docs_given) { std::cerr << "--docs: given twice\n"; return EXIT_FAILURE; }
+            if (i + 1 >= argc || std::strncmp(argv[i + 1], "--", 2) == 0 || !argv[i + 1][0]) { std::cerr << "--docs: usage: --docs FILE\n"; return EXIT_FAILURE; }
+            docs_given = true;
+            docs_path = argv[++i];
+        }
+        else if (std::strcmp(argv[i], "--kmer-sharing") == 0 || std::strcmp(argv[i], "--coll-kmers") == 0) {
+            const bool table = std::strcmp(argv[i], "--coll-kmers") == 0;
+            const char* opt = argv[i];
+            size_t k = 0;
+            if ((table ? coll.kmers_k : coll.sharing_k)) { std::cerr << opt << ": given twice\n"; return EXIT_FAILURE; }
+            if (i + 2 >= argc || !parse_count(argv[i + 1], k) || k < 1 || std::strncmp(argv[i + 2], "--", 2) == 0 || !argv[i + 2][0]) {
+                std::cerr << opt << ": usage: " << opt << " K PATH (K >= 1)\n";
+                return EXIT_FAILURE;
+            }
+            if (table) { coll.kmers_k = k; coll.kmers_path = argv[i + 2]; }
+            else { coll.sharing_k = k; coll.sharing_path = argv[i + 2]; }
+            i += 2;
+        }
+        else if (std::strcmp(argv[i], "--min-docs") == 0 || std::strcmp(argv[i], "--max-docs") == 0) {
+            const bool lo = std::strcmp(argv[i], "--min-docs") == 0;
+            size_t v = 0;
+            if (i + 1 >= argc || !parse_count(argv[i + 1], v) || v < 1) { std::cerr << argv[i] << ": a number of documents of at least 1, please\n"; return EXIT_FAILURE; }
+            (lo ? coll.min_docs : coll.max_docs) = v;
+            (lo ? min_docs_given : max_docs_given) = true;
+            ++i;
+        }
         else if (std::strcmp(argv[i], "--kmers") == 0 || std::strcmp(argv[i], "--kmer-spectrum") == 0) {
             const bool table = std::strcmp(argv[i], "--kmers") == 0;
             const char* opt = argv[i];
@@ -684,7 +794,8 @@ int main(int argc, char* argv[])
                      "<(optional)-bounded-context> <(optional)--pretty-print> <(optional)--gpus N> <(optional)--bwt PATH> "
                      "<(optional)--fm-index PATH [--fm-sample S] [--fm-text-sample T]> <(optional)--raw> "
                      "<(optional)--kmers K PATH [--min-count A] [--max-count B]> <(optional)--kmer-spectrum K PATH> <(optional)--lz77 PATH> "
-                     "<(optional)--lce-index PATH> <(optional)--cross-mums SPLIT PATH [--min-len L]> <(optional)--cross-mems SPLIT PATH [--min-len L] [--max-occ C]>\n"
+                     "<(optional)--lce-index PATH> <(optional)--cross-mums SPLIT PATH [--min-len L]> <(optional)--cross-mems SPLIT PATH [--min-len L] [--max-occ C]> "
+                     "<(optional)--docs FILE --kmer-sharing K PATH --coll-kmers K PATH [--min-docs A] [--max-docs B]>\n"
                      "       caps_sa --lce INDEX PAIRS [--mismatches K]\n"
                      "       caps_sa --inverse-bwt IN.bwt OUT\n"
                      "       caps_sa --fm-search INDEX PATTERNS [--locate K]\n"
@@ -766,6 +877,28 @@ int main(int argc, char* argv[])
             }
         }
     }
+    // --docs / --kmer-sharing / --coll-kmers: the same manners
+#ifdef CAPS_CLI_NO_COLL
+    if (coll.any() || docs_given) { std::cerr << (coll.kmers_k ? "--coll-kmers" : coll.sharing_k ? "--kmer-sharing" : "--docs") << ": not built into this driver\n"; return EXIT_FAILURE; }
+#endif
+    if (min_docs_given && !coll.kmers_k) { std::cerr << "--min-docs: only with --coll-kmers K PATH\n"; return EXIT_FAILURE; }
+    if (max_docs_given && !coll.kmers_k) { std::cerr << "--max-docs: only with --coll-kmers K PATH\n"; return EXIT_FAILURE; }
+    if (docs_given && !coll.any()) { std::cerr << "--docs: only with --kmer-sharing K PATH or --coll-kmers K PATH\n"; return EXIT_FAILURE; }
+    if (coll.any()) {
+        const char* opt = coll.kmers_k ? "--coll-kmers" : "--kmer-sharing";
+        if (!docs_given) { std::cerr << opt << ": needs --docs FILE (one `start length` per line)\n"; return EXIT_FAILURE; }
+        if (coll.kmers_k && raw) { std::cerr << "--coll-kmers: the table is lines of text, and --raw keeps arbitrary bytes that do not make lines (--kmer-sharing works with --raw)\n"; return EXIT_FAILURE; }
+        if (max_docs_given && coll.min_docs > coll.max_docs) { std::cerr << "--coll-kmers: --min-docs " << coll.min_docs << " is above --max-docs " << coll.max_docs << "\n"; return EXIT_FAILURE; }
+        struct stat sb;
+        if (stat(pos[0].c_str(), &sb) != 0) { std::cerr << pos[0] << " : cannot open\n"; return EXIT_FAILURE; }
+        const size_t n = static_cast<size_t>(sb.st_size);
+        if (ctx != 0 && ctx < n) {
+            std::cerr << opt << ": a bounded-context order (bounded-context " << ctx << ") is not a suffix array and has no k-mer table\n";
+            return EXIT_FAILURE;
+        }
+        std::string why;
+        if (!read_docs(docs_path, n, coll.docs, why)) { std::cerr << "--docs: " << why << "\n"; return EXIT_FAILURE; }
+    }
     // --fm-index: the same manners
     if (fm_sample_given && !fm) { std::cerr << "--fm-sample: only with --fm-index PATH\n"; return EXIT_FAILURE; }
     if (fm_text_given && !fm) { std::cerr << "--fm-text-sample: only with --fm-index PATH or --fm-from-bwt\n"; return EXIT_FAILURE; }
@@ -808,8 +941,8 @@ int main(int argc, char* argv[])
 
     std::cerr << "Text length: " << text.size() << ".\n";
     try {
-        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path, lce_path, cross);
-        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path, lce_path, cross);
+        if (text.size() <= std::numeric_limits<uint32_t>::max()) return run<uint32_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path, lce_path, cross, coll);
+        return run<uint64_t>(text, pos[1], p, ctx, pretty, devices, bwt_path, fm_path, (uint32_t)fm_sample, (uint32_t)fm_text_sample, raw, km, lz_path, lce_path, cross, coll);
     } catch (const std::exception& e) {
         std::cerr << e.what() << "\n";
         return EXIT_FAILURE;

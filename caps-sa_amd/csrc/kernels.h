@@ -8008,4 +8008,438 @@ GLOBAL_FN LAUNCH_BOUNDS(FM_NT) xm_finish_kernel(KCTX const idx_t* __restrict__ S
     }
 }
 
+// ---- k-mers across a collection (capi_impl.h coll_*; include/caps_sa_hip.h "k-mers across a collection") ------------------------------
+// Heads and runs are kmer_*'s; every rank of a run that lies IN a document adds that document's bit to the run's `docs` and 1 to its
+// `occ`: a segmented OR and a segmented sum whose segments are the runs.  Tiles of KMER_TILE ranks, FM_NT threads, grid-stride:
+//   ck_edge_kernel   per tile: its first head (n: none), and (docs, occ) of the ranks in front of it -- the part of the tile that belongs
+//                    to a run headed in an earlier tile.  LCP is read up to the first head, SA only in front of it.
+//   ck_close_kernel  one workgroup, backward over the tiles: carry[t] = what the tiles behind t add to the run that is open at t's end
+//                    (over any number of headless tiles, up to and with the front part of the next tile that has a head)
+//   kmer_next_kernel next[t] = the first head at or after tile t (run lengths across tiles)
+//   ck_run_kernel    per tile: coalesced 16-byte loads of LCP and SA leave one byte per rank in LDS (its document, CK_OUT, CK_HEAD); a
+//                    lane owns KMER_LANE consecutive ranks; the lanes' front parts are scanned backward in two steps of 16 as
+//                    (docs, occ, has a head), then every lane closes the runs it heads.  No lane walks beyond its own 64 ranks.
+// The document of a position is the result of at most 6 comparisons with the table in LDS; nothing is indexed by a value read from SA
+// or LCP.
+constexpr uint32_t CK_MAX_DOCS = 64;
+constexpr uint32_t CK_OUT = 0x40u, CK_HEAD = 0x80u;                // bits of a rank's byte; bits 0 .. 5: its document
+constexpr uint32_t CK_NONE = 0xFFFFFFFFu;
+constexpr uint32_t CK_LANE_WORDS = KMER_LANE / 4;                  // a lane's bytes as words ...
+constexpr uint32_t CK_LANE_PITCH = CK_LANE_WORDS + 1;              // ... one word apart: lanes that read word j hit different banks
+constexpr uint32_t CK_CELLS = CK_MAX_DOCS * CK_MAX_DOCS;           // the matrix, cell [a][b] with a <= b
+constexpr uint32_t CK_FREQ = CK_CELLS;                             // then freq[0 .. 64]
+constexpr uint32_t CK_FULL = CK_FREQ + CK_MAX_DOCS + 1;            // then the k-mers that every document has
+constexpr uint32_t CK_COLS = CK_FULL + 1;
+#ifdef CAPS_EMUL
+constexpr uint32_t CK_FLUSH_TILES = 2;                             // small on purpose: the flush runs
+#else
+constexpr uint32_t CK_FLUSH_TILES = 1u << 16;                      // a tile adds at most 2^14 to a 32-bit counter of its workgroup
+#endif
+enum { CK_COUNT = 0, CK_WRITE = 1, CK_SHARING = 2 };
+struct CkFilter { uint64_t min_docs, max_docs, all_of, none_of; };
+
+// the table in LDS: start[64] | end[64]; entries from m on hold start = 2^64 - 1, end = 0
+DEV_INLINE void ck_load_table(uint64_t* __restrict__ tab, const uint64_t* __restrict__ dtab, uint32_t tid)
+{
+    for (uint32_t j = tid; j < 2 * CK_MAX_DOCS; j += FM_NT) tab[j] = dtab[j];
+}
+// the document that holds p .. p + k - 1, or CK_OUT; top = the power of two >= m
+DEV_INLINE uint32_t ck_doc(const uint64_t* __restrict__ tab, uint32_t top, uint64_t p, uint64_t k)
+{
+    uint32_t d = 0;
+    for (uint32_t step = top >> 1; step; step >>= 1) d += tab[d + step] <= p ? step : 0u;
+    const uint64_t s = tab[d], e = tab[CK_MAX_DOCS + d];
+    return s <= p && p <= e && e - p >= k ? d : CK_OUT;
+}
+
+template <typename idx_t>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) ck_edge_kernel(KCTX const idx_t* __restrict__ SA, const idx_t* __restrict__ LCP, uint64_t n, uint64_t k,
+                                               uint64_t n_tiles, const uint64_t* __restrict__ dtab, uint32_t top, uint64_t* __restrict__ head,
+                                               uint64_t* __restrict__ pd, uint64_t* __restrict__ po)
+{
+    using G = KmerGeom<idx_t>;
+    SHARED_ARRAY(uint64_t, tab, 2 * CK_MAX_DOCS);
+    SHARED_ARRAY(uint32_t, acc, 4);                        // the first head (tile-relative), docs low / high, occ
+    PAR(tid) { ck_load_table(tab, dtab, tid); }
+    SYNC();
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t t0 = tile * KMER_TILE;
+        PAR(tid) { if (tid < 4) acc[tid] = tid == 0 ? (uint32_t)KMER_TILE : 0u; }
+        SYNC();
+        PAR(tid) {                                          // kmer_head_kernel's search: a lane stops at its first head
+            uint32_t best = (uint32_t)KMER_TILE;
+            for (uint32_t j0 = 0; j0 < G::ROUNDS && best == (uint32_t)KMER_TILE; j0 += 4) {
+                uint32_t hb[4];
+                UNROLL
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint64_t i0 = t0 + (uint64_t)((j0 + j) * FM_NT + tid) * G::PER;
+                    hb[j] = i0 < n ? kmer_head_bits<idx_t>(LCP, n, k, i0) : 0u;
+                }
+                UNROLL
+                for (uint32_t j = 0; j < 4; ++j)
+                    if (hb[j] && best == (uint32_t)KMER_TILE) best = ((j0 + j) * FM_NT + tid) * G::PER + (uint32_t)__builtin_ctz(hb[j]);
+            }
+            if (best < (uint32_t)KMER_TILE) ATOMIC_MIN_U32(&acc[0], best);
+        }
+        SYNC();
+        PAR(tid) {                                          // the ranks in front of it
+            const uint64_t lim = std::min<uint64_t>(acc[0], n - t0);
+            uint64_t docs = 0;
+            uint32_t occ = 0;
+            for (uint32_t c = tid; (uint64_t)c * G::PER < lim; c += FM_NT) {
+                const uint64_t i0 = t0 + (uint64_t)c * G::PER;
+                const KmerChunk<idx_t> s = kmer_load<idx_t>(SA, n, i0);
+                UNROLL
+                for (uint32_t e = 0; e < G::PER; ++e) {
+                    const uint32_t d = ck_doc(tab, top, (uint64_t)s.v[e], k);
+                    if ((uint64_t)c * G::PER + e < lim && d != CK_OUT) { docs |= 1ull << d; ++occ; }
+                }
+            }
+            if ((uint32_t)docs) ATOMIC_OR_U32(&acc[1], (uint32_t)docs);
+            if ((uint32_t)(docs >> 32)) ATOMIC_OR_U32(&acc[2], (uint32_t)(docs >> 32));
+            if (occ) FETCH_ADD_U32(&acc[3], occ);
+        }
+        SYNC();
+        PAR(tid) {
+            if (tid == 0) {
+                head[tile] = acc[0] < (uint32_t)KMER_TILE ? t0 + acc[0] : n;
+                pd[tile] = (uint64_t)acc[1] | ((uint64_t)acc[2] << 32);
+                po[tile] = acc[3];
+            }
+        }
+        SYNC();
+    }
+}
+
+// one workgroup, kmer_next_kernel's shape with the segmented (OR, sum) from the right: S[t] = front[t] if tile t has a head, else
+// front[t] + S[t + 1]; cd / co[t] = S[t + 1], S[n_tiles] = nothing.  head[] is ck_edge_kernel's (n: no head), not yet kmer_next_kernel's.
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) ck_close_kernel(KCTX const uint64_t* __restrict__ head, const uint64_t* __restrict__ pd,
+                                                const uint64_t* __restrict__ po, uint64_t* __restrict__ cd, uint64_t* __restrict__ co,
+                                                uint64_t n_tiles, uint64_t n)
+{
+    SHARED_ARRAY(uint64_t, part_d, FM_NT);
+    SHARED_ARRAY(uint64_t, part_o, FM_NT);
+    SHARED_ARRAY(uint32_t, part_f, FM_NT);
+    const uint64_t per = (n_tiles + FM_NT - 1) / FM_NT;
+    PAR(tid) {
+        const uint64_t a = std::min<uint64_t>(n_tiles, tid * per), b = std::min<uint64_t>(n_tiles, a + per);
+        uint64_t d = 0, o = 0;
+        uint32_t f = 0;
+        for (uint64_t t = b; t-- > a;) {
+            if (head[t] < n) { d = pd[t]; o = po[t]; f = 1; }
+            else { d |= pd[t]; o += po[t]; }
+        }
+        part_d[tid] = d;
+        part_o[tid] = o;
+        part_f[tid] = f;
+    }
+    SYNC();
+    PAR(tid) {
+        if (tid == 0) {
+            uint64_t d = 0, o = 0;
+            for (uint32_t t = FM_NT; t-- > 0;) {
+                const uint64_t vd = part_d[t], vo = part_o[t];
+                part_d[t] = d;
+                part_o[t] = o;
+                if (part_f[t]) { d = vd; o = vo; }
+                else { d |= vd; o += vo; }
+            }
+        }
+    }
+    SYNC();
+    PAR(tid) {
+        const uint64_t a = std::min<uint64_t>(n_tiles, tid * per), b = std::min<uint64_t>(n_tiles, a + per);
+        uint64_t d = part_d[tid], o = part_o[tid];
+        for (uint64_t t = b; t-- > a;) {
+            cd[t] = d;
+            co[t] = o;
+            if (head[t] < n) { d = pd[t]; o = po[t]; }
+            else { d |= pd[t]; o += po[t]; }
+        }
+    }
+}
+
+// a lane's bytes: (docs, occ) of the ranks in front of its first head, and that head (lane-relative; CK_NONE: no head, all of the lane)
+DEV_INLINE void ck_front(const uint32_t* __restrict__ w16, uint64_t& docs, uint32_t& occ, uint32_t& first)
+{
+    docs = 0;
+    occ = 0;
+    first = CK_NONE;
+    for (uint32_t j = 0; j < CK_LANE_WORDS && first == CK_NONE; ++j) {
+        const uint32_t w = w16[j];
+        UNROLL
+        for (uint32_t e = 0; e < 4; ++e) {
+            const uint32_t b = (w >> (8 * e)) & 0xFFu;
+            if ((b & CK_HEAD) && first == CK_NONE) first = 4 * j + e;
+            if (first == CK_NONE && !(b & CK_OUT)) { docs |= 1ull << (b & 63u); ++occ; }
+        }
+    }
+}
+// the runs a lane heads, in rank order: f(head rank, count, occ, docs) for those with docs != 0.  Behind the lane's last head the run goes
+// on to lane_next and gains (tail_d, tail_o).  A lane behind the last rank heads nothing.
+template <typename F>
+DEV_INLINE void ck_each_run(const uint32_t* __restrict__ w16, uint64_t r0, uint64_t n, uint64_t tail_d, uint64_t tail_o, uint64_t lane_next, F&& f)
+{
+    if (r0 >= n) return;
+    uint64_t docs = 0;
+    uint32_t occ = 0, hd = CK_NONE;
+    for (uint32_t j = 0; j < CK_LANE_WORDS; ++j) {
+        const uint32_t w = w16[j];
+        UNROLL
+        for (uint32_t e = 0; e < 4; ++e) {
+            const uint32_t b = (w >> (8 * e)) & 0xFFu, p = 4 * j + e;
+            if (b & CK_HEAD) {
+                if (hd != CK_NONE && docs) f(r0 + hd, (uint64_t)(p - hd), (uint64_t)occ, docs);
+                hd = p;
+                docs = 0;
+                occ = 0;
+            }
+            if (!(b & CK_OUT)) { docs |= 1ull << (b & 63u); ++occ; }
+        }
+    }
+    if (hd != CK_NONE) {
+        docs |= tail_d;
+        if (docs) f(r0 + hd, lane_next - (r0 + hd), (uint64_t)occ + tail_o, docs);
+    }
+}
+HD bool ck_passes(const CkFilter& q, uint64_t docs)
+{
+    const uint64_t c = (uint64_t)__builtin_popcountll(docs);
+    return c >= q.min_docs && (q.max_docs == 0 || c <= q.max_docs) && (docs & q.all_of) == q.all_of && (docs & q.none_of) == 0;
+}
+
+// MODE CK_COUNT:   cnt[tile] = the collection k-mers headed in the tile that pass the filter.
+// MODE CK_WRITE:   cnt[] scanned (fm_scan_kernel); the same k-mers as records (first | count | occ | docs) at cnt[tile] + their number in
+//                  the tile, four 8-byte stores each; a slot at or beyond cap is not written.
+// MODE CK_SHARING: every collection k-mer into the workgroup's counters in LDS -- a k-mer of all m documents into a register (added to
+//                  every cell on the host), one of a single document with one atomic on its diagonal cell and a register for freq[1],
+//                  any other by its owning lane, one atomic per pair a <= b of its bits.  The counters go out to
+//                  hist[workgroup * CK_COLS + column] as 64-bit sums, every CK_FLUSH_TILES tiles of the workgroup and at its end.
+template <typename idx_t, int MODE>
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) ck_run_kernel(KCTX const idx_t* __restrict__ SA, const idx_t* __restrict__ LCP, uint64_t n, uint64_t k,
+                                              uint64_t n_tiles, const uint64_t* __restrict__ dtab, uint32_t top, uint32_t m,
+                                              const uint64_t* __restrict__ next, const uint64_t* __restrict__ cd,
+                                              const uint64_t* __restrict__ co, CkFilter q, uint64_t* __restrict__ cnt,
+                                              uint64_t* __restrict__ rec, uint64_t cap, uint64_t* __restrict__ hist)
+{
+    using G = KmerGeom<idx_t>;
+    SHARED_ARRAY(uint64_t, tab, 2 * CK_MAX_DOCS);
+    SHARED_ARRAY(uint32_t, rk, FM_NT * CK_LANE_PITCH);     // a byte per rank, a lane's 16 words CK_LANE_PITCH apart
+    SHARED_ARRAY(uint64_t, xd, FM_NT);                     // per lane: the docs in front of its first head
+    SHARED_ARRAY(uint32_t, xo, FM_NT);                     // ... and their occurrences
+    SHARED_ARRAY(uint32_t, lane, FM_NT);                   // per lane: its first head (tile-relative; KMER_TILE: none), then its records
+    SHARED_ARRAY(uint32_t, scan, FM_NT);                   // the scan of lane[] inside its group of 16, exclusive
+    SHARED_ARRAY(uint64_t, rd, FM_NT);                     // what the lanes behind add to a lane's open run, inside its group
+    SHARED_ARRAY(uint32_t, ro, FM_NT);
+    SHARED_ARRAY(uint32_t, grp, 2 * KMER_GROUP);           // per group: its min / sum, and the exclusive scan over the groups
+    SHARED_ARRAY(uint64_t, gd, 2 * KMER_GROUP);
+    SHARED_ARRAY(uint64_t, go, 2 * KMER_GROUP);
+    SHARED_ARRAY(uint32_t, h, MODE == CK_SHARING ? CK_COLS : 1);
+    TL_DECL(uint64_t, st, 3);                              // a lane's tail docs, tail occ, the first head behind its ranks
+    TL_DECL(uint32_t, reg, 2);                             // CK_SHARING: the lane's k-mers of one document, of all m
+    const uint64_t full = m < 64 ? (1ull << m) - 1 : ~0ull;
+    uint32_t tiles_in = 0;                                 // block-uniform: tiles since the last flush
+    bool flushed = false;
+    PAR(tid) {
+        ck_load_table(tab, dtab, tid);
+        TL(reg, tid, 0) = 0;
+        TL(reg, tid, 1) = 0;
+        if (MODE == CK_SHARING) for (uint32_t b = tid; b < CK_COLS; b += FM_NT) h[b] = 0;
+    }
+    SYNC();
+    for (uint64_t tile = K_BLOCK_IDX; tile < n_tiles; tile += K_GRID_DIM) {         // block-uniform
+        const uint64_t t0 = tile * KMER_TILE;
+        PAR(tid) {
+            if (tid == 0 && MODE == CK_COUNT) h[0] = 0;
+            UNROLL
+            for (uint32_t j0 = 0; j0 < G::ROUNDS; j0 += 4) {
+                uint32_t hb[4];
+                KmerChunk<idx_t> s[4];
+                UNROLL
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint64_t i0 = t0 + (uint64_t)((j0 + j) * FM_NT + tid) * G::PER;
+                    hb[j] = 0;
+                    if (i0 < n) { hb[j] = kmer_head_bits<idx_t>(LCP, n, k, i0); s[j] = kmer_load<idx_t>(SA, n, i0); }
+                    else for (uint32_t e = 0; e < G::PER; ++e) s[j].v[e] = 0;
+                }
+                UNROLL
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint32_t c = (j0 + j) * FM_NT + tid;
+                    const uint64_t i0 = t0 + (uint64_t)c * G::PER;
+                    uint32_t w = 0;
+                    UNROLL
+                    for (uint32_t e = 0; e < G::PER; ++e) {
+                        uint32_t b = CK_HEAD | CK_OUT;                               // a rank that does not exist ends the last run
+                        if (i0 + e < n) b = ck_doc(tab, top, (uint64_t)s[j].v[e], k) | (((hb[j] >> e) & 1u) ? CK_HEAD : 0u);
+                        w |= b << (8 * e);
+                    }
+                    const uint32_t ln = c * G::PER / KMER_LANE;
+                    if (G::PER == 4) rk[c + ln] = w;
+                    else reinterpret_cast<uint16_t*>(rk)[c + 2 * ln] = (uint16_t)w;
+                }
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            uint64_t d;
+            uint32_t o, first;
+            ck_front(rk + tid * CK_LANE_PITCH, d, o, first);
+            xd[tid] = d;
+            xo[tid] = o;
+            lane[tid] = first != CK_NONE ? tid * KMER_LANE + first : (uint32_t)KMER_TILE;
+        }
+        SYNC();
+        PAR(tid) {                                          // backward: the first head behind every lane and what lies in front of it
+            if (tid < KMER_GROUP) {
+                uint32_t run = (uint32_t)KMER_TILE, so = 0;
+                uint64_t sd = 0;
+                for (uint32_t j = KMER_GROUP; j-- > 0;) {
+                    const uint32_t at = tid * KMER_GROUP + j, x = lane[at];
+                    scan[at] = run;
+                    rd[at] = sd;
+                    ro[at] = so;
+                    if (x < (uint32_t)KMER_TILE) { sd = xd[at]; so = xo[at]; }
+                    else { sd |= xd[at]; so += xo[at]; }
+                    run = std::min(run, x);
+                }
+                grp[tid] = run;
+                gd[tid] = sd;
+                go[tid] = so;
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            if (tid == 0) {
+                uint32_t run = (uint32_t)KMER_TILE;
+                uint64_t sd = cd[tile], so = co[tile];
+                for (uint32_t g = KMER_GROUP; g-- > 0;) {
+                    const uint32_t x = grp[g];
+                    grp[KMER_GROUP + g] = run;
+                    gd[KMER_GROUP + g] = sd;
+                    go[KMER_GROUP + g] = so;
+                    if (x < (uint32_t)KMER_TILE) { sd = gd[g]; so = go[g]; }
+                    else { sd |= gd[g]; so += go[g]; }
+                    run = std::min(run, x);
+                }
+            }
+        }
+        SYNC();
+        PAR(tid) {
+            const uint32_t g = tid / KMER_GROUP;
+            const uint32_t nx = std::min(scan[tid], grp[KMER_GROUP + g]);
+            const uint64_t lane_next = nx < (uint32_t)KMER_TILE ? t0 + nx : next[tile + 1];
+            uint64_t td = rd[tid], to = ro[tid];
+            if (scan[tid] == (uint32_t)KMER_TILE) { td |= gd[KMER_GROUP + g]; to += go[KMER_GROUP + g]; }
+            TL(st, tid, 0) = td;
+            TL(st, tid, 1) = to;
+            TL(st, tid, 2) = lane_next;
+            const uint64_t r0 = t0 + (uint64_t)tid * KMER_LANE;
+            if (MODE == CK_SHARING) {
+                uint32_t one = 0, all = 0;
+                ck_each_run(rk + tid * CK_LANE_PITCH, r0, n, td, to, lane_next, [&](uint64_t, uint64_t, uint64_t, uint64_t docs) {
+                    if (docs == full) { ++all; return; }
+                    if ((docs & (docs - 1)) == 0) {
+                        const uint32_t a = (uint32_t)__builtin_ctzll(docs);
+                        ++one;
+                        FETCH_ADD_U32(&h[a * CK_MAX_DOCS + a], 1u);
+                        return;
+                    }
+                    FETCH_ADD_U32(&h[CK_FREQ + (uint32_t)__builtin_popcountll(docs)], 1u);
+                    for (uint64_t x = docs; x; x &= x - 1) {
+                        const uint32_t a = (uint32_t)__builtin_ctzll(x);
+                        for (uint64_t y = x; y; y &= y - 1) FETCH_ADD_U32(&h[a * CK_MAX_DOCS + (uint32_t)__builtin_ctzll(y)], 1u);
+                    }
+                });
+                TL(reg, tid, 0) += one;
+                TL(reg, tid, 1) += all;
+            } else {
+                uint32_t mine = 0;
+                ck_each_run(rk + tid * CK_LANE_PITCH, r0, n, td, to, lane_next,
+                            [&](uint64_t, uint64_t, uint64_t, uint64_t docs) { mine += ck_passes(q, docs) ? 1u : 0u; });
+                if (MODE == CK_COUNT) { if (mine) FETCH_ADD_U32(&h[0], mine); }
+                else lane[tid] = mine;
+            }
+        }
+        SYNC();
+        if (MODE == CK_COUNT) {
+            PAR(tid) { if (tid == 0) cnt[tile] = h[0]; }
+            SYNC();
+        }
+        if (MODE == CK_WRITE) {
+            PAR(tid) {                                      // forward: the records of the lanes before every lane
+                if (tid < KMER_GROUP) {
+                    uint32_t run = 0;
+                    for (uint32_t j = 0; j < KMER_GROUP; ++j) {
+                        const uint32_t at = tid * KMER_GROUP + j, x = lane[at];
+                        scan[at] = run;
+                        run += x;
+                    }
+                    grp[tid] = run;
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                if (tid == 0) {
+                    uint32_t run = 0;
+                    for (uint32_t g = 0; g < KMER_GROUP; ++g) { const uint32_t x = grp[g]; grp[KMER_GROUP + g] = run; run += x; }
+                }
+            }
+            SYNC();
+            PAR(tid) {
+                uint64_t at = cnt[tile] + scan[tid] + grp[KMER_GROUP + tid / KMER_GROUP];
+                const uint64_t r0 = t0 + (uint64_t)tid * KMER_LANE;
+                ck_each_run(rk + tid * CK_LANE_PITCH, r0, n, TL(st, tid, 0), TL(st, tid, 1), TL(st, tid, 2),
+                            [&](uint64_t hd, uint64_t c, uint64_t occ, uint64_t docs) {
+                    if (!ck_passes(q, docs)) return;
+                    if (at < cap) {
+                        rec[4 * at] = hd;
+                        rec[4 * at + 1] = c;
+                        rec[4 * at + 2] = occ;
+                        rec[4 * at + 3] = docs;
+                    }
+                    ++at;
+                });
+            }
+            SYNC();
+        }
+        if (MODE == CK_SHARING) {
+            const bool last = tile + K_GRID_DIM >= n_tiles;
+            if (++tiles_in == CK_FLUSH_TILES || last) {     // block-uniform
+                PAR(tid) {
+                    if (TL(reg, tid, 0)) FETCH_ADD_U32(&h[CK_FREQ + 1], TL(reg, tid, 0));
+                    if (TL(reg, tid, 1)) FETCH_ADD_U32(&h[CK_FULL], TL(reg, tid, 1));
+                    TL(reg, tid, 0) = 0;
+                    TL(reg, tid, 1) = 0;
+                }
+                SYNC();
+                PAR(tid) {
+                    for (uint32_t b = tid; b < CK_COLS; b += FM_NT) {
+                        uint64_t* out = &hist[(uint64_t)K_BLOCK_IDX * CK_COLS + b];
+                        *out = (flushed ? *out : 0) + h[b];
+                        h[b] = 0;
+                    }
+                }
+                SYNC();
+                tiles_in = 0;
+                flushed = true;
+            }
+        }
+    }
+    if (MODE == CK_SHARING && !flushed) {                   // a workgroup without a tile: its columns are zeros
+        PAR(tid) { for (uint32_t b = tid; b < CK_COLS; b += FM_NT) hist[(uint64_t)K_BLOCK_IDX * CK_COLS + b] = 0; }
+    }
+}
+
+// tot[column] = the sum over the workgroups' rows of hist[workgroup * CK_COLS + column]; a thread per column, coalesced
+GLOBAL_FN LAUNCH_BOUNDS(FM_NT) ck_sum_kernel(KCTX const uint64_t* __restrict__ hist, uint32_t rows, uint64_t* __restrict__ tot)
+{
+    PAR(tid) {
+        for (uint32_t b = K_BLOCK_IDX * FM_NT + tid; b < CK_COLS; b += K_GRID_DIM * FM_NT) {
+            uint64_t s = 0;
+            for (uint32_t g = 0; g < rows; ++g) s += hist[(uint64_t)g * CK_COLS + b];
+            tot[b] = s;
+        }
+    }
+}
+
 }  // namespace caps

@@ -897,6 +897,75 @@ int caps_sa_hip_cross_mems_u32(const uint32_t* SA, const uint32_t* LCP, const ui
 int caps_sa_hip_cross_mems_u64(const uint64_t* SA, const uint64_t* LCP, const uint8_t* BWT, uint64_t n, uint64_t split, uint64_t min_len,
                                uint32_t max_occ, void* records, uint64_t capacity, uint64_t* summary, int device);
 
+/* ---- k-mers across a collection ------------------------------------------------------
+ * Which k-mers the sequences of a collection share, from the SA and LCP of the text that holds them all: the text is not read.
+ *
+ * DOCUMENTS. m in 1 .. 64 and two host arrays doc_start[m], doc_len[m]: document d is T[doc_start[d] .. doc_start[d] + doc_len[d]).
+ * The ranges are ascending and disjoint -- doc_start[d] + doc_len[d] <= doc_start[d + 1], the last one ends at or before n, all of it
+ * computed without overflow. Gaps belong to no document (separators, headers, nothing). A length of 0 is allowed.
+ *
+ * RUNS. Heads and runs are those of "k-mers from SA and LCP": rank i is a head iff i == 0 or LCP[i] < k; LCP[0] counts as 0.
+ *
+ * RANKS. Rank r with p = SA[r] is IN document d iff doc_start[d] <= p and p + k <= doc_start[d] + doc_len[d], computed without
+ * overflow; otherwise it is OUT: a position in a gap, a k-mer that runs past its document's end, p >= n in arrays that are no text's.
+ * Of a run:  docs = the OR of 1 << d over its IN ranks,  occ = the number of its IN ranks,  count = its length in ranks.
+ * A run is a COLLECTION K-MER iff docs != 0; its bytes are T[SA[first] .. SA[first] + k).
+ * Where documents touch without a separator a run may mix IN and OUT ranks (the k-mer also occurs across a boundary): the rule above
+ * is then the definition, count > occ. With a separator byte that occurs in no document every run is all IN or all OUT.
+ *
+ * coll_kmers: the collection k-mers in rank order (the library's byte order) as records of 32 bytes, little-endian:
+ *     u64 first | u64 count | u64 occ | u64 docs
+ * A record is written iff, with c = popcount(docs): min_docs <= c (min_docs = 0 is treated as 1), c <= max_docs unless max_docs == 0,
+ * (docs & all_of) == all_of and (docs & none_of) == 0. min_docs > m is no error: no record.
+ * The protocol of caps_sa_hip_kmers*: dRecords = NULL is the counting call; *n_records (host) is always written by a call that is not
+ * refused; a non-null dRecords (8-byte aligned) with *n_records > capacity is CAPS_SA_EINVAL, *n_records still valid, nothing written.
+ *
+ * coll_sharing: the summary of every collection k-mer, unfiltered.
+ *     freq (host, u64[65]):  freq[c] = the collection k-mers with popcount(docs) == c; freq[0] = 0 (all 65 words are written).
+ *     shared (host, u64[m * m], row-major):  shared[a * m + b] = the collection k-mers whose docs has both bit a and bit b. The
+ *     diagonal is the number of distinct k-mers of document a, the matrix is symmetric, and
+ *     Jaccard(a, b) = S_ab / (S_aa + S_bb - S_ab), containment of a in b = S_ab / S_aa.
+ *
+ * CAPS_SA_EINVAL, checked before any allocation, nothing written: k == 0; m == 0 or m > 64; null document arrays; ranges that overlap,
+ * descend or pass n; min_docs > max_docs > 0; all_of & none_of != 0; a mask bit at or above m; a null array with n > 0; a null output;
+ * n > UINT32_MAX with _u32; a workspace that is too small. n = 0 succeeds with zeros.
+ *
+ * Arrays of a bounded-context build are not a suffix array: the result is then unspecified. For arrays that are not the SA / LCP of any
+ * text the calls still terminate, read only SA[0 .. n) and LCP[0 .. n) and write only inside the outputs: no value read from the arrays
+ * becomes an index -- the document of a position comes from a search over the at most 64 starts, which are compared, not indexed.
+ * There is no validation pass. Ranks beyond 2^32 (_u64 with n > UINT32_MAX) are untested.
+ *
+ * The workspace (caps_sa_hip_coll_workspace_bytes) is O(n / 16,384) words and a fixed part of about 34 MB, no array of n entries; NULL is
+ * allocated and freed by the call. dSA, dLCP, dRecords and workspace are device pointers on the current device; doc_start, doc_len,
+ * freq, shared and n_records are host pointers; the work runs on hip_stream and has completed on return.
+ */
+int caps_sa_hip_coll_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes);
+int caps_sa_hip_coll_kmers_device_u32(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, const uint64_t* doc_start,
+                                      const uint64_t* doc_len, uint32_t m, uint64_t min_docs, uint64_t max_docs, uint64_t all_of,
+                                      uint64_t none_of, void* dRecords, uint64_t capacity, uint64_t* n_records, void* workspace,
+                                      uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_coll_kmers_device_u64(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, const uint64_t* doc_start,
+                                      const uint64_t* doc_len, uint32_t m, uint64_t min_docs, uint64_t max_docs, uint64_t all_of,
+                                      uint64_t none_of, void* dRecords, uint64_t capacity, uint64_t* n_records, void* workspace,
+                                      uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_coll_sharing_device_u32(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, const uint64_t* doc_start,
+                                        const uint64_t* doc_len, uint32_t m, uint64_t* freq, uint64_t* shared, void* workspace,
+                                        uint64_t workspace_bytes, void* hip_stream);
+int caps_sa_hip_coll_sharing_device_u64(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, const uint64_t* doc_start,
+                                        const uint64_t* doc_len, uint32_t m, uint64_t* freq, uint64_t* shared, void* workspace,
+                                        uint64_t workspace_bytes, void* hip_stream);
+/* Host SA and LCP (and host records): the arrays go up into device buffers of the call's own on `device`, the records come down. */
+int caps_sa_hip_coll_kmers_u32(const uint32_t* SA, const uint32_t* LCP, uint64_t n, uint64_t k, const uint64_t* doc_start,
+                               const uint64_t* doc_len, uint32_t m, uint64_t min_docs, uint64_t max_docs, uint64_t all_of, uint64_t none_of,
+                               void* records, uint64_t capacity, uint64_t* n_records, int device);
+int caps_sa_hip_coll_kmers_u64(const uint64_t* SA, const uint64_t* LCP, uint64_t n, uint64_t k, const uint64_t* doc_start,
+                               const uint64_t* doc_len, uint32_t m, uint64_t min_docs, uint64_t max_docs, uint64_t all_of, uint64_t none_of,
+                               void* records, uint64_t capacity, uint64_t* n_records, int device);
+int caps_sa_hip_coll_sharing_u32(const uint32_t* SA, const uint32_t* LCP, uint64_t n, uint64_t k, const uint64_t* doc_start,
+                                 const uint64_t* doc_len, uint32_t m, uint64_t* freq, uint64_t* shared, int device);
+int caps_sa_hip_coll_sharing_u64(const uint64_t* SA, const uint64_t* LCP, uint64_t n, uint64_t k, const uint64_t* doc_start,
+                                 const uint64_t* doc_len, uint32_t m, uint64_t* freq, uint64_t* shared, int device);
+
 /* ---- kernel-level entry points (host buffers) for differential tests -------------- */
 
 /* merge_sort (src/Suffix_Array.cpp:112-129) of an arbitrary list of cnt distinct suffix
