@@ -76,6 +76,58 @@ struct DevAllocs {
     }
 };
 
+// ---- what every entry point with a workspace shares -----------------------------------------------------------------------------------
+// A plan's `bytes` is its layout alone, every part at a multiple of WS_ALIGN (pipeline.h align_up).  What a *_workspace_bytes query
+// reports is ws_reported(bytes): WS_ALIGN more, the most that aligning a caller's pointer up can cost.  ws_check refuses a caller's
+// workspace that cannot hold the layout, ws_carve gives the aligned base -- in the caller's workspace, or in an allocation of the
+// call's own when there is none.
+inline uint64_t ws_reported(size_t layout_bytes) { return layout_bytes + WS_ALIGN; }
+// WS_SLACK: the bytes that aligning this pointer loses are subtracted first; WS_STRICT: anything below the reported size is refused
+enum WsRule { WS_SLACK, WS_STRICT };
+inline int ws_check(void* workspace, uint64_t workspace_bytes, size_t layout_bytes, const char* too_small, WsRule rule = WS_SLACK)
+{
+    if (!workspace) return CAPS_SA_OK;
+    char* ws = static_cast<char*>(workspace);
+    const uint64_t lost = rule == WS_STRICT ? WS_ALIGN : (uint64_t)(align_up(ws) - ws);
+    if (workspace_bytes < layout_bytes + lost) return fail(CAPS_SA_EINVAL, too_small);
+    return CAPS_SA_OK;
+}
+inline char* ws_carve(DevAllocs& da, void* workspace, size_t layout_bytes)
+{
+    return align_up(workspace ? static_cast<char*>(workspace) : da.get<char>(ws_reported(layout_bytes)));
+}
+
+// the arguments of a size query over (n, idx_bytes); n_limit: the queries that also refuse n above 2^60
+inline int check_size_query(uint64_t n, int idx_bytes, const uint64_t* bytes, bool n_limit = true)
+{
+    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
+    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (n_limit && n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
+    return CAPS_SA_OK;
+}
+// n against the index type, and the arrays of n entries (any_null: one of them is missing)
+template <typename idx_t> int check_arrays(uint64_t n, bool any_null, const char* null_msg)
+{
+    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
+    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
+    if (n && any_null) return fail(CAPS_SA_EINVAL, null_msg);
+    return CAPS_SA_OK;
+}
+
+// host SA and LCP of a host form, uploaded into buffers of the call's own
+template <typename idx_t> struct UploadedSaLcp {
+    idx_t* sa = nullptr;
+    idx_t* lcp = nullptr;
+    UploadedSaLcp(Backend& be, DevAllocs& da, const idx_t* SA, const idx_t* LCP, uint64_t n)
+    {
+        if (!n) return;
+        sa = da.get<idx_t>(n);
+        lcp = da.get<idx_t>(n);
+        be.h2d(sa, SA, n * sizeof(idx_t));
+        be.h2d(lcp, LCP, n * sizeof(idx_t));
+    }
+};
+
 template <typename idx_t> int check_common(const void* T, uint64_t n, uint64_t max_context)
 {
     if (n && !T) return fail(CAPS_SA_EINVAL, "null text");
@@ -93,7 +145,7 @@ int set_device(int device);   // defined by the including translation unit
 inline uint64_t wave_scratch_elems(uint64_t n, uint32_t waves) { return std::max<uint64_t>(4 * TILE_E, (n / waves) * 3 / 2 + 2 * TILE_E); }
 template <typename idx_t> inline size_t wave_scratch_bytes(uint64_t elems)
 {
-    return ((elems * sizeof(uint64_t) + 255) & ~size_t(255)) + 2 * ((elems * sizeof(idx_t) + 255) & ~size_t(255)) + 256;
+    return align_up(elems * sizeof(uint64_t)) + 2 * align_up(elems * sizeof(idx_t)) + WS_ALIGN;
 }
 template <typename idx_t>
 int build_device(const void* dT, uint64_t n, uint64_t p_arg, uint64_t max_context, void* dSA, void* dLCP, void* workspace,
@@ -118,18 +170,18 @@ int build_device(const void* dT, uint64_t n, uint64_t p_arg, uint64_t max_contex
             text_bits = 2;
         }
         // carve from a 256-byte aligned base
-        char* aligned = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(base) + 255) & ~uintptr_t(255));
+        char* aligned = align_up(base);
         Plan<idx_t> pl = make_plan<idx_t>(n, p_arg, aligned, text_bits);
         Builder<idx_t> b(be, pl);
         ElemBuf<idx_t> scratch;
         uint64_t scratch_elems = 0;
         if (waves > 1 && sink) {                         // the waves' work arrays, behind the plan in the caller's workspace
             scratch_elems = wave_scratch_elems(n, waves);
-            char* sb = aligned + ((pl.bytes + 255) & ~size_t(255));
+            char* sb = aligned + align_up(pl.bytes);
             if (workspace && static_cast<char*>(workspace) + workspace_bytes >= sb + wave_scratch_bytes<idx_t>(scratch_elems)) {
                 scratch.key = reinterpret_cast<uint64_t*>(sb);
-                scratch.sa = reinterpret_cast<idx_t*>(sb + ((scratch_elems * sizeof(uint64_t) + 255) & ~size_t(255)));
-                scratch.lcp = reinterpret_cast<idx_t*>(reinterpret_cast<char*>(scratch.sa) + ((scratch_elems * sizeof(idx_t) + 255) & ~size_t(255)));
+                scratch.sa = reinterpret_cast<idx_t*>(sb + align_up(scratch_elems * sizeof(uint64_t)));
+                scratch.lcp = reinterpret_cast<idx_t*>(reinterpret_cast<char*>(scratch.sa) + align_up(scratch_elems * sizeof(idx_t)));
                 scratch.region_bytes = wave_scratch_bytes<idx_t>(scratch_elems);
             } else scratch_elems = 0;
         }
@@ -425,11 +477,11 @@ struct HostPathCache {
     std::vector<char*> host_chunks;    // page-locked staging of the LCP bytes (HostCopySink), host_chunk_bytes each
     size_t host_chunk_bytes = 0;
     uint64_t calls = 0;                // host-buffer builds of this process so far
-    // the FM-index at the head of the block (fm_count_host / fm_locate_host): the host blob it was uploaded from, its size, its
-    // header and a sum over a stride of its body; null when anything else has used the block since
-    const void* fm_host = nullptr;
-    uint64_t fm_bytes = 0, fm_sum = 0;
-    uint64_t fm_hdr[32] = {};
+    // the index blob at the head of the block (the host queries of the FM and LCE indexes): the host blob it was uploaded from, its
+    // size, its header and a sum over a stride of its body; null when anything else has used the block since
+    const void* blob_host = nullptr;
+    uint64_t blob_bytes = 0, blob_sum = 0;
+    uint64_t blob_hdr[32] = {};
 };
 inline HostPathCache& host_cache()
 {
@@ -449,7 +501,24 @@ inline void release_host_cache_locked(HostPathCache& c)
     c.base = nullptr;
     c.bytes = 0;
     c.device = -1;
-    c.fm_host = nullptr;
+    c.blob_host = nullptr;
+}
+
+// The host-path block with room for `total` bytes on `device`: kept when it is large enough, else released and allocated again
+// (the page-locked staging chunks of the builds survive that).  -> whether it was allocated by this call.
+inline bool host_block(HostPathCache& hc, Backend& be, int device, size_t total)
+{
+    if (hc.device == device && hc.bytes >= total) return false;
+    std::vector<char*> keep;
+    keep.swap(hc.host_chunks);
+    const size_t keep_bytes = hc.host_chunk_bytes;
+    release_host_cache_locked(hc);
+    hc.host_chunks.swap(keep);
+    hc.host_chunk_bytes = keep_bytes;
+    hc.base = static_cast<char*>(be.alloc(total));
+    hc.bytes = total;
+    hc.device = device;
+    return true;
 }
 
 // BWT (build_bwt): null, or n bytes of the caller's that receive the BWT slice by slice with the rest of the result (HostCopySink);
@@ -467,8 +536,7 @@ int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, 
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        hc.fm_host = nullptr;                                // (the block is this build's now)
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        hc.blob_host = nullptr;                                // (the block is this build's now)
         // the text arena is sized for 2-bit codes when the first MiB of the text shows at most 4 distinct bytes (a text that
         // turns out to have more is built again below with the arena of 8-bit codes)
         int text_bits = 8;
@@ -483,8 +551,8 @@ int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, 
         const uint64_t earlier_calls = hc.calls++;
         for (;; text_bits = 8) {
         const Plan<idx_t> need = make_plan<idx_t>(n, p_arg, nullptr, text_bits);
-        const size_t off_sa = up(n ? n : 1), off_lcp = off_sa + up((n ? n : 1) * sizeof(idx_t));
-        const size_t off_ws = off_lcp + up((n ? n : 1) * sizeof(idx_t));
+        const size_t off_sa = align_up(n ? n : 1), off_lcp = off_sa + align_up((n ? n : 1) * sizeof(idx_t));
+        const size_t off_ws = off_lcp + align_up((n ? n : 1) * sizeof(idx_t));
         // waves pay when the build is long enough to hide: measured at C2 (256 Mi: 5 ms of build against 38 ms of copies) twelve
         // waves cost 14 ms (per-wave host synchronisations, 24 copies instead of 2), at C3 (3e9) they save 31 of 524 ms
         uint32_t waves = n >= (400ull << 20) ? CAPS_HOST_WAVES : 1u;
@@ -499,29 +567,18 @@ int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, 
         // ~130 GB, which takes seconds)
         const bool narrow_later = sizeof(idx_t) == 4 && waves > 1 && !(std::getenv("CAPS_SA_HOST_NARROW_LCP") && !narrow);
         const uint64_t exc_cap = narrow || narrow_later ? std::max<uint64_t>(1024, n / 32) : 0;
-        const size_t narrow_dev = narrow || narrow_later ? up(n) + up((exc_cap + 1) * sizeof(uint64_t)) + 512 : 0;
+        const size_t narrow_dev = narrow || narrow_later ? align_up(n) + align_up((exc_cap + 1) * sizeof(uint64_t)) + 512 : 0;
         const size_t ws_room = need.bytes + 1024 + wave_scratch_bytes<idx_t>(wave_scratch_elems(n, waves));
         // the BWT's bytes and its primary index, behind everything else (builds without a BWT ask for the block they always did)
-        const size_t off_bwt = off_ws + up(ws_room) + up(narrow_dev);
-        const size_t total = want_bwt ? off_bwt + up(n) + 512 : off_ws + ws_room + narrow_dev;
-        if (hc.device != device || hc.bytes < total) {
-            std::vector<char*> keep;
-            keep.swap(hc.host_chunks);                       // (the staging chunks survive a larger device block)
-            const size_t keep_bytes = hc.host_chunk_bytes;
-            release_host_cache_locked(hc);
-            hc.host_chunks.swap(keep);
-            hc.host_chunk_bytes = keep_bytes;
-            const auto a0 = std::chrono::steady_clock::now();
-            hc.base = static_cast<char*>(be.alloc(total));
-            hc.bytes = total;
-            hc.device = device;
-            if (std::getenv("CAPS_SA_DEBUG_ALLOC"))
-                std::fprintf(stderr, "[alloc] device block of %zu bytes: %.1f ms\n", total,
-                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a0).count());
-        }
+        const size_t off_bwt = off_ws + align_up(ws_room) + align_up(narrow_dev);
+        const size_t total = want_bwt ? off_bwt + align_up(n) + 512 : off_ws + ws_room + narrow_dev;
+        const auto a0 = std::chrono::steady_clock::now();
+        if (host_block(hc, be, device, total) && std::getenv("CAPS_SA_DEBUG_ALLOC"))
+            std::fprintf(stderr, "[alloc] device block of %zu bytes: %.1f ms\n", total,
+                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a0).count());
         // the page-locked chunks for the LCP bytes, allocated beside the upload (HostCopySink::chunks)
         constexpr uint32_t N_CHUNKS = 16;
-        const uint64_t chunk_bytes = narrow ? up((n + N_CHUNKS - 1) / N_CHUNKS) : 0;
+        const uint64_t chunk_bytes = narrow ? align_up((n + N_CHUNKS - 1) / N_CHUNKS) : 0;
         const size_t chunks_need = narrow ? (size_t)((n + chunk_bytes - 1) / chunk_bytes) : 0;
         std::thread ring_alloc;
         std::exception_ptr ring_error;
@@ -557,7 +614,7 @@ int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, 
 #endif
         }
         struct JoinGuard { std::thread& t; ~JoinGuard() { if (t.joinable()) t.join(); } } ring_join{ring_alloc};
-        char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(hc.base) + 255) & ~uintptr_t(255));
+        char* base = align_up(hc.base);
         uint8_t* dT = reinterpret_cast<uint8_t*>(base);
         idx_t* dSA = reinterpret_cast<idx_t*>(base + off_sa);
         idx_t* dLCP = reinterpret_cast<idx_t*>(base + off_lcp);
@@ -581,9 +638,9 @@ int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, 
         sink.dSA = dSA;
         sink.dLCP = dLCP;
         if (narrow) {
-            char* nb = base + off_ws + up(ws_room);
+            char* nb = base + off_ws + align_up(ws_room);
             sink.d8 = reinterpret_cast<uint8_t*>(nb);
-            sink.dexc = reinterpret_cast<uint64_t*>(nb + up(n));
+            sink.dexc = reinterpret_cast<uint64_t*>(nb + align_up(n));
             sink.dexc_count = sink.dexc + exc_cap;
             sink.exc_cap = exc_cap;
             sink.chunks = &hc.host_chunks;
@@ -600,7 +657,7 @@ int build_host(const char* T, uint64_t n, uint64_t p_arg, uint64_t max_context, 
         if (want_bwt) {
             sink.n = n;
             sink.dBWT = reinterpret_cast<uint8_t*>(base + off_bwt);
-            sink.dprimary = reinterpret_cast<uint64_t*>(base + off_bwt + up(n));
+            sink.dprimary = reinterpret_cast<uint64_t*>(base + off_bwt + align_up(n));
             sink.BWT = BWT;
             be.memset(sink.dprimary, 0xFF, sizeof(uint64_t));
             be.sync();
@@ -999,44 +1056,47 @@ int bwt_device(const void* dT, uint64_t n, const void* dSA, uint64_t first, uint
 // The workspace: the LF table ((n + 1) entries), the per-tile key counts, C and the range table, then per level of the splitter
 // lists succ / len / off (level 0: one node per IBWT_S0 rows; level k + 1: one per IBWT_S1 nodes of level k, until a level has at
 // most IBWT_TOP nodes), and the result words of the top walk.
+struct IbwtLevels {
+    uint32_t levels = 0;
+    uint64_t M[16] = {};                                   // nodes of every level
+    size_t succ[16] = {}, len[16] = {}, off[16] = {};      // offsets of the level's three lists
+};
+// the levels over n rows, laid out from offset o on; -> the offset behind the last list
+inline size_t ibwt_levels(IbwtLevels& lv, uint64_t n, size_t idx_bytes, size_t o)
+{
+    for (uint64_t m = n / IBWT_S0 + 1;; m = (m - 1) / IBWT_S1 + 1) {
+        lv.M[lv.levels] = m;
+        lv.succ[lv.levels] = o; o += align_up(m * idx_bytes);
+        lv.len[lv.levels] = o;  o += align_up(m * sizeof(uint64_t));
+        lv.off[lv.levels] = o;  o += align_up(m * sizeof(uint64_t));
+        ++lv.levels;
+        if (m <= IBWT_TOP) return o;
+    }
+}
 struct InvPlan {
     uint64_t n_tiles = 0;
-    uint32_t levels = 0;
-    uint64_t M[16] = {};
     size_t off_cnt = 0, off_total = 0, off_C = 0, off_sym = 0, off_res = 0;
-    size_t off_succ[16] = {}, off_len[16] = {}, off_off[16] = {};
+    IbwtLevels lv;
     size_t bytes = 0;
 };
 template <typename idx_t> InvPlan inv_plan(uint64_t n)
 {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     InvPlan p;
     p.n_tiles = (n + 1 + IBWT_TILE - 1) / IBWT_TILE;
-    size_t o = up((n + 1) * sizeof(idx_t));
-    p.off_cnt = o;   o += up(p.n_tiles * IBWT_KEYS * sizeof(idx_t));
-    p.off_total = o; o += up(IBWT_KEYS * sizeof(uint64_t));
-    p.off_C = o;     o += up((IBWT_KEYS + 1) * sizeof(uint64_t));
-    p.off_sym = o;   o += up((IBWT_KEYS + 1) * sizeof(uint64_t));
-    p.off_res = o;   o += 256;
-    uint64_t m = n / IBWT_S0 + 1;
-    for (;;) {
-        p.M[p.levels] = m;
-        p.off_succ[p.levels] = o; o += up(m * sizeof(idx_t));
-        p.off_len[p.levels] = o;  o += up(m * sizeof(uint64_t));
-        p.off_off[p.levels] = o;  o += up(m * sizeof(uint64_t));
-        ++p.levels;
-        if (m <= IBWT_TOP) break;
-        m = (m - 1) / IBWT_S1 + 1;
-    }
-    p.bytes = o + 256;                               // (room to align the caller's base)
+    size_t o = align_up((n + 1) * sizeof(idx_t));
+    p.off_cnt = o;   o += align_up(p.n_tiles * IBWT_KEYS * sizeof(idx_t));
+    p.off_total = o; o += align_up(IBWT_KEYS * sizeof(uint64_t));
+    p.off_C = o;     o += align_up((IBWT_KEYS + 1) * sizeof(uint64_t));
+    p.off_sym = o;   o += align_up((IBWT_KEYS + 1) * sizeof(uint64_t));
+    p.off_res = o;   o += WS_ALIGN;
+    p.bytes = ibwt_levels(p.lv, n, sizeof(idx_t), o);
     return p;
 }
 
 inline int inverse_bwt_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
 {
-    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
-    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
-    *bytes = idx_bytes == 4 ? inv_plan<uint32_t>(n).bytes : inv_plan<uint64_t>(n).bytes;
+    if (int rc = check_size_query(n, idx_bytes, bytes, false)) return rc;
+    *bytes = ws_reported(idx_bytes == 4 ? inv_plan<uint32_t>(n).bytes : inv_plan<uint64_t>(n).bytes);
     return CAPS_SA_OK;
 }
 
@@ -1050,33 +1110,33 @@ bool run_inverse_bwt(Backend& be, const uint8_t* dB, uint64_t n, uint64_t primar
     uint64_t* C = reinterpret_cast<uint64_t*>(base + p.off_C);
     uint64_t* sym = reinterpret_cast<uint64_t*>(base + p.off_sym);
     uint64_t* res = reinterpret_cast<uint64_t*>(base + p.off_res);
-    auto succ = [&](uint32_t k) { return reinterpret_cast<idx_t*>(base + p.off_succ[k]); };
-    auto len = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.off_len[k]); };
-    auto off = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.off_off[k]); };
+    auto succ = [&](uint32_t k) { return reinterpret_cast<idx_t*>(base + p.lv.succ[k]); };
+    auto len = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.lv.len[k]); };
+    auto off = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.lv.off[k]); };
     auto walk_grid = [](uint64_t walks) { return capped_grid(std::min<uint64_t>((walks + IBWT_Q - 1) / IBWT_Q, 8192), IBWT_NT); };
     const uint32_t tg = capped_grid(std::min<uint64_t>(p.n_tiles, 8192), IBWT_NT);
     CAPS_LAUNCH((ibwt_count_kernel<idx_t>), tg, IBWT_NT, be, dB, n, primary, p.n_tiles, cnt);
     CAPS_LAUNCH((ibwt_scan_kernel<idx_t>), IBWT_KEYS, IBWT_NT, be, cnt, p.n_tiles, total);
     CAPS_LAUNCH(ibwt_c_kernel, 1, 64, be, total, C, sym);
     CAPS_LAUNCH((ibwt_lf_kernel<idx_t>), tg, IBWT_NT, be, dB, n, primary, p.n_tiles, cnt, C, LF);
-    const uint32_t top = p.levels - 1;
-    CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_LINK0>), walk_grid(p.M[0]), IBWT_NT, be, LF, n, p.M[0], (uint64_t)0,
+    const uint32_t top = p.lv.levels - 1;
+    CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_LINK0>), walk_grid(p.lv.M[0]), IBWT_NT, be, LF, n, p.lv.M[0], (uint64_t)0,
                 (const idx_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr, succ(0), len(0), (const uint64_t*)nullptr,
                 (const uint64_t*)nullptr, (uint8_t*)nullptr);
     for (uint32_t k = 1; k <= top; ++k)
-        CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_LINK>), walk_grid(p.M[k]), IBWT_NT, be, LF, n, p.M[k], p.M[k - 1],
+        CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_LINK>), walk_grid(p.lv.M[k]), IBWT_NT, be, LF, n, p.lv.M[k], p.lv.M[k - 1],
                     (const idx_t*)succ(k - 1), (const uint64_t*)len(k - 1), (uint64_t*)nullptr, succ(k), len(k),
                     (const uint64_t*)nullptr, (const uint64_t*)nullptr, (uint8_t*)nullptr);
-    CAPS_LAUNCH((ibwt_top_kernel<idx_t>), 1, IBWT_NT, be, (const idx_t*)succ(top), (const uint64_t*)len(top), p.M[top], n, off(top), res);
+    CAPS_LAUNCH((ibwt_top_kernel<idx_t>), 1, IBWT_NT, be, (const idx_t*)succ(top), (const uint64_t*)len(top), p.lv.M[top], n, off(top), res);
     uint64_t h[3] = {0, 0, 0};
     be.d2h(h, res, sizeof h);
     be.sync();
     if (h[0] != 1) return false;
     for (uint32_t k = top; k >= 1; --k)
-        CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_PROP>), walk_grid(p.M[k]), IBWT_NT, be, LF, n, p.M[k], p.M[k - 1],
+        CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_PROP>), walk_grid(p.lv.M[k]), IBWT_NT, be, LF, n, p.lv.M[k], p.lv.M[k - 1],
                     (const idx_t*)succ(k - 1), (const uint64_t*)len(k - 1), off(k - 1), (idx_t*)nullptr, (uint64_t*)nullptr,
                     (const uint64_t*)off(k), (const uint64_t*)nullptr, (uint8_t*)nullptr);
-    CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_WRITE>), walk_grid(p.M[0]), IBWT_NT, be, LF, n, p.M[0], (uint64_t)0,
+    CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_WRITE>), walk_grid(p.lv.M[0]), IBWT_NT, be, LF, n, p.lv.M[0], (uint64_t)0,
                 (const idx_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr, (idx_t*)nullptr, len(0),
                 (const uint64_t*)off(0), (const uint64_t*)sym, dT);
     be.sync();
@@ -1101,10 +1161,10 @@ int inverse_bwt_device(const void* dB, uint64_t n, uint64_t primary, void* dT, v
     if (int rc = check_inverse<idx_t>(dB, n, primary, dT)) return rc;
     if (!workspace) return fail(CAPS_SA_EINVAL, "null workspace");
     const InvPlan p = inv_plan<idx_t>(n);
-    if (workspace_bytes < p.bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_inverse_bwt_workspace_bytes)");
+    if (int rc = ws_check(workspace, workspace_bytes, p.bytes, "workspace too small (caps_sa_hip_inverse_bwt_workspace_bytes)", WS_STRICT)) return rc;
     return guarded([&]() -> int {
         Backend be(static_cast<decltype(Backend::stream)>(stream));
-        char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+        char* base = align_up(static_cast<char*>(workspace));
         if (!run_inverse_bwt<idx_t>(be, static_cast<const uint8_t*>(dB), n, primary, static_cast<uint8_t*>(dT), base, p))
             return fail(CAPS_SA_EINVAL, not_a_bwt_msg());
         return CAPS_SA_OK;
@@ -1123,21 +1183,10 @@ int inverse_bwt_host(const uint8_t* B, uint64_t n, uint64_t primary, char* T, in
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        hc.fm_host = nullptr;
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        hc.blob_host = nullptr;
         const InvPlan p = inv_plan<idx_t>(n);
-        const size_t off_T = up(n), off_ws = off_T + up(n), total = off_ws + p.bytes;
-        if (hc.device != device || hc.bytes < total) {
-            std::vector<char*> keep;
-            keep.swap(hc.host_chunks);                       // (the staging chunks of the builds survive a larger device block)
-            const size_t keep_bytes = hc.host_chunk_bytes;
-            release_host_cache_locked(hc);
-            hc.host_chunks.swap(keep);
-            hc.host_chunk_bytes = keep_bytes;
-            hc.base = static_cast<char*>(be.alloc(total));
-            hc.bytes = total;
-            hc.device = device;
-        }
+        const size_t off_T = align_up(n), off_ws = off_T + align_up(n), total = off_ws + p.bytes;
+        host_block(hc, be, device, total);
         uint8_t* dB = reinterpret_cast<uint8_t*>(hc.base);
         uint8_t* dT = reinterpret_cast<uint8_t*>(hc.base + off_T);
         be.h2d(dB, B, n);
@@ -1156,20 +1205,21 @@ constexpr uint32_t FM_HDR_WORDS = 32;
 enum { FMH_MAGIC = 0, FMH_VERSION, FMH_N, FMH_PRIMARY, FMH_IDX_BYTES, FMH_SIGMA, FMH_SYMS, FMH_C0, FMH_S = FMH_C0 + 5, FMH_NSAMPLES,
        FMH_NBLOCKS, FMH_OFF_OCC, FMH_OFF_MRANK, FMH_OFF_SAMPLES, FMH_TOTAL, FMH_T, FMH_NTEXT, FMH_OFF_ROWOF, FMH_TOTAL2 };
 
+// (the sections behind the Occ blocks start at multiples of 64 bytes: part of the blob format, not the workspaces' WS_ALIGN)
+inline uint64_t fm_blob_up(uint64_t b) { return (b + 63) & ~uint64_t(63); }
 struct FmLayout {
     uint64_t n_blocks = 0, n_samples = 0, off_occ = 0, off_mrank = 0, off_samples = 0, total = 0;
 };
 inline FmLayout fm_layout(uint64_t n, uint32_t s, int idx_bytes)
 {
-    auto up = [](uint64_t b) { return (b + 63) & ~uint64_t(63); };
     const uint64_t rows = idx_bytes == 4 ? 128 : 256, block_bytes = rows / 2;
     FmLayout l;
     l.n_blocks = (n + 1) / rows + 1;
     l.n_samples = s && n ? (n - 1) / s + 1 : 0;
     l.off_occ = FM_HDR_WORDS * sizeof(uint64_t);
     l.off_mrank = l.off_occ + l.n_blocks * block_bytes;
-    l.off_samples = l.off_mrank + (s ? up(l.n_blocks * (uint64_t)idx_bytes) : 0);
-    l.total = l.off_samples + (s ? up(l.n_samples * (uint64_t)idx_bytes) : 0);
+    l.off_samples = l.off_mrank + (s ? fm_blob_up(l.n_blocks * (uint64_t)idx_bytes) : 0);
+    l.total = l.off_samples + (s ? fm_blob_up(l.n_samples * (uint64_t)idx_bytes) : 0);
     return l;
 }
 inline bool fm_sample_ok(uint64_t s) { return s >= 1 && s <= FM_MAX_SAMPLE && (s & (s - 1)) == 0; }
@@ -1182,7 +1232,7 @@ inline FmTextLayout fm_text_layout(const FmLayout& l, uint64_t n, uint64_t t, in
     FmTextLayout tl;
     tl.m = n ? (n - 1) / t + 1 : 0;
     tl.off = l.total;
-    tl.total = tl.off + ((tl.m * (uint64_t)idx_bytes + 63) & ~uint64_t(63));
+    tl.total = tl.off + fm_blob_up(tl.m * (uint64_t)idx_bytes);
     return tl;
 }
 // the bytes of the blob whose (checked) header is h
@@ -1190,24 +1240,22 @@ inline uint64_t fm_blob_bytes(const uint64_t* h) { return h[FMH_VERSION] == FM_V
 
 inline int fm_index_bytes(uint64_t n, uint32_t s, int idx_bytes, uint64_t* bytes)
 {
-    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
-    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (int rc = check_size_query(n, idx_bytes, bytes, false)) return rc;
     if (s && !fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be 0 (no samples) or a power of two in 1 .. 1024");
     *bytes = fm_layout(n, s, idx_bytes).total;
     return CAPS_SA_OK;
 }
 inline int fm_index_bytes_ex(uint64_t n, uint32_t s, uint32_t t, int idx_bytes, uint64_t* bytes)
 {
-    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
-    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (int rc = check_size_query(n, idx_bytes, bytes, false)) return rc;
     if (!fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be a power of two in 1 .. 1024 (text samples need SA samples)");
     if (!fm_sample_ok(t) || t < s) return fail(CAPS_SA_EINVAL, "text_sample must be a power of two in sa_sample .. 1024");
     *bytes = fm_text_layout(fm_layout(n, s, idx_bytes), n, t, idx_bytes).total;
     return CAPS_SA_OK;
 }
 
-// a few device words of the FM calls (flags, totals), one set per thread and device, kept (primary_word's reasons)
-inline uint64_t* fm_words(Backend& be)
+// a few device words of a call (flags, totals), one set per thread and device, kept (primary_word's reasons)
+inline uint64_t* call_words(Backend& be)
 {
 #ifdef CAPS_EMUL
     const int dev = 0;
@@ -1399,34 +1447,20 @@ int fm_build_device(const void* dB, uint64_t n, uint64_t primary, const void* dS
     });
 }
 
-// the host-path block with room for `total` bytes (what build_host and inverse_bwt_host do)
-inline void fm_host_block(HostPathCache& hc, Backend& be, int device, size_t total)
-{
-    if (hc.device == device && hc.bytes >= total) return;
-    std::vector<char*> keep;
-    keep.swap(hc.host_chunks);
-    const size_t keep_bytes = hc.host_chunk_bytes;
-    release_host_cache_locked(hc);
-    hc.host_chunks.swap(keep);
-    hc.host_chunk_bytes = keep_bytes;
-    hc.base = static_cast<char*>(be.alloc(total));
-    hc.bytes = total;
-    hc.device = device;
-}
 // what identifies an uploaded blob beside its address and size: its header and a sum over at most 4096 words of its body
-inline uint64_t fm_body_sum(const void* index, uint64_t bytes)
+inline uint64_t blob_body_sum(const void* index, uint64_t bytes)
 {
     const uint64_t words = bytes / 8, step = std::max<uint64_t>(1, words / 4096);
     uint64_t s = 0, w = 0;
     for (uint64_t k = FM_HDR_WORDS; k < words; k += step) { std::memcpy(&w, static_cast<const char*>(index) + k * 8, 8); s = s * 0x9E3779B97F4A7C15ull + w; }
     return s;
 }
-inline void fm_mark_resident(HostPathCache& hc, const void* index, uint64_t bytes)
+inline void blob_mark_resident(HostPathCache& hc, const void* index, uint64_t bytes)
 {
-    hc.fm_host = index;
-    hc.fm_bytes = bytes;
-    std::memcpy(hc.fm_hdr, index, sizeof hc.fm_hdr);
-    hc.fm_sum = fm_body_sum(index, bytes);
+    hc.blob_host = index;
+    hc.blob_bytes = bytes;
+    std::memcpy(hc.blob_hdr, index, sizeof hc.blob_hdr);
+    hc.blob_sum = blob_body_sum(index, bytes);
 }
 
 template <typename idx_t>
@@ -1440,10 +1474,9 @@ int fm_build_host(const uint8_t* B, uint64_t n, uint64_t primary, const idx_t* S
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        hc.fm_host = nullptr;
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-        const size_t off_B = up(need), off_SA = off_B + up(n ? n : 1), total = off_SA + (SA ? up(n * sizeof(idx_t)) : 0) + 256;
-        fm_host_block(hc, be, device, total);
+        hc.blob_host = nullptr;
+        const size_t off_B = align_up(need), off_SA = off_B + align_up(n ? n : 1), total = off_SA + (SA ? align_up(n * sizeof(idx_t)) : 0) + WS_ALIGN;
+        host_block(hc, be, device, total);
         uint8_t* dB = reinterpret_cast<uint8_t*>(hc.base + off_B);
         idx_t* dSA = SA ? reinterpret_cast<idx_t*>(hc.base + off_SA) : nullptr;
         be.h2d(dB, B, n);
@@ -1451,7 +1484,7 @@ int fm_build_host(const uint8_t* B, uint64_t n, uint64_t primary, const idx_t* S
         if (int rc = run_fm_build<idx_t>(be, dB, n, primary, dSA, (uint32_t)s, hc.base, nullptr)) return rc;
         be.d2h(index, hc.base, need);
         be.sync();
-        fm_mark_resident(hc, index, need);
+        blob_mark_resident(hc, index, need);
         return CAPS_SA_OK;
     });
 }
@@ -1461,43 +1494,29 @@ int fm_build_host(const uint8_t* B, uint64_t n, uint64_t primary, const idx_t* S
 // inverse BWT's splitter lists (inv_plan's levels: succ / len / off per node).  No array of n entries: n_samples entries of the
 // index width + 20 or 24 bytes per IBWT_S0 rows (+ 1/63 of that for the levels above) + 40 bytes per tile.
 struct FmBwtPlan {
-    uint32_t levels = 0;
-    uint64_t M[16] = {};
     size_t off_present = 0, off_cnt = 0, off_total = 0, off_res = 0, off_stage = 0;
-    size_t off_succ[16] = {}, off_len[16] = {}, off_off[16] = {};
+    IbwtLevels lv;
     size_t bytes = 0;
 };
 template <typename idx_t> FmBwtPlan fm_bwt_plan(uint64_t n, uint32_t s)
 {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     const FmLayout l = fm_layout(n, s, (int)sizeof(idx_t));
     FmBwtPlan p;
     size_t o = 0;
-    p.off_present = o; o += 256;
-    p.off_total = o;   o += 256;
-    p.off_res = o;     o += 256;
-    p.off_cnt = o;     o += up(FM_KEYS * fm_tiles<idx_t>(l) * sizeof(uint64_t));
-    p.off_stage = o;   o += up(l.n_samples * sizeof(idx_t));
-    uint64_t m = n / IBWT_S0 + 1;
-    for (;;) {
-        p.M[p.levels] = m;
-        p.off_succ[p.levels] = o; o += up(m * sizeof(idx_t));
-        p.off_len[p.levels] = o;  o += up(m * sizeof(uint64_t));
-        p.off_off[p.levels] = o;  o += up(m * sizeof(uint64_t));
-        ++p.levels;
-        if (m <= IBWT_TOP) break;
-        m = (m - 1) / IBWT_S1 + 1;
-    }
-    p.bytes = o + 256;                               // (room to align the caller's base)
+    p.off_present = o; o += WS_ALIGN;
+    p.off_total = o;   o += WS_ALIGN;
+    p.off_res = o;     o += WS_ALIGN;
+    p.off_cnt = o;     o += align_up(FM_KEYS * fm_tiles<idx_t>(l) * sizeof(uint64_t));
+    p.off_stage = o;   o += align_up(l.n_samples * sizeof(idx_t));
+    p.bytes = ibwt_levels(p.lv, n, sizeof(idx_t), o);
     return p;
 }
 
 inline int fm_from_bwt_workspace_bytes(uint64_t n, uint32_t s, int idx_bytes, uint64_t* bytes)
 {
-    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
-    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (int rc = check_size_query(n, idx_bytes, bytes, false)) return rc;
     if (!fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be a power of two in 1 .. 1024");
-    *bytes = idx_bytes == 4 ? fm_bwt_plan<uint32_t>(n, s).bytes : fm_bwt_plan<uint64_t>(n, s).bytes;
+    *bytes = ws_reported(idx_bytes == 4 ? fm_bwt_plan<uint32_t>(n, s).bytes : fm_bwt_plan<uint64_t>(n, s).bytes);
     return CAPS_SA_OK;
 }
 
@@ -1533,9 +1552,9 @@ int run_fm_from_bwt(Backend& be, const uint8_t* dB, uint64_t n, uint64_t primary
         sc.total = reinterpret_cast<uint64_t*>(base + p.off_total);
         uint64_t* res = reinterpret_cast<uint64_t*>(base + p.off_res);
         idx_t* stage = reinterpret_cast<idx_t*>(base + p.off_stage);
-        auto succ = [&](uint32_t k) { return reinterpret_cast<idx_t*>(base + p.off_succ[k]); };
-        auto len = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.off_len[k]); };
-        auto off = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.off_off[k]); };
+        auto succ = [&](uint32_t k) { return reinterpret_cast<idx_t*>(base + p.lv.succ[k]); };
+        auto len = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.lv.len[k]); };
+        auto off = [&](uint32_t k) { return reinterpret_cast<uint64_t*>(base + p.lv.off[k]); };
         uint64_t tot[FM_KEYS] = {};
         if (int rc = fm_build_occ<idx_t>(be, dB, n, primary, s, l, dIndex, sc, h, tot)) return rc;
         be.sync();
@@ -1546,24 +1565,24 @@ int run_fm_from_bwt(Backend& be, const uint8_t* dB, uint64_t n, uint64_t primary
         idx_t* mrank = reinterpret_cast<idx_t*>(dIndex + l.off_mrank);
         idx_t* samples = reinterpret_cast<idx_t*>(dIndex + l.off_samples);
         auto walk_grid = [](uint64_t walks) { return capped_grid(std::min<uint64_t>((walks + IBWT_Q - 1) / IBWT_Q, 8192), IBWT_NT); };
-        const uint32_t top = p.levels - 1;
-        CAPS_LAUNCH((fm_walk_kernel<idx_t, FMW_LINK0>), walk_grid(p.M[0]), IBWT_NT, be, v, p.M[0], succ(0), len(0), (const uint64_t*)nullptr,
+        const uint32_t top = p.lv.levels - 1;
+        CAPS_LAUNCH((fm_walk_kernel<idx_t, FMW_LINK0>), walk_grid(p.lv.M[0]), IBWT_NT, be, v, p.lv.M[0], succ(0), len(0), (const uint64_t*)nullptr,
                     (uint32_t*)nullptr, (idx_t*)nullptr);
         // the list levels of the inverse BWT as they are (they never touch LF)
         for (uint32_t k = 1; k <= top; ++k)
-            CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_LINK>), walk_grid(p.M[k]), IBWT_NT, be, (const idx_t*)nullptr, n, p.M[k], p.M[k - 1],
+            CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_LINK>), walk_grid(p.lv.M[k]), IBWT_NT, be, (const idx_t*)nullptr, n, p.lv.M[k], p.lv.M[k - 1],
                         (const idx_t*)succ(k - 1), (const uint64_t*)len(k - 1), (uint64_t*)nullptr, succ(k), len(k),
                         (const uint64_t*)nullptr, (const uint64_t*)nullptr, (uint8_t*)nullptr);
-        CAPS_LAUNCH((ibwt_top_kernel<idx_t>), 1, IBWT_NT, be, (const idx_t*)succ(top), (const uint64_t*)len(top), p.M[top], n, off(top), res);
+        CAPS_LAUNCH((ibwt_top_kernel<idx_t>), 1, IBWT_NT, be, (const idx_t*)succ(top), (const uint64_t*)len(top), p.lv.M[top], n, off(top), res);
         uint64_t flag[3] = {0, 0, 0};
         be.d2h(flag, res, sizeof flag);
         be.sync();
         if (flag[0] != 1) return fail(CAPS_SA_EINVAL, not_a_bwt_msg());
         for (uint32_t k = top; k >= 1; --k)
-            CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_PROP>), walk_grid(p.M[k]), IBWT_NT, be, (const idx_t*)nullptr, n, p.M[k], p.M[k - 1],
+            CAPS_LAUNCH((ibwt_walk_kernel<idx_t, IBWT_PROP>), walk_grid(p.lv.M[k]), IBWT_NT, be, (const idx_t*)nullptr, n, p.lv.M[k], p.lv.M[k - 1],
                         (const idx_t*)succ(k - 1), (const uint64_t*)len(k - 1), off(k - 1), (idx_t*)nullptr, (uint64_t*)nullptr,
                         (const uint64_t*)off(k), (const uint64_t*)nullptr, (uint8_t*)nullptr);
-        CAPS_LAUNCH((fm_walk_kernel<idx_t, FMW_MARK>), walk_grid(p.M[0]), IBWT_NT, be, v, p.M[0], (idx_t*)nullptr, len(0), (const uint64_t*)off(0),
+        CAPS_LAUNCH((fm_walk_kernel<idx_t, FMW_MARK>), walk_grid(p.lv.M[0]), IBWT_NT, be, v, p.lv.M[0], (idx_t*)nullptr, len(0), (const uint64_t*)off(0),
                     occ, stage);
         const uint32_t tg = capped_grid(std::min<uint64_t>(n_tiles, 16384), FM_NT);
         CAPS_LAUNCH((fm_mark_kernel<idx_t, true>), tg, FM_NT, be, (const idx_t*)nullptr, n, n_tiles, l.n_blocks, s, occ, mrank, sc.cnt);
@@ -1588,12 +1607,11 @@ int fm_build_from_bwt_device(const void* dB, uint64_t n, uint64_t primary, uint6
     uint64_t need = 0;
     if (int rc = fm_check_from_bwt<idx_t>(dB, n, primary, s, dIndex, index_bytes, &need)) return rc;
     const FmBwtPlan p = fm_bwt_plan<idx_t>(n, (uint32_t)s);
-    if (workspace && workspace_bytes < p.bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_fm_from_bwt_workspace_bytes)");
+    if (int rc = ws_check(workspace, workspace_bytes, p.bytes, "workspace too small (caps_sa_hip_fm_from_bwt_workspace_bytes)", WS_STRICT)) return rc;
     return guarded([&]() -> int {
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);                                    // a null workspace: allocated here, freed on return
-        if (!workspace) workspace = da.get<char>(p.bytes);
-        char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+        char* base = ws_carve(da, workspace, p.bytes);
         return run_fm_from_bwt<idx_t>(be, static_cast<const uint8_t*>(dB), n, primary, (uint32_t)s, static_cast<char*>(dIndex), base, p);
     });
 }
@@ -1610,17 +1628,16 @@ int fm_build_from_bwt_host(const uint8_t* B, uint64_t n, uint64_t primary, uint6
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        hc.fm_host = nullptr;
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        hc.blob_host = nullptr;
         const FmBwtPlan p = fm_bwt_plan<idx_t>(n, (uint32_t)s);
-        const size_t off_B = up(need), off_ws = off_B + up(n ? n : 1), total = off_ws + p.bytes;
-        fm_host_block(hc, be, device, total);
+        const size_t off_B = align_up(need), off_ws = off_B + align_up(n ? n : 1), total = off_ws + p.bytes;
+        host_block(hc, be, device, total);
         uint8_t* dB = reinterpret_cast<uint8_t*>(hc.base + off_B);
         be.h2d(dB, B, n);
         if (int rc = run_fm_from_bwt<idx_t>(be, dB, n, primary, (uint32_t)s, hc.base, hc.base + off_ws, p)) return rc;
         be.d2h(index, hc.base, need);
         be.sync();
-        fm_mark_resident(hc, index, need);
+        blob_mark_resident(hc, index, need);
         return CAPS_SA_OK;
     });
 }
@@ -1644,7 +1661,6 @@ struct FmwLayout {
 };
 inline FmwLayout fmw_layout(uint64_t n, uint64_t sigma, uint32_t s, int idx_bytes)
 {
-    auto up = [](uint64_t b) { return (b + 63) & ~uint64_t(63); };
     const uint64_t rows = idx_bytes == 4 ? 128 : 256;
     FmwLayout l;
     l.Lv = fmw_levels(sigma);
@@ -1654,14 +1670,13 @@ inline FmwLayout fmw_layout(uint64_t n, uint64_t sigma, uint32_t s, int idx_byte
     l.off_lev0 = l.off_tab + FMW_TAB_BYTES;
     l.level_bytes = l.n_blocks * (rows / 2);
     l.off_mrank = l.off_lev0 + l.Lv * l.level_bytes;
-    l.off_samples = l.off_mrank + (s ? up(l.n_blocks * (uint64_t)idx_bytes) : 0);
-    l.total = l.off_samples + (s ? up(l.n_samples * (uint64_t)idx_bytes) : 0);
+    l.off_samples = l.off_mrank + (s ? fm_blob_up(l.n_blocks * (uint64_t)idx_bytes) : 0);
+    l.total = l.off_samples + (s ? fm_blob_up(l.n_samples * (uint64_t)idx_bytes) : 0);
     return l;
 }
 inline int fmw_index_bytes(uint64_t n, uint32_t sigma, uint32_t s, int idx_bytes, uint64_t* bytes)
 {
-    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
-    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
+    if (int rc = check_size_query(n, idx_bytes, bytes, false)) return rc;
     if (s && !fm_sample_ok(s)) return fail(CAPS_SA_EINVAL, "sa_sample must be 0 (no samples) or a power of two in 1 .. 1024");
     if (sigma > 256) return fail(CAPS_SA_EINVAL, "sigma must be 0 (unknown) or 1 .. 256");
     *bytes = fmw_layout(n, sigma ? sigma : 256, s, idx_bytes).total;
@@ -1812,26 +1827,24 @@ constexpr uint32_t FMW_HIST_WGS = 1024;
 struct FmwPlan { size_t off_present, off_cnt, off_total, off_hist, off_a, off_b, bytes; uint64_t n_tiles, cap; uint32_t hist_wgs; };
 template <typename idx_t> FmwPlan fmw_plan(uint64_t n)
 {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     FmwPlan p;
     const uint64_t n_blocks = (n + 1) / FmGeom<idx_t>::ROWS + 1;
     p.n_tiles = (n_blocks * FmGeom<idx_t>::ROWS + FM_TILE - 1) / FM_TILE;
     p.cap = (n + 1 + 63) & ~uint64_t(63);
     p.hist_wgs = (uint32_t)std::min<uint64_t>((n / FM_WROWS + 1 + FM_NT - 1) / FM_NT, FMW_HIST_WGS);
     p.off_present = 0;
-    p.off_cnt = up(8 * sizeof(uint32_t));
-    p.off_total = p.off_cnt + up(FM_KEYS * p.n_tiles * sizeof(uint64_t));
-    p.off_hist = p.off_total + up(256 * sizeof(uint64_t));
-    p.off_a = p.off_hist + up(256ull * p.hist_wgs * sizeof(uint64_t));
-    p.off_b = p.off_a + up(p.cap);
-    p.bytes = p.off_b + up(p.cap) + 256;          // (+ the slack that aligns a caller's pointer)
+    p.off_cnt = align_up(8 * sizeof(uint32_t));
+    p.off_total = p.off_cnt + align_up(FM_KEYS * p.n_tiles * sizeof(uint64_t));
+    p.off_hist = p.off_total + align_up(256 * sizeof(uint64_t));
+    p.off_a = p.off_hist + align_up(256ull * p.hist_wgs * sizeof(uint64_t));
+    p.off_b = p.off_a + align_up(p.cap);
+    p.bytes = p.off_b + align_up(p.cap);
     return p;
 }
 inline int fmw_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
 {
-    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
-    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
-    *bytes = idx_bytes == 4 ? fmw_plan<uint32_t>(n).bytes : fmw_plan<uint64_t>(n).bytes;
+    if (int rc = check_size_query(n, idx_bytes, bytes, false)) return rc;
+    *bytes = ws_reported(idx_bytes == 4 ? fmw_plan<uint32_t>(n).bytes : fmw_plan<uint64_t>(n).bytes);
     return CAPS_SA_OK;
 }
 
@@ -1930,12 +1943,11 @@ int fmw_build_device(const void* dB, uint64_t n, uint64_t primary, const void* d
 {
     if (int rc = fmw_check_build<idx_t>(dB, n, primary, dSA, s, dIndex, index_bytes)) return rc;
     const FmwPlan p = fmw_plan<idx_t>(n);
-    if (workspace && workspace_bytes < p.bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_fm_wide_workspace_bytes)");
+    if (int rc = ws_check(workspace, workspace_bytes, p.bytes, "workspace too small (caps_sa_hip_fm_wide_workspace_bytes)", WS_STRICT)) return rc;
     return guarded([&]() -> int {
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);                                    // a null workspace: allocated here, freed on return
-        if (!workspace) workspace = da.get<char>(p.bytes);
-        char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+        char* base = ws_carve(da, workspace, p.bytes);
         return run_fmw_build<idx_t>(be, static_cast<const uint8_t*>(dB), n, primary, static_cast<const idx_t*>(dSA), (uint32_t)s,
                                     static_cast<char*>(dIndex), index_bytes, base, p, nullptr);
     });
@@ -1952,12 +1964,12 @@ int fmw_build_host(const uint8_t* B, uint64_t n, uint64_t primary, const idx_t* 
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        hc.fm_host = nullptr;
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        hc.blob_host = nullptr;
         const FmwPlan p = fmw_plan<idx_t>(n);
         const uint64_t room = std::min<uint64_t>(index_bytes, fmw_layout(n, 256, SA ? (uint32_t)s : 0u, (int)sizeof(idx_t)).total);
-        const size_t off_B = up(room), off_SA = off_B + up(n ? n : 1), off_ws = off_SA + (SA ? up(n * sizeof(idx_t)) : 0), total = off_ws + p.bytes;
-        fm_host_block(hc, be, device, total);
+        const size_t off_B = align_up(room), off_SA = off_B + align_up(n ? n : 1), off_ws = off_SA + (SA ? align_up(n * sizeof(idx_t)) : 0),
+                     total = off_ws + p.bytes;
+        host_block(hc, be, device, total);
         uint8_t* dB = reinterpret_cast<uint8_t*>(hc.base + off_B);
         idx_t* dSA = SA ? reinterpret_cast<idx_t*>(hc.base + off_SA) : nullptr;
         be.h2d(dB, B, n);
@@ -1966,7 +1978,7 @@ int fmw_build_host(const uint8_t* B, uint64_t n, uint64_t primary, const idx_t* 
         if (int rc = run_fmw_build<idx_t>(be, dB, n, primary, dSA, (uint32_t)s, hc.base, room, hc.base + off_ws, p, &made)) return rc;
         be.d2h(index, hc.base, made);
         be.sync();
-        fm_mark_resident(hc, index, made);
+        blob_mark_resident(hc, index, made);
         return CAPS_SA_OK;
     });
 }
@@ -1982,7 +1994,7 @@ inline int run_fm_count(Backend& be, const void* dIndex, uint64_t index_bytes, c
     FmwView w;
     if (int rc = fm_check_any(be, h, index_bytes, dIndex, v, w)) return rc;
     if (q == 0) return CAPS_SA_OK;
-    uint64_t* words = fm_words(be);
+    uint64_t* words = call_words(be);
     uint32_t* flags = reinterpret_cast<uint32_t*>(words);
     const uint32_t g = capped_grid(std::min<uint64_t>((q + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
     be.memset(words, 0, sizeof(uint64_t));
@@ -2035,7 +2047,7 @@ inline int run_fm_locate(Backend& be, const void* dIndex, uint64_t index_bytes, 
     if (int rc = fm_check_any(be, h, index_bytes, dIndex, v, w)) return rc;
     if (v.s == 0 && v.n) return fail(CAPS_SA_EUNSUPPORTED, "this FM-index was built without SA samples: it can count, not locate");
     if (q == 0) return CAPS_SA_OK;
-    uint64_t* words = fm_words(be);
+    uint64_t* words = call_words(be);
     uint32_t* flags = reinterpret_cast<uint32_t*>(words);
     const uint32_t g = capped_grid(std::min<uint64_t>((q + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
     be.memset(words, 0, sizeof(uint64_t));
@@ -2084,16 +2096,16 @@ inline int fm_locate_device(const void* dIndex, uint64_t index_bytes, const void
 }
 
 // the host forms: the blob at the head of the host-path block (uploaded unless it is the one there already), the query arrays behind it
-inline void fm_upload(HostPathCache& hc, Backend& be, int device, const void* index, uint64_t blob, size_t total)
+inline void blob_upload(HostPathCache& hc, Backend& be, int device, const void* index, uint64_t blob, size_t total)
 {
-    const bool resident = hc.fm_host == index && hc.fm_bytes == blob && hc.device == device && hc.bytes >= total && hc.base &&
-                          std::memcmp(hc.fm_hdr, index, sizeof hc.fm_hdr) == 0 && hc.fm_sum == fm_body_sum(index, blob);
+    const bool resident = hc.blob_host == index && hc.blob_bytes == blob && hc.device == device && hc.bytes >= total && hc.base &&
+                          std::memcmp(hc.blob_hdr, index, sizeof hc.blob_hdr) == 0 && hc.blob_sum == blob_body_sum(index, blob);
     if (resident) return;
-    hc.fm_host = nullptr;
-    fm_host_block(hc, be, device, total);
+    hc.blob_host = nullptr;
+    host_block(hc, be, device, total);
     be.h2d(hc.base, index, blob);
     be.sync();
-    fm_mark_resident(hc, index, blob);
+    blob_mark_resident(hc, index, blob);
 }
 // w: a call that answers wide blobs passes it (w->Lv = 0 for a narrow blob); without it a wide blob is CAPS_SA_EUNSUPPORTED
 inline int fm_host_header(const void* index, uint64_t index_bytes, uint64_t* h, FmView& v, FmwView* w = nullptr)
@@ -2131,10 +2143,10 @@ inline int fm_count_host(const void* index, uint64_t index_bytes, const uint8_t*
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
         const uint64_t blob = fm_blob_bytes(h);
-        const size_t off_pat = up(blob), off_off = off_pat + up(pbytes + 1), off_first = off_off + up((q + 1) * 8), off_count = off_first + up(q * 8);
-        fm_upload(hc, be, device, index, blob, off_count + up(q * 8));
+        const size_t off_pat = align_up(blob), off_off = off_pat + align_up(pbytes + 1), off_first = off_off + align_up((q + 1) * 8),
+                     off_count = off_first + align_up(q * 8);
+        blob_upload(hc, be, device, index, blob, off_count + align_up(q * 8));
         be.h2d(hc.base + off_pat, pat, pbytes);
         be.h2d(hc.base + off_off, patoff, (q + 1) * 8);
         if (int rc = run_fm_count(be, hc.base, blob, h, hc.base + off_pat, hc.base + off_off, q, hc.base + off_first, hc.base + off_count)) return rc;
@@ -2167,10 +2179,10 @@ inline int fm_locate_host(const void* index, uint64_t index_bytes, const uint64_
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
         const uint64_t blob = fm_blob_bytes(h);
-        const size_t off_first = up(blob), off_count = off_first + up(q * 8), off_off = off_count + up(q * 8), off_pos = off_off + up((q + 1) * 8);
-        fm_upload(hc, be, device, index, blob, off_pos + up(o_end * 8 + 8));
+        const size_t off_first = align_up(blob), off_count = off_first + align_up(q * 8), off_off = off_count + align_up(q * 8),
+                     off_pos = off_off + align_up((q + 1) * 8);
+        blob_upload(hc, be, device, index, blob, off_pos + align_up(o_end * 8 + 8));
         be.h2d(hc.base + off_first, first, q * 8);
         be.h2d(hc.base + off_count, count, q * 8);
         be.h2d(hc.base + off_off, outoff, (q + 1) * 8);
@@ -2204,7 +2216,7 @@ inline int run_fm_add_text_samples(Backend& be, char* dIndex, uint64_t capacity,
     uint32_t f = 0;
     if (tl.total > tl.off) be.memset(dIndex + tl.off, 0, tl.total - tl.off);
     if (v.n) {
-        uint64_t* words = fm_words(be);
+        uint64_t* words = call_words(be);
         uint32_t* flags = reinterpret_cast<uint32_t*>(words);
         be.memset(words, 0, sizeof(uint64_t));
         const uint64_t mark_words = v.n_blocks * (W == 4 ? FmGeom<uint32_t>::MWN : FmGeom<uint64_t>::MWN);
@@ -2267,8 +2279,8 @@ inline int fm_add_text_samples_host(void* index, uint64_t index_bytes, uint32_t 
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
         const uint64_t room = std::max<uint64_t>(tl.total, fm_blob_bytes(h));    // (a version-2 blob at a smaller distance is the larger)
-        fm_upload(hc, be, device, index, fm_blob_bytes(h), (size_t)room + 256);
-        hc.fm_host = nullptr;                                // (the block is about to differ from the caller's blob)
+        blob_upload(hc, be, device, index, fm_blob_bytes(h), (size_t)room + WS_ALIGN);
+        hc.blob_host = nullptr;                                // (the block is about to differ from the caller's blob)
         uint64_t out[FM_HDR_WORDS];
         std::memcpy(out, h, sizeof out);
         const int rc = run_fm_add_text_samples(be, hc.base, room, t, h, out);
@@ -2278,18 +2290,19 @@ inline int fm_add_text_samples_host(void* index, uint64_t index_bytes, uint32_t 
         if (rc == CAPS_SA_OK) {
             if (tl.total > tl.off) be.d2h(static_cast<char*>(index) + tl.off, hc.base + tl.off, tl.total - tl.off);
             be.sync();
-            fm_mark_resident(hc, index, tl.total);
+            blob_mark_resident(hc, index, tl.total);
         }
         last_error_ref() = msg;
         return rc;
     });
 }
 
+inline size_t fm_extract_plan_bytes(uint64_t q) { return align_up((q + 1) * sizeof(uint64_t)); }     // the workspace: pre u64[q + 1]
 inline int fm_extract_workspace_bytes(uint64_t q, uint64_t* bytes)
 {
     if (!bytes) return fail(CAPS_SA_EINVAL, "bad argument");
     if (q > (1ull << 56)) return fail(CAPS_SA_EINVAL, "too many queries");
-    *bytes = (((q + 1) * sizeof(uint64_t) + 255) & ~uint64_t(255)) + 256;
+    *bytes = ws_reported(fm_extract_plan_bytes(q));
     return CAPS_SA_OK;
 }
 
@@ -2306,7 +2319,7 @@ inline int run_fm_extract(Backend& be, const void* dIndex, uint64_t index_bytes,
     if (h[FMH_VERSION] != FM_VERSION_TEXT)
         return fail(CAPS_SA_EUNSUPPORTED, "this FM-index has no text-position samples (format version 1): caps_sa_hip_fm_add_text_samples first");
     if (q == 0) return CAPS_SA_OK;
-    uint64_t* words = fm_words(be);
+    uint64_t* words = call_words(be);
     uint32_t* flags = reinterpret_cast<uint32_t*>(words);
     const uint32_t sh = (uint32_t)__builtin_ctz(v.t);
     const uint32_t g = capped_grid(std::min<uint64_t>((q + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
@@ -2349,12 +2362,12 @@ inline int fm_extract_device(const void* dIndex, uint64_t index_bytes, const voi
     if (q && (!dStart || !dOutOff)) return fail(CAPS_SA_EINVAL, "null pointer");
     uint64_t need = 0;
     if (int rc = fm_extract_workspace_bytes(q, &need)) return rc;
-    if (workspace && workspace_bytes < need) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_fm_extract_workspace_bytes)");
+    const size_t layout = fm_extract_plan_bytes(q);
+    if (int rc = ws_check(workspace, workspace_bytes, layout, "workspace too small (caps_sa_hip_fm_extract_workspace_bytes)", WS_STRICT)) return rc;
     return guarded([&]() -> int {
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);                                    // a null workspace: allocated here, freed on return
-        if (!workspace && q) workspace = da.get<char>(need);
-        uint64_t* pre = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+        uint64_t* pre = q ? reinterpret_cast<uint64_t*>(ws_carve(da, workspace, layout)) : nullptr;
         return run_fm_extract(be, dIndex, index_bytes, nullptr, dStart, dOutOff, q, dText, pre);
     });
 }
@@ -2383,10 +2396,9 @@ inline int fm_extract_host(const void* index, uint64_t index_bytes, const uint64
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
         const uint64_t blob = fm_blob_bytes(h);
-        const size_t off_start = up(blob), off_off = off_start + up(q * 8), off_ws = off_off + up((q + 1) * 8), off_text = off_ws + up(ws);
-        fm_upload(hc, be, device, index, blob, off_text + up(o_end + 8));
+        const size_t off_start = align_up(blob), off_off = off_start + align_up(q * 8), off_ws = off_off + align_up((q + 1) * 8), off_text = off_ws + align_up(ws);
+        blob_upload(hc, be, device, index, blob, off_text + align_up(o_end + 8));
         be.h2d(hc.base + off_start, start, q * 8);
         be.h2d(hc.base + off_off, outoff, (q + 1) * 8);
         if (int rc = run_fm_extract(be, hc.base, blob, h, hc.base + off_start, hc.base + off_off, q, hc.base + off_text,
@@ -2405,7 +2417,7 @@ constexpr uint64_t FM_MEM_BYTES = 32;
 // the entry checks of both calls on the caller's device offsets: monotone, no pattern above FM_MAX_PATTERN; -> [o_begin, o_end)
 inline int fm_match_offsets(Backend& be, const void* dPatOff, uint64_t q, uint64_t n, uint64_t& o_begin, uint64_t& o_end)
 {
-    uint64_t* words = fm_words(be);
+    uint64_t* words = call_words(be);
     uint32_t* flags = reinterpret_cast<uint32_t*>(words);
     const uint32_t g = capped_grid(std::min<uint64_t>((q + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
     be.memset(words, 0, sizeof(uint64_t));
@@ -2510,11 +2522,10 @@ inline int fm_match_host(const void* index, uint64_t index_bytes, const uint8_t*
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
         const uint64_t blob = fm_blob_bytes(h);
-        const size_t off_pat = up(blob), off_off = off_pat + up(pbytes + 1), off_len = off_off + up((q + 1) * 8), off_first = off_len + up(total * 4),
-                     off_count = off_first + up(first ? total * 8 : 0);
-        fm_upload(hc, be, device, index, blob, off_count + up(count ? total * 8 : 0));
+        const size_t off_pat = align_up(blob), off_off = off_pat + align_up(pbytes + 1), off_len = off_off + align_up((q + 1) * 8),
+                     off_first = off_len + align_up(total * 4), off_count = off_first + align_up(first ? total * 8 : 0);
+        blob_upload(hc, be, device, index, blob, off_count + align_up(count ? total * 8 : 0));
         be.h2d(hc.base + off_pat, pat, pbytes);
         be.h2d(hc.base + off_off, patoff, (q + 1) * 8);
         if (int rc = run_fm_match(be, hc.base, blob, h, hc.base + off_pat, hc.base + off_off, q, max_len, hc.base + off_len,
@@ -2534,31 +2545,30 @@ constexpr uint64_t FM_MEM_COLS = 1024, FM_MEM_COL_MIN = 1u << 16;
 struct FmMemPlan { size_t off_len, off_first, off_count, off_slot, off_base, bytes; uint64_t cols, per, padded; };
 inline FmMemPlan fm_mem_plan(uint64_t total)
 {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     FmMemPlan p;
     p.cols = std::min<uint64_t>(FM_MEM_COLS, (total + 1 + FM_MEM_COL_MIN - 1) / FM_MEM_COL_MIN);
     p.per = (total + 1 + p.cols - 1) / p.cols;
     p.padded = p.cols * p.per;
     p.off_len = 0;
-    p.off_first = p.off_len + up((total + 1) * 4);
-    p.off_count = p.off_first + up(total * 8);
-    p.off_slot = p.off_count + up(total * 8);
-    p.off_base = p.off_slot + up(p.padded * 8);
-    p.bytes = p.off_base + up(FM_MEM_COLS * 8);
+    p.off_first = p.off_len + align_up((total + 1) * 4);
+    p.off_count = p.off_first + align_up(total * 8);
+    p.off_slot = p.off_count + align_up(total * 8);
+    p.off_base = p.off_slot + align_up(p.padded * 8);
+    p.bytes = p.off_base + align_up(FM_MEM_COLS * 8);
     return p;
 }
 inline int fm_mems_workspace_bytes(uint64_t total, uint64_t q, uint64_t* bytes)
 {
     if (!bytes) return fail(CAPS_SA_EINVAL, "bad argument");
     if (total > (1ull << 56) || q > (1ull << 56)) return fail(CAPS_SA_EINVAL, "too many pattern bytes or patterns");
-    *bytes = fm_mem_plan(total).bytes + 256;
+    *bytes = ws_reported(fm_mem_plan(total).bytes);
     return CAPS_SA_OK;
 }
 
-// MEMs on device arrays.  dMemOff is written whenever the header and the offsets pass (offsets_written); ws: 256-byte aligned, or
-// null: allocated here once the pattern bytes are known.  `hdr` as in run_fm_count.
+// MEMs on device arrays.  dMemOff is written whenever the header and the offsets pass (offsets_written); workspace: the caller's (at
+// any alignment), or null: allocated here once the pattern bytes are known.  `hdr` as in run_fm_count.
 inline int run_fm_mems(Backend& be, DevAllocs& da, const void* dIndex, uint64_t index_bytes, const uint64_t* hdr, const void* dPat, const void* dPatOff,
-                       uint64_t q, uint32_t min_len, void* dMemOff, void* dMems, uint64_t mem_capacity, char* ws, uint64_t ws_bytes,
+                       uint64_t q, uint32_t min_len, void* dMemOff, void* dMems, uint64_t mem_capacity, void* workspace, uint64_t workspace_bytes,
                        bool* offsets_written)
 {
     if (offsets_written) *offsets_written = false;
@@ -2584,14 +2594,14 @@ inline int run_fm_mems(Backend& be, DevAllocs& da, const void* dIndex, uint64_t 
     }
     if (!dPat) return fail(CAPS_SA_EINVAL, "null pointer");
     const FmMemPlan p = fm_mem_plan(total);
-    if (ws && ws_bytes < p.bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_fm_mems_workspace_bytes)");
-    if (!ws) ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(da.get<char>(p.bytes + 256)) + 255) & ~uintptr_t(255));
+    if (int rc = ws_check(workspace, workspace_bytes, p.bytes, "workspace too small (caps_sa_hip_fm_mems_workspace_bytes)")) return rc;
+    char* ws = ws_carve(da, workspace, p.bytes);
     uint32_t* len = reinterpret_cast<uint32_t*>(ws + p.off_len);
     uint64_t* first = reinterpret_cast<uint64_t*>(ws + p.off_first);
     uint64_t* count = reinterpret_cast<uint64_t*>(ws + p.off_count);
     uint64_t* slot = reinterpret_cast<uint64_t*>(ws + p.off_slot);
     uint64_t* colbase = reinterpret_cast<uint64_t*>(ws + p.off_base);
-    uint64_t* words = fm_words(be);
+    uint64_t* words = call_words(be);
     const uint64_t* off = static_cast<const uint64_t*>(dPatOff);
     launch_fm_match(be, v, w, (int)h[FMH_IDX_BYTES], dPat, dPatOff, q, o_begin, o_end, 0u, len, dMems ? first : nullptr, dMems ? count : nullptr);
     const uint32_t g = capped_grid(std::min<uint64_t>((p.padded + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
@@ -2624,14 +2634,8 @@ inline int fm_mems_device(const void* dIndex, uint64_t index_bytes, const void* 
     return guarded([&]() -> int {
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);                                    // a null workspace: allocated here, freed on return
-        char* ws = nullptr;
-        uint64_t ws_bytes = 0;
-        if (workspace) {
-            ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
-            const uint64_t slack = (uint64_t)(ws - static_cast<char*>(workspace));
-            ws_bytes = workspace_bytes > slack ? workspace_bytes - slack : 0;
-        }
-        return run_fm_mems(be, da, dIndex, index_bytes, nullptr, dPat, dPatOff, q, min_len, dMemOff, dMems, mem_capacity, ws, ws_bytes, nullptr);
+        return run_fm_mems(be, da, dIndex, index_bytes, nullptr, dPat, dPatOff, q, min_len, dMemOff, dMems, mem_capacity, workspace, workspace_bytes,
+                           nullptr);
     });
 }
 
@@ -2654,17 +2658,16 @@ inline int fm_mems_host(const void* index, uint64_t index_bytes, const uint8_t* 
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
         DevAllocs da(be);
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
         const uint64_t blob = fm_blob_bytes(h), room = mems ? std::min(mem_capacity, total) : 0;
         const FmMemPlan p = fm_mem_plan(total);
-        const size_t off_pat = up(blob), off_off = off_pat + up(pbytes + 1), off_memoff = off_off + up((q + 1) * 8), off_ws = off_memoff + up((q + 1) * 8),
-                     off_mems = off_ws + up(p.bytes);
-        fm_upload(hc, be, device, index, blob, off_mems + up(room * FM_MEM_BYTES + 8));
+        const size_t off_pat = align_up(blob), off_off = off_pat + align_up(pbytes + 1), off_memoff = off_off + align_up((q + 1) * 8),
+                     off_ws = off_memoff + align_up((q + 1) * 8), off_mems = off_ws + ws_reported(p.bytes);   // (run_fm_mems aligns the workspace)
+        blob_upload(hc, be, device, index, blob, off_mems + align_up(room * FM_MEM_BYTES + 8));
         be.h2d(hc.base + off_pat, pat, pbytes);
         be.h2d(hc.base + off_off, patoff, (q + 1) * 8);
         bool written = false;
         const int rc = run_fm_mems(be, da, hc.base, blob, h, hc.base + off_pat, hc.base + off_off, q, min_len, hc.base + off_memoff,
-                                   mems ? hc.base + off_mems : nullptr, mem_capacity, hc.base + off_ws, p.bytes, &written);
+                                   mems ? hc.base + off_mems : nullptr, mem_capacity, hc.base + off_ws, ws_reported(p.bytes), &written);
         if (written) {
             be.d2h(memoff, hc.base + off_memoff, (q + 1) * 8);
             be.sync();
@@ -2685,24 +2688,21 @@ struct KmerPlan {
 };
 inline KmerPlan kmer_plan(uint64_t n)
 {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     KmerPlan p;
     p.n_tiles = (n + KMER_TILE - 1) / KMER_TILE;
     // a workgroup's LDS bins are 32 bits wide: at most 2^16 tiles (2^30 ranks) each
     p.grid = capped_grid(std::max<uint64_t>(std::min<uint64_t>(p.n_tiles, 1024), (p.n_tiles + 65535) / 65536), FM_NT);
     p.off_next = 0;
-    p.off_cnt = p.off_next + up((p.n_tiles + 1) * 8);
-    p.off_tot = p.off_cnt + up((p.n_tiles + 1) * 8);
-    p.off_hist = p.off_tot + up(2 * KMER_KEYS * 8);
-    p.bytes = p.off_hist + up((size_t)2 * KMER_KEYS * p.grid * 8);
+    p.off_cnt = p.off_next + align_up((p.n_tiles + 1) * 8);
+    p.off_tot = p.off_cnt + align_up((p.n_tiles + 1) * 8);
+    p.off_hist = p.off_tot + align_up(2 * KMER_KEYS * 8);
+    p.bytes = p.off_hist + align_up((size_t)2 * KMER_KEYS * p.grid * 8);
     return p;
 }
 inline int kmer_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
 {
-    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
-    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
-    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
-    *bytes = kmer_plan(n).bytes + 256;
+    if (int rc = check_size_query(n, idx_bytes, bytes)) return rc;
+    *bytes = ws_reported(kmer_plan(n).bytes);
     return CAPS_SA_OK;
 }
 
@@ -2715,35 +2715,15 @@ struct KmerWs {
     uint64_t* tot() const { return reinterpret_cast<uint64_t*>(base + p.off_tot); }
     uint64_t* hist() const { return reinterpret_cast<uint64_t*>(base + p.off_hist); }
 };
-inline char* kmer_align_ws(void* workspace, uint64_t workspace_bytes, uint64_t& usable)
-{
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
-    const uint64_t slack = (uint64_t)(ws - static_cast<char*>(workspace));
-    usable = workspace_bytes > slack ? workspace_bytes - slack : 0;
-    return ws;
-}
-template <typename idx_t> int kmer_check_arrays(const void* SA, const void* LCP, uint64_t n)
-{
-    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
-    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
-    if (n && (!SA || !LCP)) return fail(CAPS_SA_EINVAL, "null pointer");
-    return CAPS_SA_OK;
-}
 inline int kmer_check_ws(void* workspace, uint64_t workspace_bytes, uint64_t n)
 {
-    if (!workspace) return CAPS_SA_OK;
-    uint64_t usable = 0;
-    kmer_align_ws(workspace, workspace_bytes, usable);
-    if (usable < kmer_plan(n).bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_kmer_workspace_bytes)");
-    return CAPS_SA_OK;
+    return ws_check(workspace, workspace_bytes, kmer_plan(n).bytes, "workspace too small (caps_sa_hip_kmer_workspace_bytes)");
 }
-inline KmerWs kmer_ws(Backend& be, DevAllocs& da, void* workspace, uint64_t workspace_bytes, uint64_t n)
+inline KmerWs kmer_ws(DevAllocs& da, void* workspace, uint64_t n)
 {
     KmerWs w;
     w.p = kmer_plan(n);
-    uint64_t usable = 0;
-    if (workspace) w.base = kmer_align_ws(workspace, workspace_bytes, usable);
-    else w.base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(da.get<char>(w.p.bytes + 256)) + 255) & ~uintptr_t(255));
+    w.base = ws_carve(da, workspace, w.p.bytes);
     return w;
 }
 inline int kmer_check_counts(uint64_t k, uint64_t min_count, uint64_t max_count)
@@ -2827,7 +2807,7 @@ template <typename idx_t>
 int kmers_device(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, uint64_t min_count, uint64_t max_count, void* dRec, uint64_t capacity,
                  uint64_t* n_records, void* workspace, uint64_t workspace_bytes, void* stream)
 {
-    if (int rc = kmer_check_arrays<idx_t>(dSA, dLCP, n)) return rc;
+    if (int rc = check_arrays<idx_t>(n, !dSA || !dLCP, "null pointer")) return rc;
     if (!n_records) return fail(CAPS_SA_EINVAL, "null pointer");
     if (int rc = kmer_check_counts(k, min_count, max_count)) return rc;
     if (reinterpret_cast<uintptr_t>(dRec) & 7u) return fail(CAPS_SA_EINVAL, "dRecords must be 8-byte aligned");
@@ -2836,7 +2816,7 @@ int kmers_device(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, uint
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);
         KmerWs w;
-        if (n && k <= n) w = kmer_ws(be, da, workspace, workspace_bytes, n);
+        if (n && k <= n) w = kmer_ws(da, workspace, n);
         return run_kmers<idx_t>(be, static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), n, k, min_count, max_count, dRec, capacity,
                                 n_records, w);
     });
@@ -2845,7 +2825,7 @@ template <typename idx_t>
 int kmer_spectrum_device(const void* dSA, const void* dLCP, uint64_t n, uint64_t k, uint32_t bins, uint64_t* hist, void* workspace,
                          uint64_t workspace_bytes, void* stream)
 {
-    if (int rc = kmer_check_arrays<idx_t>(dSA, dLCP, n)) return rc;
+    if (int rc = check_arrays<idx_t>(n, !dSA || !dLCP, "null pointer")) return rc;
     if (!hist) return fail(CAPS_SA_EINVAL, "null pointer");
     if (k == 0) return fail(CAPS_SA_EINVAL, "k must be at least 1");
     if (bins < 1 || bins > KMER_MAX_BINS) return fail(CAPS_SA_EINVAL, "bins must be in 1 .. 1024");
@@ -2854,7 +2834,7 @@ int kmer_spectrum_device(const void* dSA, const void* dLCP, uint64_t n, uint64_t
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);
         KmerWs w;
-        if (n && k <= n) w = kmer_ws(be, da, workspace, workspace_bytes, n);
+        if (n && k <= n) w = kmer_ws(da, workspace, n);
         return run_kmer_spectrum<idx_t>(be, static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), n, k, bins, hist, w);
     });
 }
@@ -2862,7 +2842,7 @@ template <typename idx_t>
 int kmer_census_device(const void* dSA, const void* dLCP, uint64_t n, uint32_t max_k, uint64_t* distinct, uint64_t* unique, void* workspace,
                        uint64_t workspace_bytes, void* stream)
 {
-    if (int rc = kmer_check_arrays<idx_t>(dSA, dLCP, n)) return rc;
+    if (int rc = check_arrays<idx_t>(n, !dSA || !dLCP, "null pointer")) return rc;
     if (!distinct || !unique) return fail(CAPS_SA_EINVAL, "null pointer");
     if (max_k < 1 || max_k > KMER_MAX_BINS) return fail(CAPS_SA_EINVAL, "max_k must be in 1 .. 1024");
     if (int rc = kmer_check_ws(workspace, workspace_bytes, n)) return rc;
@@ -2870,29 +2850,17 @@ int kmer_census_device(const void* dSA, const void* dLCP, uint64_t n, uint32_t m
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);
         KmerWs w;
-        if (n) w = kmer_ws(be, da, workspace, workspace_bytes, n);
+        if (n) w = kmer_ws(da, workspace, n);
         return run_kmer_census<idx_t>(be, static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), n, max_k, distinct, unique, w);
     });
 }
 
-// host SA / LCP: both up into buffers of the call's own, the device form on them, the records down
-template <typename idx_t> struct KmerHostArrays {
-    idx_t* sa = nullptr;
-    idx_t* lcp = nullptr;
-    KmerHostArrays(Backend& be, DevAllocs& da, const idx_t* SA, const idx_t* LCP, uint64_t n)
-    {
-        if (!n) return;
-        sa = da.get<idx_t>(n);
-        lcp = da.get<idx_t>(n);
-        be.h2d(sa, SA, n * sizeof(idx_t));
-        be.h2d(lcp, LCP, n * sizeof(idx_t));
-    }
-};
+// host SA / LCP: both up into buffers of the call's own (UploadedSaLcp), the device form on them, the records down
 template <typename idx_t>
 int kmers_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint64_t k, uint64_t min_count, uint64_t max_count, void* records, uint64_t capacity,
                uint64_t* n_records, int device)
 {
-    if (int rc = kmer_check_arrays<idx_t>(SA, LCP, n)) return rc;
+    if (int rc = check_arrays<idx_t>(n, !SA || !LCP, "null pointer")) return rc;
     if (!n_records) return fail(CAPS_SA_EINVAL, "null pointer");
     if (int rc = kmer_check_counts(k, min_count, max_count)) return rc;
     if (reinterpret_cast<uintptr_t>(records) & 7u) return fail(CAPS_SA_EINVAL, "records must be 8-byte aligned");
@@ -2902,8 +2870,8 @@ int kmers_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint64_t k, uint64
     return guarded([&]() -> int {
         Backend be(nullptr);
         DevAllocs da(be);
-        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
-        const KmerWs w = kmer_ws(be, da, nullptr, 0, n);
+        UploadedSaLcp<idx_t> a(be, da, SA, LCP, n);
+        const KmerWs w = kmer_ws(da, nullptr, n);
         if (int rc = run_kmers<idx_t>(be, a.sa, a.lcp, n, k, min_count, max_count, nullptr, 0, n_records, w)) return rc;
         if (!records) return CAPS_SA_OK;
         if (*n_records > capacity) return fail(CAPS_SA_EINVAL, "capacity is smaller than the number of k-mers (*n_records; a call with records = NULL counts them)");
@@ -2919,7 +2887,7 @@ int kmers_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint64_t k, uint64
 template <typename idx_t>
 int kmer_spectrum_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint64_t k, uint32_t bins, uint64_t* hist, int device)
 {
-    if (int rc = kmer_check_arrays<idx_t>(SA, LCP, n)) return rc;
+    if (int rc = check_arrays<idx_t>(n, !SA || !LCP, "null pointer")) return rc;
     if (!hist) return fail(CAPS_SA_EINVAL, "null pointer");
     if (k == 0) return fail(CAPS_SA_EINVAL, "k must be at least 1");
     if (bins < 1 || bins > KMER_MAX_BINS) return fail(CAPS_SA_EINVAL, "bins must be in 1 .. 1024");
@@ -2929,14 +2897,14 @@ int kmer_spectrum_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint64_t k
     return guarded([&]() -> int {
         Backend be(nullptr);
         DevAllocs da(be);
-        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
-        return run_kmer_spectrum<idx_t>(be, a.sa, a.lcp, n, k, bins, hist, kmer_ws(be, da, nullptr, 0, n));
+        UploadedSaLcp<idx_t> a(be, da, SA, LCP, n);
+        return run_kmer_spectrum<idx_t>(be, a.sa, a.lcp, n, k, bins, hist, kmer_ws(da, nullptr, n));
     });
 }
 template <typename idx_t>
 int kmer_census_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint32_t max_k, uint64_t* distinct, uint64_t* unique, int device)
 {
-    if (int rc = kmer_check_arrays<idx_t>(SA, LCP, n)) return rc;
+    if (int rc = check_arrays<idx_t>(n, !SA || !LCP, "null pointer")) return rc;
     if (!distinct || !unique) return fail(CAPS_SA_EINVAL, "null pointer");
     if (max_k < 1 || max_k > KMER_MAX_BINS) return fail(CAPS_SA_EINVAL, "max_k must be in 1 .. 1024");
     if (n == 0) {
@@ -2949,8 +2917,8 @@ int kmer_census_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint32_t max
     return guarded([&]() -> int {
         Backend be(nullptr);
         DevAllocs da(be);
-        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
-        return run_kmer_census<idx_t>(be, a.sa, a.lcp, n, max_k, distinct, unique, kmer_ws(be, da, nullptr, 0, n));
+        UploadedSaLcp<idx_t> a(be, da, SA, LCP, n);
+        return run_kmer_census<idx_t>(be, a.sa, a.lcp, n, max_k, distinct, unique, kmer_ws(da, nullptr, n));
     });
 }
 
@@ -2964,11 +2932,10 @@ struct CollPlan {
 };
 inline CollPlan coll_plan(uint64_t n)
 {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     CollPlan p;
     p.n_tiles = (n + KMER_TILE - 1) / KMER_TILE;
     p.grid = capped_grid(std::min<uint64_t>(p.n_tiles, 1024), FM_NT);     // (the kernel flushes its 32-bit counters itself)
-    const size_t col = up((p.n_tiles + 1) * 8);
+    const size_t col = align_up((p.n_tiles + 1) * 8);
     p.off_next = 0;
     p.off_cnt = p.off_next + col;
     p.off_pd = p.off_cnt + col;
@@ -2976,17 +2943,15 @@ inline CollPlan coll_plan(uint64_t n)
     p.off_cd = p.off_po + col;
     p.off_co = p.off_cd + col;
     p.off_tab = p.off_co + col;
-    p.off_tot = p.off_tab + up(2 * CK_MAX_DOCS * 8);
-    p.off_hist = p.off_tot + up((size_t)CK_COLS * 8);
-    p.bytes = p.off_hist + up((size_t)CK_COLS * p.grid * 8);
+    p.off_tot = p.off_tab + align_up(2 * CK_MAX_DOCS * 8);
+    p.off_hist = p.off_tot + align_up((size_t)CK_COLS * 8);
+    p.bytes = p.off_hist + align_up((size_t)CK_COLS * p.grid * 8);
     return p;
 }
 inline int coll_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
 {
-    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
-    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
-    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
-    *bytes = coll_plan(n).bytes + 256;
+    if (int rc = check_size_query(n, idx_bytes, bytes)) return rc;
+    *bytes = ws_reported(coll_plan(n).bytes);
     return CAPS_SA_OK;
 }
 struct CollWs {
@@ -2994,13 +2959,11 @@ struct CollWs {
     CollPlan p;
     uint64_t* at(size_t off) const { return reinterpret_cast<uint64_t*>(base + off); }
 };
-inline CollWs coll_ws(DevAllocs& da, void* workspace, uint64_t workspace_bytes, uint64_t n)
+inline CollWs coll_ws(DevAllocs& da, void* workspace, uint64_t n)
 {
     CollWs w;
     w.p = coll_plan(n);
-    uint64_t usable = 0;
-    if (workspace) w.base = kmer_align_ws(workspace, workspace_bytes, usable);
-    else w.base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(da.get<char>(w.p.bytes + 256)) + 255) & ~uintptr_t(255));
+    w.base = ws_carve(da, workspace, w.p.bytes);
     return w;
 }
 struct CollDocs { const uint64_t* start; const uint64_t* len; uint32_t m; };
@@ -3009,7 +2972,7 @@ struct CollDocs { const uint64_t* start; const uint64_t* len; uint32_t m; };
 template <typename idx_t>
 int coll_check(const void* SA, const void* LCP, uint64_t n, uint64_t k, const CollDocs& dc, void* workspace, uint64_t workspace_bytes)
 {
-    if (int rc = kmer_check_arrays<idx_t>(SA, LCP, n)) return rc;
+    if (int rc = check_arrays<idx_t>(n, !SA || !LCP, "null pointer")) return rc;
     if (k == 0) return fail(CAPS_SA_EINVAL, "k must be at least 1");
     if (dc.m < 1 || dc.m > CK_MAX_DOCS) return fail(CAPS_SA_EINVAL, "m must be in 1 .. 64");
     if (!dc.start || !dc.len) return fail(CAPS_SA_EINVAL, "null pointer");
@@ -3019,12 +2982,7 @@ int coll_check(const void* SA, const void* LCP, uint64_t n, uint64_t k, const Co
         if (dc.start[d] < prev_end) return fail(CAPS_SA_EINVAL, "the documents must be ascending and disjoint");
         prev_end = dc.start[d] + dc.len[d];
     }
-    if (workspace) {
-        uint64_t usable = 0;
-        kmer_align_ws(workspace, workspace_bytes, usable);
-        if (usable < coll_plan(n).bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_coll_workspace_bytes)");
-    }
-    return CAPS_SA_OK;
+    return ws_check(workspace, workspace_bytes, coll_plan(n).bytes, "workspace too small (caps_sa_hip_coll_workspace_bytes)");
 }
 inline int coll_check_filter(const CollDocs& dc, const CkFilter& q)
 {
@@ -3122,7 +3080,7 @@ int coll_kmers_device(const void* dSA, const void* dLCP, uint64_t n, uint64_t k,
     return guarded([&]() -> int {
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);
-        const CollWs w = coll_ws(da, workspace, workspace_bytes, n);
+        const CollWs w = coll_ws(da, workspace, n);
         const idx_t* sa = static_cast<const idx_t*>(dSA);
         const idx_t* lcp = static_cast<const idx_t*>(dLCP);
         CollTable tab;
@@ -3143,7 +3101,7 @@ int coll_sharing_device(const void* dSA, const void* dLCP, uint64_t n, uint64_t 
     return guarded([&]() -> int {
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);
-        const CollWs w = coll_ws(da, workspace, workspace_bytes, n);
+        const CollWs w = coll_ws(da, workspace, n);
         run_coll_sharing<idx_t>(be, static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), n, k, dc, freq, shared, w);
         return CAPS_SA_OK;
     });
@@ -3165,8 +3123,8 @@ int coll_kmers_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint64_t k, c
     return guarded([&]() -> int {
         Backend be(nullptr);
         DevAllocs da(be);
-        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
-        const CollWs w = coll_ws(da, nullptr, 0, n);
+        UploadedSaLcp<idx_t> a(be, da, SA, LCP, n);
+        const CollWs w = coll_ws(da, nullptr, n);
         CollTable tab;
         run_coll_count<idx_t>(be, a.sa, a.lcp, n, k, dc, tab, q, n_records, w);
         if (!records) return CAPS_SA_OK;
@@ -3191,8 +3149,8 @@ int coll_sharing_host(const idx_t* SA, const idx_t* LCP, uint64_t n, uint64_t k,
     return guarded([&]() -> int {
         Backend be(nullptr);
         DevAllocs da(be);
-        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
-        run_coll_sharing<idx_t>(be, a.sa, a.lcp, n, k, dc, freq, shared, coll_ws(da, nullptr, 0, n));
+        UploadedSaLcp<idx_t> a(be, da, SA, LCP, n);
+        run_coll_sharing<idx_t>(be, a.sa, a.lcp, n, k, dc, freq, shared, coll_ws(da, nullptr, n));
         return CAPS_SA_OK;
     });
 }
@@ -3206,23 +3164,20 @@ struct CrossPlan {
 };
 inline CrossPlan cross_plan(uint64_t n)
 {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     CrossPlan p;
     p.n_tiles = (n + XM_TILE - 1) / XM_TILE;
     p.grid = capped_grid(std::min<uint64_t>(p.n_tiles, 8192), FM_NT);
     p.off_cnt = 0;
-    p.off_tot = p.off_cnt + up((XM_KEYS * p.n_tiles + 1) * 8);
-    p.off_lcs = p.off_tot + up(XM_KEYS * 8);
-    p.off_out = p.off_lcs + up((size_t)2 * p.grid * 8);
-    p.bytes = p.off_out + up(8 * 8);
+    p.off_tot = p.off_cnt + align_up((XM_KEYS * p.n_tiles + 1) * 8);
+    p.off_lcs = p.off_tot + align_up(XM_KEYS * 8);
+    p.off_out = p.off_lcs + align_up((size_t)2 * p.grid * 8);
+    p.bytes = p.off_out + align_up(8 * 8);
     return p;
 }
 inline int cross_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
 {
-    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
-    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
-    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
-    *bytes = cross_plan(n).bytes + 256;
+    if (int rc = check_size_query(n, idx_bytes, bytes)) return rc;
+    *bytes = ws_reported(cross_plan(n).bytes);
     return CAPS_SA_OK;
 }
 struct CrossWs {
@@ -3233,13 +3188,11 @@ struct CrossWs {
     uint64_t* lcs() const { return reinterpret_cast<uint64_t*>(base + p.off_lcs); }
     uint64_t* out() const { return reinterpret_cast<uint64_t*>(base + p.off_out); }
 };
-inline CrossWs cross_ws(DevAllocs& da, void* workspace, uint64_t workspace_bytes, uint64_t n)
+inline CrossWs cross_ws(DevAllocs& da, void* workspace, uint64_t n)
 {
     CrossWs w;
     w.p = cross_plan(n);
-    uint64_t usable = 0;
-    if (workspace) w.base = kmer_align_ws(workspace, workspace_bytes, usable);
-    else w.base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(da.get<char>(w.p.bytes + 256)) + 255) & ~uintptr_t(255));
+    w.base = ws_carve(da, workspace, w.p.bytes);
     return w;
 }
 // every refusal that needs no device; max_occ = 0 is MUM mode
@@ -3247,20 +3200,13 @@ template <typename idx_t>
 int cross_check(const void* SA, const void* LCP, const void* BWT, uint64_t n, uint64_t split, uint64_t min_len, bool mems, uint32_t max_occ,
                 const void* records, const uint64_t* summary, void* workspace, uint64_t workspace_bytes)
 {
-    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
-    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
-    if (n && (!SA || !LCP || !BWT)) return fail(CAPS_SA_EINVAL, "null pointer");
+    if (int rc = check_arrays<idx_t>(n, !SA || !LCP || !BWT, "null pointer")) return rc;
     if (!summary) return fail(CAPS_SA_EINVAL, "null pointer");
     if (min_len == 0) return fail(CAPS_SA_EINVAL, "min_len must be at least 1");
     if (split > n) return fail(CAPS_SA_EINVAL, "split is beyond the text (split <= n)");
     if (mems && (max_occ < 2 || max_occ > XM_MAX_OCC)) return fail(CAPS_SA_EINVAL, "max_occ must be in 2 .. 64");
     if (reinterpret_cast<uintptr_t>(records) & 7u) return fail(CAPS_SA_EINVAL, "the records must be 8-byte aligned");
-    if (workspace) {
-        uint64_t usable = 0;
-        kmer_align_ws(workspace, workspace_bytes, usable);
-        if (usable < cross_plan(n).bytes) return fail(CAPS_SA_EINVAL, "workspace too small (caps_sa_hip_cross_workspace_bytes)");
-    }
-    return CAPS_SA_OK;
+    return ws_check(workspace, workspace_bytes, cross_plan(n).bytes, "workspace too small (caps_sa_hip_cross_workspace_bytes)");
 }
 
 // the counting pass: the 8 summary words (n >= 1)
@@ -3305,7 +3251,7 @@ int cross_device(const void* dSA, const void* dLCP, const void* dBWT, uint64_t n
     return guarded([&]() -> int {
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);
-        const CrossWs w = cross_ws(da, workspace, workspace_bytes, n);
+        const CrossWs w = cross_ws(da, workspace, n);
         const idx_t* sa = static_cast<const idx_t*>(dSA);
         const idx_t* lcp = static_cast<const idx_t*>(dLCP);
         const uint8_t* bwt = static_cast<const uint8_t*>(dBWT);
@@ -3330,10 +3276,10 @@ int cross_host(const idx_t* SA, const idx_t* LCP, const uint8_t* BWT, uint64_t n
     return guarded([&]() -> int {
         Backend be(nullptr);
         DevAllocs da(be);
-        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
+        UploadedSaLcp<idx_t> a(be, da, SA, LCP, n);
         uint8_t* bwt = da.get<uint8_t>(n);
         be.h2d(bwt, BWT, n);
-        const CrossWs w = cross_ws(da, nullptr, 0, n);
+        const CrossWs w = cross_ws(da, nullptr, n);
         run_cross_count<idx_t>(be, a.sa, a.lcp, bwt, n, split, min_len, max_occ, summary, w);
         if (!records) return CAPS_SA_OK;
         if (summary[0] > capacity) return fail(CAPS_SA_EINVAL, cross_capacity_msg());
@@ -3357,7 +3303,6 @@ struct LpfPlan {
 };
 inline LpfPlan lpf_plan(uint64_t n, size_t w)
 {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     LpfPlan p;
     p.n_tiles = (n + LPF_TILE - 1) / LPF_TILE;
     uint64_t cnt = n;
@@ -3369,10 +3314,10 @@ inline LpfPlan lpf_plan(uint64_t n, size_t w)
         p.nodes += cnt;
     } while (cnt > 1 && p.top + 1 < LPF_MAX_LEVELS);
     p.off_tab = 0;
-    p.off_bad = up(sizeof(p.tab));
-    p.off_sa = p.off_bad + 256;
-    p.off_lcp = p.off_sa + up(p.nodes * w);
-    p.bytes = p.off_lcp + up(p.nodes * w);
+    p.off_bad = align_up(sizeof(p.tab));
+    p.off_sa = p.off_bad + WS_ALIGN;
+    p.off_lcp = p.off_sa + align_up(p.nodes * w);
+    p.bytes = p.off_lcp + align_up(p.nodes * w);
     return p;
 }
 // lz77 workspace: ex[n] | gx[n_groups * LZ_SPEC] (index width) | gentry[n_groups] | entry[n_tiles] | cnt[n_tiles + 1] | total, 64-bit words
@@ -3382,60 +3327,28 @@ struct LzPlan {
 };
 inline LzPlan lz_plan(uint64_t n, size_t w)
 {
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     LzPlan p;
     p.n_tiles = (n + LZ_TILE - 1) / LZ_TILE;
     p.n_groups = (n + LZ_GPOS - 1) / LZ_GPOS;
     p.off_ex = 0;
-    p.off_gx = up(n * w);
-    p.off_gentry = p.off_gx + up(p.n_groups * LZ_SPEC * w);
-    p.off_entry = p.off_gentry + up(p.n_groups * 8);
-    p.off_cnt = p.off_entry + up(p.n_tiles * 8);
-    p.off_tot = p.off_cnt + up((p.n_tiles + 1) * 8);
-    p.bytes = p.off_tot + 256;
+    p.off_gx = align_up(n * w);
+    p.off_gentry = p.off_gx + align_up(p.n_groups * LZ_SPEC * w);
+    p.off_entry = p.off_gentry + align_up(p.n_groups * 8);
+    p.off_cnt = p.off_entry + align_up(p.n_tiles * 8);
+    p.off_tot = p.off_cnt + align_up((p.n_tiles + 1) * 8);
+    p.bytes = p.off_tot + WS_ALIGN;
     return p;
-}
-inline int lz_ws_args(uint64_t n, int idx_bytes, uint64_t* bytes)
-{
-    if (!bytes || (idx_bytes != 4 && idx_bytes != 8)) return fail(CAPS_SA_EINVAL, "bad argument");
-    if (idx_bytes == 4 && n > 0xFFFFFFFFull) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use idx_bytes = 8)");
-    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
-    return CAPS_SA_OK;
 }
 inline int lpf_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
 {
-    if (int rc = lz_ws_args(n, idx_bytes, bytes)) return rc;
-    *bytes = lpf_plan(n, (size_t)idx_bytes).bytes + 256;
+    if (int rc = check_size_query(n, idx_bytes, bytes)) return rc;
+    *bytes = ws_reported(lpf_plan(n, (size_t)idx_bytes).bytes);
     return CAPS_SA_OK;
 }
 inline int lz77_workspace_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
 {
-    if (int rc = lz_ws_args(n, idx_bytes, bytes)) return rc;
-    *bytes = lz_plan(n, (size_t)idx_bytes).bytes + 256;
-    return CAPS_SA_OK;
-}
-// the caller's workspace aligned up (null: one of the call's own); `need` was checked by lz_check_ws before
-inline int lz_check_ws(void* workspace, uint64_t workspace_bytes, size_t need, const char* which)
-{
-    if (!workspace) return CAPS_SA_OK;
-    uint64_t usable = 0;
-    kmer_align_ws(workspace, workspace_bytes, usable);
-    if (usable < need) return fail(CAPS_SA_EINVAL, which);
-    return CAPS_SA_OK;
-}
-inline char* lz_ws(DevAllocs& da, void* workspace, uint64_t workspace_bytes, size_t need)
-{
-    uint64_t usable = 0;
-    if (workspace) return kmer_align_ws(workspace, workspace_bytes, usable);
-    return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(da.get<char>(need + 256)) + 255) & ~uintptr_t(255));
-}
-
-// kmer_check_arrays' checks with messages that name this call's arrays
-template <typename idx_t> int lz_check_arrays(const void* a, const void* b, uint64_t n, const char* null_msg)
-{
-    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
-    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
-    if (n && (!a || !b)) return fail(CAPS_SA_EINVAL, null_msg);
+    if (int rc = check_size_query(n, idx_bytes, bytes)) return rc;
+    *bytes = ws_reported(lz_plan(n, (size_t)idx_bytes).bytes);
     return CAPS_SA_OK;
 }
 
@@ -3506,14 +3419,14 @@ int run_lz77(Backend& be, const idx_t* dLPF, const idx_t* dPrev, uint64_t n, voi
 template <typename idx_t>
 int lpf_device(const void* dSA, const void* dLCP, uint64_t n, void* dLPF, void* dPrev, void* workspace, uint64_t workspace_bytes, void* stream)
 {
-    if (int rc = lz_check_arrays<idx_t>(dSA, dLCP, n, "dSA or dLCP is null")) return rc;
+    if (int rc = check_arrays<idx_t>(n, !dSA || !dLCP, "dSA or dLCP is null")) return rc;
     if (n && !dLPF && !dPrev) return fail(CAPS_SA_EINVAL, "dLPF and dPrev are both null");
-    if (int rc = lz_check_ws(workspace, workspace_bytes, lpf_plan(n, sizeof(idx_t)).bytes, "workspace too small (caps_sa_hip_lpf_workspace_bytes)")) return rc;
+    if (int rc = ws_check(workspace, workspace_bytes, lpf_plan(n, sizeof(idx_t)).bytes, "workspace too small (caps_sa_hip_lpf_workspace_bytes)")) return rc;
     if (n == 0) return CAPS_SA_OK;
     return guarded([&]() -> int {
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);
-        char* ws = lz_ws(da, workspace, workspace_bytes, lpf_plan(n, sizeof(idx_t)).bytes);
+        char* ws = ws_carve(da, workspace, lpf_plan(n, sizeof(idx_t)).bytes);
         return run_lpf<idx_t>(be, static_cast<const idx_t*>(dSA), static_cast<const idx_t*>(dLCP), n, static_cast<idx_t*>(dLPF),
                               static_cast<idx_t*>(dPrev), ws);
     });
@@ -3522,22 +3435,22 @@ template <typename idx_t>
 int lz77_device(const void* dLPF, const void* dPrev, uint64_t n, void* dRec, uint64_t capacity, uint64_t* n_phrases, void* workspace,
                 uint64_t workspace_bytes, void* stream)
 {
-    if (int rc = lz_check_arrays<idx_t>(dLPF, dPrev, n, "dLPF or dPrev is null")) return rc;
+    if (int rc = check_arrays<idx_t>(n, !dLPF || !dPrev, "dLPF or dPrev is null")) return rc;
     if (!n_phrases) return fail(CAPS_SA_EINVAL, "n_phrases is null");
     if (reinterpret_cast<uintptr_t>(dRec) & 7u) return fail(CAPS_SA_EINVAL, "dRecords must be 8-byte aligned");
-    if (int rc = lz_check_ws(workspace, workspace_bytes, lz_plan(n, sizeof(idx_t)).bytes, "workspace too small (caps_sa_hip_lz77_workspace_bytes)")) return rc;
+    if (int rc = ws_check(workspace, workspace_bytes, lz_plan(n, sizeof(idx_t)).bytes, "workspace too small (caps_sa_hip_lz77_workspace_bytes)")) return rc;
     if (n == 0) { *n_phrases = 0; return CAPS_SA_OK; }
     return guarded([&]() -> int {
         Backend be(static_cast<decltype(Backend::stream)>(stream));
         DevAllocs da(be);
-        char* ws = lz_ws(da, workspace, workspace_bytes, lz_plan(n, sizeof(idx_t)).bytes);
+        char* ws = ws_carve(da, workspace, lz_plan(n, sizeof(idx_t)).bytes);
         return run_lz77<idx_t>(be, static_cast<const idx_t*>(dLPF), static_cast<const idx_t*>(dPrev), n, dRec, capacity, n_phrases, ws);
     });
 }
 template <typename idx_t>
 int lpf_host(const idx_t* SA, const idx_t* LCP, uint64_t n, idx_t* LPF, idx_t* Prev, int device)
 {
-    if (int rc = lz_check_arrays<idx_t>(SA, LCP, n, "SA or LCP is null")) return rc;
+    if (int rc = check_arrays<idx_t>(n, !SA || !LCP, "SA or LCP is null")) return rc;
     if (n && !LPF && !Prev) return fail(CAPS_SA_EINVAL, "LPF and Prev are both null");
     if (n == 0) return CAPS_SA_OK;
     DeviceScope restore_device_;
@@ -3545,13 +3458,13 @@ int lpf_host(const idx_t* SA, const idx_t* LCP, uint64_t n, idx_t* LPF, idx_t* P
     return guarded([&]() -> int {
         Backend be(nullptr);
         DevAllocs da(be);
-        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
+        UploadedSaLcp<idx_t> a(be, da, SA, LCP, n);
         idx_t* dLPF = LPF ? da.get<idx_t>(n) : nullptr;
         idx_t* dPrev = Prev ? da.get<idx_t>(n) : nullptr;
         // slots whose position never occurs in SA keep what they held
         if (LPF) be.h2d(dLPF, LPF, n * sizeof(idx_t));
         if (Prev) be.h2d(dPrev, Prev, n * sizeof(idx_t));
-        char* ws = lz_ws(da, nullptr, 0, lpf_plan(n, sizeof(idx_t)).bytes);
+        char* ws = ws_carve(da, nullptr, lpf_plan(n, sizeof(idx_t)).bytes);
         const int rc = run_lpf<idx_t>(be, a.sa, a.lcp, n, dLPF, dPrev, ws);
         if (LPF) be.d2h(LPF, dLPF, n * sizeof(idx_t));
         if (Prev) be.d2h(Prev, dPrev, n * sizeof(idx_t));
@@ -3562,7 +3475,7 @@ int lpf_host(const idx_t* SA, const idx_t* LCP, uint64_t n, idx_t* LPF, idx_t* P
 template <typename idx_t>
 int lz77_host(const idx_t* SA, const idx_t* LCP, uint64_t n, void* records, uint64_t capacity, uint64_t* n_phrases, int device)
 {
-    if (int rc = lz_check_arrays<idx_t>(SA, LCP, n, "SA or LCP is null")) return rc;
+    if (int rc = check_arrays<idx_t>(n, !SA || !LCP, "SA or LCP is null")) return rc;
     if (!n_phrases) return fail(CAPS_SA_EINVAL, "n_phrases is null");
     if (reinterpret_cast<uintptr_t>(records) & 7u) return fail(CAPS_SA_EINVAL, "records must be 8-byte aligned");
     if (n == 0) { *n_phrases = 0; return CAPS_SA_OK; }
@@ -3571,12 +3484,12 @@ int lz77_host(const idx_t* SA, const idx_t* LCP, uint64_t n, void* records, uint
     return guarded([&]() -> int {
         Backend be(nullptr);
         DevAllocs da(be);
-        KmerHostArrays<idx_t> a(be, da, SA, LCP, n);
+        UploadedSaLcp<idx_t> a(be, da, SA, LCP, n);
         idx_t* dLPF = da.get<idx_t>(n);
         idx_t* dPrev = da.get<idx_t>(n);
         be.memset(dLPF, 0, n * sizeof(idx_t));              // a position that SA never names parses as a literal
         be.memset(dPrev, 0xFF, n * sizeof(idx_t));
-        char* ws = lz_ws(da, nullptr, 0, std::max(lpf_plan(n, sizeof(idx_t)).bytes, lz_plan(n, sizeof(idx_t)).bytes));
+        char* ws = ws_carve(da, nullptr, std::max(lpf_plan(n, sizeof(idx_t)).bytes, lz_plan(n, sizeof(idx_t)).bytes));
         if (int rc = run_lpf<idx_t>(be, a.sa, a.lcp, n, dLPF, dPrev, ws)) return rc;
         if (int rc = run_lz77<idx_t>(be, dLPF, dPrev, n, nullptr, 0, n_phrases, ws)) return rc;
         if (!records) return CAPS_SA_OK;
@@ -3596,7 +3509,7 @@ int lz77_host(const idx_t* SA, const idx_t* LCP, uint64_t n, void* records, uint
 constexpr uint64_t LCE_MAGIC = 0x3145434C53504143ull;     // "CAPSLCE1"
 constexpr uint64_t LCE_VERSION = 1;
 constexpr uint32_t LCE_HDR_WORDS = 32;
-static_assert(LCE_HDR_WORDS == FM_HDR_WORDS, "fm_mark_resident keeps a header of this size and sums the body behind it");
+static_assert(LCE_HDR_WORDS == FM_HDR_WORDS, "blob_mark_resident keeps a header of this size and sums the body behind it");
 enum { LCEH_MAGIC = 0, LCEH_VERSION, LCEH_N, LCEH_IDX_BYTES, LCEH_BLOCK, LCEH_SUPER, LCEH_NB, LCEH_NS, LCEH_TLEVELS, LCEH_OFF_ISA, LCEH_OFF_LCP,
        LCEH_OFF_M, LCEH_M_STRIDE, LCEH_OFF_T, LCEH_T_STRIDE, LCEH_TOTAL };
 
@@ -3605,17 +3518,16 @@ struct LceLayout {
 };
 inline LceLayout lce_layout(uint64_t n, uint64_t w)
 {
-    auto up = [](uint64_t b) { return (b + 255) & ~uint64_t(255); };
     LceLayout l;
     l.nb = (n + LCE_BLOCK - 1) / LCE_BLOCK;
     l.ns = (n + LCE_SUPER - 1) / LCE_SUPER;
     l.tlevels = l.ns ? 64u - (uint64_t)caps_clz64(l.ns) : 0;          // floor(log2 ns) + 1
     l.off_isa = LCE_HDR_WORDS * sizeof(uint64_t);
-    l.off_lcp = l.off_isa + up(n * w);
-    l.off_m = l.off_lcp + up(n * w);
-    l.m_stride = up(l.nb * w);
+    l.off_lcp = l.off_isa + align_up(n * w);
+    l.off_m = l.off_lcp + align_up(n * w);
+    l.m_stride = align_up(l.nb * w);
     l.off_t = l.off_m + LCE_MLEVELS * l.m_stride;
-    l.t_stride = up(l.ns * w);
+    l.t_stride = align_up(l.ns * w);
     l.total = l.off_t + l.tlevels * l.t_stride;
     return l;
 }
@@ -3630,7 +3542,7 @@ inline void lce_header(uint64_t* h, uint64_t n, uint64_t w)
 }
 inline int lce_index_bytes(uint64_t n, int idx_bytes, uint64_t* bytes)
 {
-    if (int rc = lz_ws_args(n, idx_bytes, bytes)) return rc;
+    if (int rc = check_size_query(n, idx_bytes, bytes)) return rc;
     *bytes = lce_layout(n, (uint64_t)idx_bytes).total;
     return CAPS_SA_OK;
 }
@@ -3688,14 +3600,14 @@ template <typename idx_t> int run_lce_build(Backend& be, const idx_t* dSA, const
     be.h2d(dIndex, h, sizeof h);
     if (n == 0) { be.sync(); return CAPS_SA_OK; }
     auto pad = [&](uint64_t off, uint64_t bytes) {                  // the section's padding is zero: equal inputs, equal blobs
-        const uint64_t end = (bytes + 255) & ~uint64_t(255);
+        const uint64_t end = align_up(bytes);
         if (end > bytes) be.memset(dIndex + off + bytes, 0, end - bytes);
     };
     pad(l.off_isa, n * w);
     pad(l.off_lcp, n * w);
     for (uint64_t j = 0; j < LCE_MLEVELS; ++j) pad(l.off_m + j * l.m_stride, l.nb * w);
     for (uint64_t j = 0; j < l.tlevels; ++j) pad(l.off_t + j * l.t_stride, l.ns * w);
-    uint32_t* flags = reinterpret_cast<uint32_t*>(fm_words(be));
+    uint32_t* flags = reinterpret_cast<uint32_t*>(call_words(be));
     if (int rc = run_isa<idx_t>(be, dSA, n, reinterpret_cast<idx_t*>(dIndex + l.off_isa), flags)) { be.sync(); return rc; }
     auto M = [&](uint64_t j) { return reinterpret_cast<idx_t*>(dIndex + l.off_m + j * l.m_stride); };
     auto T = [&](uint64_t j) { return reinterpret_cast<idx_t*>(dIndex + l.off_t + j * l.t_stride); };
@@ -3713,10 +3625,7 @@ template <typename idx_t> int run_lce_build(Backend& be, const idx_t* dSA, const
 
 template <typename idx_t> int isa_check_args(const void* SA, uint64_t n, const void* ISA)
 {
-    if (n > (uint64_t)std::numeric_limits<idx_t>::max()) return fail(CAPS_SA_EINVAL, "n does not fit 32-bit indices (use the _u64 entry point)");
-    if (n > (1ull << 60)) return fail(CAPS_SA_EINVAL, "n is too large");
-    if (n && (!SA || !ISA)) return fail(CAPS_SA_EINVAL, "SA or ISA is null");
-    return CAPS_SA_OK;
+    return check_arrays<idx_t>(n, !SA || !ISA, "SA or ISA is null");
 }
 template <typename idx_t> int isa_device(const void* dSA, uint64_t n, void* dISA, void* stream)
 {
@@ -3724,7 +3633,7 @@ template <typename idx_t> int isa_device(const void* dSA, uint64_t n, void* dISA
     if (n == 0) return CAPS_SA_OK;
     return guarded([&]() -> int {
         Backend be(static_cast<decltype(Backend::stream)>(stream));
-        return run_isa<idx_t>(be, static_cast<const idx_t*>(dSA), n, static_cast<idx_t*>(dISA), reinterpret_cast<uint32_t*>(fm_words(be)));
+        return run_isa<idx_t>(be, static_cast<const idx_t*>(dSA), n, static_cast<idx_t*>(dISA), reinterpret_cast<uint32_t*>(call_words(be)));
     });
 }
 template <typename idx_t> int isa_host(const idx_t* SA, uint64_t n, idx_t* ISA, int device)
@@ -3737,14 +3646,13 @@ template <typename idx_t> int isa_host(const idx_t* SA, uint64_t n, idx_t* ISA, 
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        hc.fm_host = nullptr;
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-        const size_t off_isa = up(n * sizeof(idx_t));
-        fm_host_block(hc, be, device, off_isa + up(n * sizeof(idx_t)));
+        hc.blob_host = nullptr;
+        const size_t off_isa = align_up(n * sizeof(idx_t));
+        host_block(hc, be, device, off_isa + align_up(n * sizeof(idx_t)));
         idx_t* dSA = reinterpret_cast<idx_t*>(hc.base);
         idx_t* dISA = reinterpret_cast<idx_t*>(hc.base + off_isa);
         be.h2d(dSA, SA, n * sizeof(idx_t));
-        if (int rc = run_isa<idx_t>(be, dSA, n, dISA, reinterpret_cast<uint32_t*>(fm_words(be)))) return rc;      // ISA is not written
+        if (int rc = run_isa<idx_t>(be, dSA, n, dISA, reinterpret_cast<uint32_t*>(call_words(be)))) return rc;      // ISA is not written
         be.d2h(ISA, dISA, n * sizeof(idx_t));
         be.sync();
         return CAPS_SA_OK;
@@ -3753,7 +3661,7 @@ template <typename idx_t> int isa_host(const idx_t* SA, uint64_t n, idx_t* ISA, 
 
 template <typename idx_t> int lce_check_build(const void* SA, const void* LCP, uint64_t n, const void* index, uint64_t index_bytes)
 {
-    if (int rc = lz_check_arrays<idx_t>(SA, LCP, n, "SA or LCP is null")) return rc;
+    if (int rc = check_arrays<idx_t>(n, !SA || !LCP, "SA or LCP is null")) return rc;
     if (!index) return fail(CAPS_SA_EINVAL, "null index");
     if (reinterpret_cast<uintptr_t>(index) & 15u) return fail(CAPS_SA_EINVAL, "the index must be 16-byte aligned");
     if (index_bytes < lce_layout(n, sizeof(idx_t)).total) return fail(CAPS_SA_EINVAL, "index_bytes too small (caps_sa_hip_lce_index_bytes)");
@@ -3776,10 +3684,9 @@ template <typename idx_t> int lce_build_host(const idx_t* SA, const idx_t* LCP, 
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        hc.fm_host = nullptr;
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-        const size_t need = lce_layout(n, sizeof(idx_t)).total, off_sa = up(need), off_lcp = off_sa + up(n * sizeof(idx_t));
-        fm_host_block(hc, be, device, off_lcp + up(n * sizeof(idx_t)) + 256);
+        hc.blob_host = nullptr;
+        const size_t need = lce_layout(n, sizeof(idx_t)).total, off_sa = align_up(need), off_lcp = off_sa + align_up(n * sizeof(idx_t));
+        host_block(hc, be, device, off_lcp + align_up(n * sizeof(idx_t)) + WS_ALIGN);
         idx_t* dSA = reinterpret_cast<idx_t*>(hc.base + off_sa);
         idx_t* dLCP = reinterpret_cast<idx_t*>(hc.base + off_lcp);
         be.h2d(dSA, SA, n * sizeof(idx_t));
@@ -3787,7 +3694,7 @@ template <typename idx_t> int lce_build_host(const idx_t* SA, const idx_t* LCP, 
         if (int rc = run_lce_build<idx_t>(be, dSA, dLCP, n, hc.base)) return rc;                                  // the caller's blob is not written
         be.d2h(index, hc.base, need);
         be.sync();
-        fm_mark_resident(hc, index, need);
+        blob_mark_resident(hc, index, need);
         return CAPS_SA_OK;
     });
 }
@@ -3803,7 +3710,7 @@ inline int run_lce_query(Backend& be, const void* dIndex, uint64_t index_bytes, 
     LceView v;
     if (int rc = lce_check_header(h, index_bytes, dIndex, v)) return rc;
     if (q == 0) return CAPS_SA_OK;
-    uint32_t* flags = reinterpret_cast<uint32_t*>(fm_words(be));
+    uint32_t* flags = reinterpret_cast<uint32_t*>(call_words(be));
     be.memset(flags, 0, sizeof(uint32_t));
     const uint32_t g = capped_grid(std::min<uint64_t>((q + FM_NT - 1) / FM_NT, 1u << 20), FM_NT);
     const uint64_t* A = static_cast<const uint64_t*>(dA);
@@ -3851,10 +3758,9 @@ inline int lce_query_host(const void* index, uint64_t index_bytes, const uint64_
         HostPathCache& hc = host_cache();
         std::lock_guard<std::mutex> lock(hc.mu);
         Backend be(nullptr);
-        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
         const uint64_t blob = h[LCEH_TOTAL];
-        const size_t off_a = up(blob), off_b = off_a + up(q * 8), off_out = off_b + up(q * 8);
-        fm_upload(hc, be, device, index, blob, off_out + up(q * 8));
+        const size_t off_a = align_up(blob), off_b = off_a + align_up(q * 8), off_out = off_b + align_up(q * 8);
+        blob_upload(hc, be, device, index, blob, off_out + align_up(q * 8));
         be.h2d(hc.base + off_a, A, q * 8);
         be.h2d(hc.base + off_b, B, q * 8);
         const int rc = run_lce_query(be, hc.base, blob, h, hc.base + off_a, hc.base + off_b, q, mismatches, hc.base + off_out);
@@ -4215,8 +4121,8 @@ void CAPS_API(host_free)(void* p) { caps::Backend::host_free(p); }
 int CAPS_API(workspace_bytes_ex)(uint64_t n, uint64_t subproblem_count, int idx_bytes, int bits_per_char, uint64_t* bytes)
 {
     if (!bytes || (idx_bytes != 4 && idx_bytes != 8) || (bits_per_char != 2 && bits_per_char != 8)) return caps::fail(CAPS_SA_EINVAL, "bad argument");
-    *bytes = (idx_bytes == 4 ? caps::make_plan<uint32_t>(n, subproblem_count, nullptr, bits_per_char).bytes
-                             : caps::make_plan<uint64_t>(n, subproblem_count, nullptr, bits_per_char).bytes) + 256;
+    *bytes = caps::ws_reported(idx_bytes == 4 ? caps::make_plan<uint32_t>(n, subproblem_count, nullptr, bits_per_char).bytes
+                                              : caps::make_plan<uint64_t>(n, subproblem_count, nullptr, bits_per_char).bytes);
     return CAPS_SA_OK;
 }
 int CAPS_API(workspace_bytes)(uint64_t n, uint64_t subproblem_count, int idx_bytes, uint64_t* bytes)

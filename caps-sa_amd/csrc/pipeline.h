@@ -44,13 +44,19 @@ template <typename idx_t> struct ElemBuf {
                                   // (it can then be viewed as a slot buffer of a speculative bucket split)
 };
 
+// Every part of a device workspace starts at a multiple of WS_ALIGN bytes: sizes and offsets are rounded up with align_up(size_t),
+// a caller's pointer with align_up(char*) (which is why a reported workspace size carries WS_ALIGN bytes on top of its layout).
+constexpr size_t WS_ALIGN = 256;
+inline size_t align_up(size_t b) { return (b + (WS_ALIGN - 1)) & ~(WS_ALIGN - 1); }
+inline char* align_up(char* p) { return reinterpret_cast<char*>(align_up(reinterpret_cast<uintptr_t>(p))); }
+
 // Bump allocator over one device allocation (or a dry run that only measures).
 struct Arena {
     char* base = nullptr;
     size_t off = 0;
     template <typename T> T* take(size_t count)
     {
-        off = (off + 255) & ~size_t(255);
+        off = align_up(off);
         T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
         off += count * sizeof(T);
         return p;
@@ -1133,12 +1139,11 @@ struct MsdArena {
     char* lo[2] = {nullptr, nullptr};
     char* hi[2] = {nullptr, nullptr};
     bool failed = false;
-    static char* up(char* p) { return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p) + 255) & ~uintptr_t(255)); }
     template <typename T> T* head(size_t count, int pref = 0)
     {
         for (int k = 0; k < 2; ++k) {
             const int c = (pref + k) & 1;
-            char* p = up(lo[c]);
+            char* p = align_up(lo[c]);
             if (p && p + count * sizeof(T) <= hi[c]) { lo[c] = p + count * sizeof(T); return reinterpret_cast<T*>(p); }
         }
         failed = true;

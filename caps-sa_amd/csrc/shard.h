@@ -753,7 +753,7 @@ private:
         // one allocation (key | sa | lcp): a speculative bucket split views it as its slot buffer
         ElemBuf<idx_t> b;
         const size_t c = cnt ? cnt : 1;
-        const size_t key_bytes = (c * sizeof(uint64_t) + 255) & ~size_t(255), idx_bytes = (c * sizeof(idx_t) + 255) & ~size_t(255);
+        const size_t key_bytes = align_up(c * sizeof(uint64_t)), idx_bytes = align_up(c * sizeof(idx_t));
         char* base = get<char>(key_bytes + 2 * idx_bytes);
         b.key = reinterpret_cast<uint64_t*>(base);
         b.sa = reinterpret_cast<idx_t*>(base + key_bytes);
