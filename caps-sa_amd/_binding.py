@@ -81,6 +81,7 @@ class Stats(ctypes.Structure):
         ("direct_records", ctypes.c_uint32),
         ("tile_chain", ctypes.c_uint32),
         ("scatter_issue", ctypes.c_uint32),
+        ("slot_keys", ctypes.c_uint32),
     ]
 
     def as_dict(self) -> dict:

@@ -676,6 +676,47 @@ DEV_INLINE uint32_t bucket_of(const BucketParams& bp, uint64_t key)
     return b < bp.B ? b : bp.B - 1;
 }
 
+// ---- slot keys: what level B of the direct path hands to the tile sort in 8-byte records (CAPS_SA_SLOT_KEYS) ----------------
+// A bucket of a group with map bp holds the keys of ONE contiguous interval no wider than W = bp.range / bp.B + 1 (the preimage
+// of one bucket under the monotone bucket_of), and all of them share their top bits: those need not travel.  The slot holds
+//     r = (uint32_t)(key >> s),    s = slot_key_shift(bp.range, bp.B) = max(0, bitlength(W) - 30)         (one shift per group)
+// so 2^(30 + s) > W and the window 2^(32 + s) of r is more than four bucket widths.  With l the nominal lower end of the bucket
+// (bucket_ranges_kernel: the kmin of its bin map) and
+//     base = slot_key_base(l, s) = max(0, l - 2^(30 + s))                                                 (0 when 30 + s >= 64)
+// every key k of the bucket satisfies 0 <= (k >> s) - (base >> s) < 2^32, hence x = r - (uint32_t)(base >> s), in 32-bit
+// wrap-around arithmetic, is monotone in k whichever multiple of 2^(32 + s) the bucket straddles, and k >> s == (base >> s) + x
+// as a 64-bit sum: slot_key_restore gives back k with its low s bits cleared.  Two elements with different x differ in their top
+// 64 - s bits (order and LCP as from the 64-bit keys, bit for bit); equal x = the first (64 - s) / BITS chars agree and the text
+// decides from there.  The rule is THIS function in both places: the scatter derives s from bps[g], bucket_ranges_kernel stores
+// it per bucket in kshift[] for the tile sort.
+HD uint32_t slot_key_shift(uint64_t range, uint32_t B)
+{
+    const uint64_t w = range / (B ? B : 1u);                             // W - 1
+    const uint32_t bl = w == ~0ull ? 65u : 64u - (uint32_t)caps_clz64(w + 1);   // bitlength(W)
+    return bl > 30u ? bl - 30u : 0u;
+}
+HD uint64_t slot_key_base(uint64_t l, uint32_t s)
+{
+    if (30u + s >= 64u) return 0;
+    const uint64_t m = 1ull << (30u + s);
+    return l > m ? l - m : 0;
+}
+HD uint64_t slot_key_restore(uint64_t base, uint32_t s, uint32_t r)
+{
+    const uint64_t bs = base >> s;
+    return (bs + (uint32_t)(r - (uint32_t)bs)) << s;
+}
+// kshift[g] through the scalar unit: the aligned word that holds the byte.  (A byte load from a uniform address is a VECTOR load
+// on gfx950, and the wait for it -- the shift is wanted in a scalar register -- would also wait for every data load issued before
+// it.)  REQUIRES a table that starts at a multiple of 4 bytes and whose last word can be read: pipeline.h plan() starts every table
+// at a multiple of 256 bytes and puts another one behind this one.
+DEV_INLINE uint32_t slot_kshift_of(const uint8_t* __restrict__ kshift, uint32_t g)
+{
+    return (reinterpret_cast<const uint32_t*>(kshift)[g >> 2] >> (8u * (g & 3u))) & 0xFFu;
+}
+// the record of a slot: r in the low word, the index in the high one (one 8-byte store, one 8-byte load)
+HD uint64_t slot_rec(uint64_t key, uint32_t s, uint32_t sa) { return ((uint64_t)sa << 32) | (uint32_t)(key >> s); }
+
 // Exclusive scan of NBINS counters in LDS, in place; h[NBINS] = total.
 // gfx950: every thread owns NBINS / TILE_NT consecutive counters; wave64 shuffle scan of the
 // per-thread sums, wave totals combined through LDS (two barriers).
@@ -809,6 +850,15 @@ template <int BITS, bool RUNS, typename idx_t>
 DEV_INLINE uint64_t tile_pair_lcp(const uint32_t* __restrict__ P, uint64_t n, uint32_t ka, idx_t a, uint32_t kb, idx_t b, uint32_t cs)
 {
     return pair_lcp32<BITS, RUNS>(P, n, ka, (uint64_t)a, kb, (uint64_t)b, cs);
+}
+
+// ... of two keys put together from slot keys (tile_sort_kernel SLOTREC): equal keys stand for `from` equal chars, not KCH
+template <int BITS, typename idx_t>
+DEV_INLINE uint64_t slot_pair_lcp(const uint32_t* __restrict__ P, uint64_t n, uint64_t ka, idx_t a, uint64_t kb, idx_t b, uint32_t from)
+{
+    const uint64_t x = ka ^ kb;
+    if (x) return lcp_capped<idx_t>((uint32_t)caps_clz64(x) / BITS, n, a, b);
+    return deep_lcp<BITS, false>(P, n, (uint64_t)a, (uint64_t)b, from);
 }
 
 // ... or TIE_SENTINEL for a pair of equal keys when ties are deferred (bflag != null: "Deferred ties" above)
@@ -1015,7 +1065,13 @@ DEV_INLINE const uint32_t* tile_src(const uint32_t* in, const uint64_t*, bool) {
 // bucket fills 7/8 of its slot, and loading the whole slot early -- 5 GB more at 3e9 -- took back most of the gain.
 // The queue of unfinished tiles still carries tile indices (the kernels behind this one read their tiles through tile_rec):
 // tile_off[g].  grid = the slots.
-template <typename idx_t, int BITS, bool FROM_TEXT, typename KT = uint64_t, int CHAIN = 0>
+// SLOTREC (CHAIN != 0): the slots hold 8-byte records of slot keys ("slot keys" above; in_key points at them, in_sa is unused,
+// kshift[bucket] = the shift of the bucket's group).  Only the load differs: one 8-byte load per element, and behind the wait
+// the 64-bit key is put together again from the record, the shift and the bucket's nominal lower end (the kmin of its bin map)
+// -- with its low `shift` bits cleared.  From there this is the 64-bit kernel, except that equal keys stand for tie_from =
+// (64 - shift) / BITS equal chars instead of KCH: the tie-break and the LCP of such a pair read the text from there.  A tile
+// this build cannot finish is queued as ever; the kernels behind it cut their keys from the text (slot_unpack_kernel).
+template <typename idx_t, int BITS, bool FROM_TEXT, typename KT = uint64_t, int CHAIN = 0, bool SLOTREC = false>
 GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX SegDesc sd, const uint32_t* __restrict__ P, uint64_t n,
                                                   uint64_t text_base, uint32_t lcp_mode, uint32_t slot_cap, const KT* in_key,
                                                   const idx_t* in_sa, uint64_t* out_key, idx_t* out_sa, idx_t* out_lcp,
@@ -1029,10 +1085,12 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX Seg
     constexpr uint32_t CHAIN_EARLY = BY_BUCKET ? TILE_EPT - 1 : 0u;
     static_assert(!K32 || !FROM_TEXT, "32-bit keys come from the slots of level B");
     static_assert(!BY_BUCKET || (!FROM_TEXT && !K32 && sizeof(idx_t) == 4), "bucket-indexed: 64-bit keys and 32-bit indices in slots");
+    static_assert(!SLOTREC || (BY_BUCKET && BITS == 2), "records of slot keys: the bucket-indexed build on 2-bit texts");
     TL_DECL(KT, rk, TILE_EPT);
     TL_DECL(idx_t, rs, TILE_EPT);
     uint64_t bs0 = 0, bs1 = 0;                                              // BY_BUCKET: the bucket's bounds and its bin map, requested
     BucketParams tb_early = BucketParams();                                 //   here and not waited for before the loads below are out
+    uint32_t ks_early = 0;                                                  // SLOTREC: ... and the shift of the bucket's slot keys
     // BY_BUCKET REQUIRES seg_map (one prepared bin map per slot of the grid) and seg_start[0 .. grid]: the launch reads both
     // unconditionally, and this build does not initialise kmm -- the min / max route of TILE_SORT_RANGE_ (seg_map == null) would
     // read it unset.  segmented_sort takes this launch only with seg_map != null and grid <= G (pipeline.h, by_bucket).
@@ -1040,12 +1098,13 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX Seg
         bs0 = sd.seg_start[K_BLOCK_IDX];
         bs1 = sd.seg_start[K_BLOCK_IDX + 1];
         tb_early = seg_map[K_BLOCK_IDX];
+        if (SLOTREC) ks_early = slot_kshift_of(kshift, K_BLOCK_IDX);
         PAR(tid) {
             const uint64_t in0e = (uint64_t)K_BLOCK_IDX * slot_cap;
             UNROLL
             for (uint32_t k = 0; k < CHAIN_EARLY; ++k) {
-                TL(rk, tid, k) = STREAM_LOAD(&in_key[in0e + tid + k * TILE_NT]);
-                TL(rs, tid, k) = STREAM_LOAD(&in_sa[in0e + tid + k * TILE_NT]);
+                TL(rk, tid, k) = STREAM_LOAD(&in_key[in0e + tid + k * TILE_NT]);                  // (SLOTREC: the record)
+                if (!SLOTREC) TL(rs, tid, k) = STREAM_LOAD(&in_sa[in0e + tid + k * TILE_NT]);
             }
         }
         ISSUE_FENCE();                                                        // ... and stay ahead of the branch on the bounds
@@ -1072,7 +1131,9 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX Seg
     // of its time.)
     const uint64_t in0 = slot_cap ? (uint64_t)g * slot_cap : start;
     const uint32_t TILE_KEY_SHIFT = K32 ? kshift[g] : 0u;                                  // block-uniform
-    const uint32_t tie_from = K32 ? (TILE_KEY_SHIFT + 32u) / BITS : TextTraits<BITS>::KCH;   // chars two equal keys stand for
+    const uint32_t tie_from = K32       ? (TILE_KEY_SHIFT + 32u) / BITS                    // chars two equal keys stand for
+                              : SLOTREC ? (64u - ks_early) / BITS
+                                        : TextTraits<BITS>::KCH;
     SHARED_ARRAY(KT, skey, TILE_E);
     SHARED_ARRAY(idx_t, ssa, TILE_E);
     SHARED_ARRAY(uint32_t, hist, TILE_BINS + 1);
@@ -1101,7 +1162,7 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX Seg
                 const uint32_t e = tid + k * TILE_NT;
                 if (e < cnt) {
                     TL(rk, tid, k) = STREAM_LOAD(&in_key[in0 + e]);
-                    TL(rs, tid, k) = STREAM_LOAD(&in_sa[in0 + e]);
+                    if (!SLOTREC) TL(rs, tid, k) = STREAM_LOAD(&in_sa[in0 + e]);
                 }
             }
         }
@@ -1109,6 +1170,19 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX Seg
         TILE_SORT_LOAD
     }
     TILE_SORT_RANGE_(BY_BUCKET ? tb_early : seg_map[g])
+    if (SLOTREC) {
+        // record -> (64-bit key with its low bits cleared, index); lanes at or beyond cnt hold whatever the slot held, as before
+        const uint64_t kbase = slot_key_base(tb.kmin, ks_early);
+        PAR(tid) {
+            UNROLL
+            for (uint32_t k = 0; k < TILE_EPT; ++k) {
+                if (k >= CHAIN_EARLY && tid + k * TILE_NT >= cnt) continue;                     // (the late load was not made)
+                const uint64_t rec = (uint64_t)TL(rk, tid, k);
+                TL(rs, tid, k) = (idx_t)(rec >> 32);
+                TL(rk, tid, k) = (KT)slot_key_restore(kbase, ks_early, (uint32_t)rec);
+            }
+        }
+    }
     PHASE_MARK(0);                                             // load (+ range)
     bool fast = cnt > 1 && tb.range > 0;
     if (fast) {
@@ -1204,7 +1278,11 @@ GLOBAL_FN LAUNCH_BOUNDS2(TILE_NT, TILE_WAVES_PER_SIMD) tile_sort_kernel(KCTX Seg
                     const KT key = skey[sl];
                     const idx_t sa = ssa[sl];
                     uint64_t l = 0;
-                    if (with_lcp && e) { const uint32_t sp = perm[e - 1]; l = TILE_EMIT_LCP_(skey[sp], ssa[sp], key, sa); }
+                    if (with_lcp && e) {
+                        const uint32_t sp = perm[e - 1];
+                        if (SLOTREC) l = slot_pair_lcp<BITS, idx_t>(P, n, (uint64_t)skey[sp], ssa[sp], (uint64_t)key, sa, tie_from);
+                        else l = TILE_EMIT_LCP_(skey[sp], ssa[sp], key, sa);
+                    }
                     if (direct) {
                         STREAM_STORE(&fin.sa[start + e], sa);
                         STREAM_STORE(&fin.lcp[start + e], (idx_t)l);
@@ -1248,6 +1326,47 @@ GLOBAL_FN LAUNCH_BOUNDS(256) queue_all_tiles_kernel(KCTX SegDesc sd, uint32_t* _
         const uint32_t i = K_BLOCK_IDX * K_BLOCK_DIM + tid;
         if (i < nt) redo[1 + i] = i;
         if (i == 0) redo[0] = nt;
+    }
+}
+
+// Slots of 8-byte records (tile_sort_kernel SLOTREC): the kernels behind tile_sort_kernel in the queue chain read an index array and cut
+// their 64-bit keys from the text (their keys_from_text route, as behind 32-bit keys).  The indices of the QUEUED tiles -- a handful,
+// none on random DNA -- are copied out of their records into the index array of the two-array view of the slots, which lies behind the
+// records and is idle: no record layout in the three large kernels.  A fixed grid walks the queue.
+GLOBAL_FN LAUNCH_BOUNDS(256) slot_unpack_kernel(KCTX SegDesc sd, const uint32_t* __restrict__ redo, uint32_t slot_cap,
+                                                const uint64_t* __restrict__ rec, uint32_t* __restrict__ out_sa)
+{
+    const uint32_t n_redo = redo[0];
+    for (uint32_t qi = K_BLOCK_IDX; qi < n_redo; qi += K_GRID_DIM) {
+        const TileInfo t = tile_info(sd, redo[1 + qi]);
+        const uint64_t len = t.s1 - t.s0, in0 = (uint64_t)t.g * slot_cap;
+        const uint32_t cnt = (uint32_t)(len < slot_cap ? len : slot_cap);
+        PAR(tid) {
+            for (uint32_t i = tid; i < cnt; i += K_BLOCK_DIM) out_sa[in0 + i] = (uint32_t)(rec[in0 + i] >> 32);
+        }
+    }
+}
+
+// CAPS_SA_DEBUG only, behind a sort over slots of slot-key records: count[0] = neighbours of the result inside one bucket whose
+// slot keys were equal (their keys agree above the bucket's shift) -- the pairs the tile sort had to settle from the text;
+// count[1] = bucket heads whose key agrees above the shift with the key of the element before them (the last one of the bucket
+// below): ties ACROSS a boundary, whose LCP head_lcp_kernel must take from the text.
+template <typename idx_t, int BITS>
+GLOBAL_FN LAUNCH_BOUNDS(256) slot_tie_count_kernel(KCTX const uint32_t* __restrict__ P, const uint64_t* __restrict__ seg_start, uint32_t G,
+                                                   const uint8_t* __restrict__ kshift, const idx_t* __restrict__ sa,
+                                                   uint64_t* __restrict__ count)
+{
+    for (uint32_t g = K_BLOCK_IDX; g < G; g += K_GRID_DIM) {
+        const uint64_t s0 = seg_start[g], s1 = seg_start[g + 1];
+        const uint32_t s = kshift[g];
+        PAR(tid) {
+            uint64_t c = 0;
+            for (uint64_t i = s0 + 1 + tid; i < s1; i += K_BLOCK_DIM)
+                c += (window64<BITS>(P, (uint64_t)sa[i - 1]) >> s) == (window64<BITS>(P, (uint64_t)sa[i]) >> s) ? 1u : 0u;
+            if (c) ATOMIC_ADD_U64(count, c);
+            if (tid == 0 && s1 > s0 && s0 > 0 && (window64<BITS>(P, (uint64_t)sa[s0 - 1]) >> s) == (window64<BITS>(P, (uint64_t)sa[s0]) >> s))
+                ATOMIC_ADD_U64(count + 1, 1ull);
+        }
     }
 }
 
@@ -2788,9 +2907,10 @@ GLOBAL_FN LAUNCH_BOUNDS(256) bucket_ranges_kernel(KCTX const uint64_t* __restric
                                                   uint32_t range_mode, uint32_t part_off, uint32_t part_total, uint32_t sub,
                                                   BucketParams* __restrict__ tile_map,
                                                   const BucketParams* __restrict__ fbps, const uint32_t* __restrict__ gfirst,
-                                                  const uint8_t* __restrict__ gshift, uint8_t* __restrict__ kshift)
+                                                  const uint8_t* __restrict__ gshift, uint8_t* __restrict__ kshift, uint32_t slot_keys)
 {
     // range_mode 2 (32-bit keys): the ranges are in the parent's key32 space; kshift[bucket] = the parent's shift
+    // slot_keys != 0 (never with range_mode 2): kshift[bucket] = the shift of the slot keys of the bucket's group (slot_key_shift)
     // gfirst != null (equalised split): bucket slot i is the group of fine buckets [gfirst[i], gfirst[i + 1]) of fbps[g]
     PAR(tid) {
         const uint64_t i = (uint64_t)K_BLOCK_IDX * K_BLOCK_DIM + tid;
@@ -2809,6 +2929,7 @@ GLOBAL_FN LAUNCH_BOUNDS(256) bucket_ranges_kernel(KCTX const uint64_t* __restric
                 if (j + 1 < part_total) kmax = pkey[j];
                 if (range_mode == 2) { key32_range(kmin, kmax, j > 0, gshift[j]); kshift[i] = gshift[j]; }
             }
+            if (slot_keys && range_mode != 2) kshift[i] = (uint8_t)slot_key_shift(bp.range, bp.B);
             const uint32_t bk = (uint32_t)(i - bstart[g]);
             const double range1 = (double)(kmax - kmin) + 1.0;
             uint64_t l = kmin, h = kmax;
@@ -3043,7 +3164,12 @@ constexpr uint32_t SPILL_CHUNK = TILE_E / 128 ? TILE_E / 128 : 1;   // a tile of
 // travel meanwhile) and in front of the emit (a lane without a bucket to bump still counts the bump: every store pair waited
 // for the pair before it).  At none of the three is anything outstanding when the kernel runs, but the unused load of a wave
 // that lies beyond the end of a last tile.
-template <typename idx_t, int BITS, int SRC, int MAP, typename KT = uint64_t, bool SPILL = false, bool REC_IN = false, bool ISSUE = false>
+// SLOT32 (ISSUE, slots only): the elements leave as 8-byte records (slot_rec above: the key narrowed by the group's shift, the
+// index) in ONE array of slots -- out_key, out_sa is unused -- 8 instead of 12 bytes and one run instead of two per (tile,
+// bucket).  Classified on the 64-bit key as before; the key is narrowed where the element is placed into LDS, so the staging
+// array holds the records (skey; ssa is not used) and the emit is one 8-byte LDS read and one 8-byte store per element.
+template <typename idx_t, int BITS, int SRC, int MAP, typename KT = uint64_t, bool SPILL = false, bool REC_IN = false, bool ISSUE = false,
+          bool SLOT32 = false>
 GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const uint32_t* __restrict__ P, uint64_t n_words,
                                                        uint64_t text_base, const KT* __restrict__ in_key,
                                                        const idx_t* __restrict__ in_sa, RunSrc<idx_t> rsrc,
@@ -3084,6 +3210,7 @@ GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const ui
     const uint64_t start = t.s0 + (uint64_t)t.tl * TILE_E;
     const uint32_t cnt = (uint32_t)(t.s1 - start < TILE_E ? t.s1 - start : TILE_E);
     static_assert(!ISSUE || (REC_IN && MAP == MAP_LINEAR && !SPILL), "loads first: the records of level A under the linear map");
+    static_assert(!SLOT32 || (ISSUE && sizeof(KT) == 8 && sizeof(idx_t) == 4), "slot keys: the build that issues its loads first, 32-bit indices");
     TL_DECL(KT, rk, TILE_EPT);
     TL_DECL(idx_t, rs, TILE_EPT);
     if (ISSUE) {
@@ -3102,6 +3229,7 @@ GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const ui
     }
     const BucketParams bp = bps[g];
     const uint64_t b0 = bstart[g];
+    const uint32_t ks = SLOT32 ? slot_key_shift(bp.range, bp.B) : 0u;    // block-uniform: a tile belongs to one group
     const bool grouped = GROUPED && bp.B > 1 && bp.B <= BUCKET_LDS;      // GROUPED: a build of its own, the plain scatter is hot
     const BucketParams fbp = GROUPED ? fbps[g] : bp;
     SHARED_ARRAY(uint32_t, hist, TILE_BINS + 1);          // counts -> exclusive prefix inside the tile
@@ -3110,7 +3238,7 @@ GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const ui
     static_assert(sizeof(KT) == 8 || (SRC == SRC_ARRAYS && MAP == MAP_LINEAR), "32-bit keys: arrays in, linear map");
     static_assert(!REC_IN || (SRC == SRC_ARRAYS && sizeof(KT) == 8 && sizeof(idx_t) == 4), "records: arrays in, 64-bit keys, 32-bit indices");
     SHARED_ARRAY(KT, skey, TILE_E);
-    SHARED_ARRAY(idx_t, ssa, TILE_E);
+    SHARED_ARRAY(idx_t, ssa, SLOT32 ? 1 : TILE_E);
     SHARED_ARRAY(uint16_t, sbk, TILE_E);
     // SPILL: the long runs of the tile that went to the stream (at, cursor value, length, bucket)
     SHARED_ARRAY(uint64_t, lr_at, SPILL ? SPILL_LONG_CAP : 1);
@@ -3155,8 +3283,11 @@ GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const ui
                         const uint64_t off = bp.B == 1 ? (start - t.s0) + e : (uint64_t)caps_fetch_add(&cursor[bi], (idx_t)1);
                         if (!spec || off < slot_cap) {
                             const uint64_t dst = (spec ? bi * slot_cap : sub_start[bi]) + off;
-                            out_key[dst] = TL(rk, tid, k);
-                            out_sa[dst] = TL(rs, tid, k);
+                            if (SLOT32) out_key[dst] = (KT)slot_rec((uint64_t)TL(rk, tid, k), ks, (uint32_t)TL(rs, tid, k));
+                            else {
+                                out_key[dst] = TL(rk, tid, k);
+                                out_sa[dst] = TL(rs, tid, k);
+                            }
                         }
                     }
                 }
@@ -3336,8 +3467,11 @@ GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const ui
             if (e < cnt) {
                 const uint32_t bk = TL(rb, tid, k);
                 const uint32_t q = hist[bk] + (uint32_t)TL(rr, tid, k);
-                skey[q] = TL(rk, tid, k);
-                ssa[q] = TL(rs, tid, k);
+                if (SLOT32) skey[q] = (KT)slot_rec((uint64_t)TL(rk, tid, k), ks, (uint32_t)TL(rs, tid, k));
+                else {
+                    skey[q] = TL(rk, tid, k);
+                    ssa[q] = TL(rs, tid, k);
+                }
                 sbk[q] = (uint16_t)bk;
             }
         }
@@ -3398,7 +3532,7 @@ GLOBAL_FN LAUNCH_BOUNDS(TILE_NT) bucket_scatter_kernel(KCTX SegDesc sd, const ui
                 } else if (ob != NO_SLOT) {
                     const uint64_t dst = (uint64_t)ob + (q - hist[bk]);
                     STREAM_STORE2(&out_key[dst], skey[q]);
-                    STREAM_STORE2(&out_sa[dst], ssa[q]);
+                    if (!SLOT32) STREAM_STORE2(&out_sa[dst], ssa[q]);
                 }
             }
         }

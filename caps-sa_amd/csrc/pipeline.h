@@ -91,6 +91,9 @@ constexpr uint32_t DIRECT_TILE_CHAIN_DEFAULT = 1;
 // level A (group_scatter_kernel's tables staged together): measured slower and not built (DESIGN 5.3,
 // docs/r08_level_a_staging.patch); the bit is read and ignored.  Linear mode with 32-bit indices, records and one wave only.
 constexpr uint32_t DIRECT_SCATTER_ISSUE_DEFAULT = 1;
+// Whether level B of the direct path hands the tile sort slot keys when CAPS_SA_SLOT_KEYS does not say (kernels.h "slot keys"): bit 0 =
+// 8-byte records of bucket-relative 32-bit keys in the slots; 0 = 64-bit keys and indices in two arrays.
+constexpr uint32_t DIRECT_SLOT_KEYS_DEFAULT = 1;
 // Quantile mode of the direct path (skewed keys): mean bucket size (sampling noise on top: sigma = 1 / sqrt(QUANTILE_SPB)) and
 // samples drawn per bucket.
 #ifndef CAPS_BUCKET_Q_32NDS
@@ -431,6 +434,8 @@ template <typename idx_t> struct SortResult {
     bool skip_finished = false;
     bool unified = false;                                             // everything was gathered into buf[0]
     bool k32 = false;                                                 // sorted with 32-bit keys (boundary LCPs come from the text)
+    bool slot_keys = false;                                           // sorted from slots of slot-key records: the boundary records' keys have
+                                                                      //   their low bits cleared (boundary LCPs come from the text)
     bool failed = false;                                              // k32 only: a slot overflowed, nothing was sorted
     SegBufs segs;                                                     // the segments that were sorted (buckets, if bucketed)
     // letter-run buckets (text.h "letter runs"): they sat out the sort; finalize() orders them by their run keys
@@ -519,12 +524,61 @@ struct SortOpts {
     uint32_t* tile_chain_used = nullptr;   // host word: the stages the sort's tile_sort_kernel launch really ran with
     uint32_t scatter_issue = 0;         // bit 0: the scatter of records under the linear map runs bucket_scatter_kernel's ISSUE build
     uint32_t* scatter_issue_used = nullptr;   // host word: bit 0 is set when such a launch was made
+    uint32_t slot_keys = 0;             // bit 0 (run_direct, CAPS_SA_SLOT_KEYS): a linear slot split of records writes its slots as 8-byte
+                                        //   records of slot keys (kernels.h "slot keys") and the bucket-indexed tile sort reads those;
+                                        //   only where both the ISSUE scatter and the bucket-indexed launch are asked for
+    uint32_t* slot_keys_used = nullptr;    // host word: the mask the sort really ran with (0: a redone split, or a sort that does not qualify)
     KernelClock* tile_clock = nullptr;
     KernelClock* merge_clock = nullptr;
     KernelClock* scatter_clock = nullptr;
     KernelClock* count_clock = nullptr;
     uint64_t* pass_counters = nullptr;
 };
+
+// CAPS_SA_DEBUG, behind a sort over slots of slot-key records (kernels.h "slot keys"; segmented_sort's bucket-indexed launch): the
+// shifts of the non-empty buckets, the buckets whose nominal key range straddles a multiple of the window 2^(32 + shift) -- their
+// r wraps around inside the bucket -- and the neighbours of the result whose slot keys were equal, counted on the device here and
+// only here; for a sort of a few groups also the groups' maps (a test plants a tie on a bucket's edge with them).  The tests read
+// these lines through the patterns _SLOT_KEYS and _MAP of tests/slot_keys_cases.py: change wording and patterns together.
+// ss: the bounds of the launch's buckets on the host; G: the parent segments; sa: the sorted indices (the caller's SA slice).
+template <typename idx_t, int BITS>
+void describe_slot_keys(Backend& be, const uint32_t* P, const BucketBufs& bk, const uint64_t* seg_start, const std::vector<uint64_t>& ss,
+                        uint32_t slot_grid, uint32_t G, const idx_t* sa)
+{
+    std::vector<uint8_t> ks(slot_grid);
+    std::vector<BucketParams> tm(slot_grid);
+    uint64_t ties[2] = {0, 0};
+    uint64_t* dbg_ties = bk.count;                 // (idle since the tile tables were made; nb_cap >= 2 entries)
+    be.memset(dbg_ties, 0, sizeof ties);
+    CAPS_LAUNCH((slot_tie_count_kernel<idx_t, BITS>), slot_grid < 4096 ? slot_grid : 4096u, 256, be, P, seg_start, slot_grid,
+                (const uint8_t*)bk.kshift, sa, dbg_ties);
+    be.d2h(ks.data(), bk.kshift, ks.size());
+    be.d2h(tm.data(), bk.tile_map, tm.size() * sizeof(BucketParams));
+    be.d2h(ties, dbg_ties, sizeof ties);
+    be.sync();
+    uint32_t smin = 64, smax = 0, wraps = 0, full = 0;
+    for (uint32_t g = 0; g < slot_grid; ++g) {
+        if (ss[g + 1] == ss[g]) continue;
+        ++full;
+        smin = std::min<uint32_t>(smin, ks[g]);
+        smax = std::max<uint32_t>(smax, ks[g]);
+        const uint32_t w = 32u + ks[g];
+        if (w < 64 && (tm[g].kmin >> w) != ((tm[g].kmin + tm[g].range) >> w)) ++wraps;
+    }
+    std::fprintf(stderr, "[sort] slot keys: shifts %u .. %u, %u of %u buckets whose window wraps, %llu neighbour pairs with equal slot keys, "
+                 "%llu bucket heads tied with the element before them\n", full ? smin : 0u, smax, wraps, full,
+                 (unsigned long long)ties[0], (unsigned long long)ties[1]);
+    if (G > 256) return;
+    std::vector<BucketParams> gp(G);
+    std::vector<uint64_t> gb((size_t)G + 1);
+    be.d2h(gp.data(), bk.params, gp.size() * sizeof(BucketParams));
+    be.d2h(gb.data(), bk.bstart, gb.size() * sizeof(uint64_t));
+    be.sync();
+    for (uint32_t g = 0; g < G; ++g)
+        if (gb[g + 1] > gb[g])                      // (sub-streams of one parent share its map: the last one carries the buckets)
+            std::fprintf(stderr, "[sort] slot keys: group map kmin %llu kmax %llu B %u first bucket %llu\n",
+                         (unsigned long long)gp[g].kmin, (unsigned long long)(gp[g].kmin + gp[g].range), gp[g].B, (unsigned long long)gb[g]);
+}
 
 // Sort every segment of `s`:  [bucket split]  ->  tile sort  ->  LCP-merge passes.
 //   not bucketed: input (unless from_text) is in `cur`, sorted in place, passes ping-pong cur <-> oth;
@@ -559,6 +613,15 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
     uint64_t* slot_key = nullptr;
     idx_t* slot_sa = nullptr;
     uint32_t slot_grid = 0;                          // != 0: the slots of a kept linear slot split (every bucket is one tile or empty)
+    // Slot keys (kernels.h "slot keys"; o.slot_keys bit 0): the slots of a linear slot split of level A's records hold 8-byte records.
+    // Decided before the plan (bucket_ranges_kernel stores the groups' shifts for the tile sort) and only for a sort whose kept
+    // split is certain to take the bucket-indexed launch below; a redone split runs on today's route and reports 0.
+    bool slot32 = false;
+    if constexpr (sizeof(idx_t) == 4 && BITS == 2)
+        slot32 = (o.slot_keys & 1u) != 0 && (o.scatter_issue & 1u) != 0 && (o.tile_chain & 1u) != 0 && o.in_records && o.in_key && o.bk && !o.knots &&
+                 !o.k32 && o.speculate && !o.skewed_keys && !o.comparison_only && !o.keys_only && !o.runs && !o.from_text && o.need_lcp &&
+                 o.final_sa && o.final_lcp;
+    if (o.slot_keys_used) *o.slot_keys_used = 0;
     if (o.bk && (max_len > TILE_E || o.seg_ends)) {      // segments in regions are always bucketed: results are written compactly
         const BucketBufs& bk = *o.bk;
         const SegDesc psd = s.desc();
@@ -577,7 +640,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
         CAPS_LAUNCH(scan_sizes_kernel, 1, 1024, be, (const uint64_t*)bk.segB, s.G, bk.bstart);
         CAPS_LAUNCH(bucket_ranges_kernel, (bk.nb_cap + 255) / 256, 256, be, (const uint64_t*)bk.bstart, s.G,
                     (const BucketParams*)bk.params, o.pkey, o.range_mode, o.part_off, o.part_total ? o.part_total : s.G, o.sub,
-                    bk.tile_map, (const BucketParams*)nullptr, (const uint32_t*)nullptr, o.gshift, bk.kshift);
+                    bk.tile_map, (const BucketParams*)nullptr, (const uint32_t*)nullptr, o.gshift, bk.kshift, slot32 ? 1u : 0u);
         }
         seg_map = bk.tile_map;
         mark("bucket plan");
@@ -600,7 +663,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
             const uint64_t extent = o.in_key ? o.in_extent : n_elems;
             if (room >= extent * sizeof(uint16_t)) bid = reinterpret_cast<uint16_t*>(oth.lcp);
         }
-        auto scatter = [&](const uint64_t* sub_start, uint32_t cap, uint64_t* okey, idx_t* osa, bool grouped = false) {
+        auto scatter = [&](const uint64_t* sub_start, uint32_t cap, uint64_t* okey, idx_t* osa, bool grouped = false, bool rec_out = false) {
             const BucketParams* fbps = grouped ? bk.fparams : nullptr;
             const uint32_t* gfirst = grouped ? bk.gfirst : nullptr;
             BackendEvent s0 = be.record();
@@ -620,7 +683,14 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
                 if constexpr (sizeof(idx_t) == 4) {
                     if (by_knots) CAPS_SCATTER_LAUNCH_REC(MAP_SPLIT);
                     else if (grouped) CAPS_SCATTER_LAUNCH_REC(MAP_GROUPED);
-                    else if (o.scatter_issue & 1u) {
+                    else if (rec_out) {                  // slots of 8-byte records (slot32: scatter_issue bit 0 is set)
+                        if constexpr (BITS == 2)
+                            CAPS_LAUNCH((bucket_scatter_kernel<idx_t, BITS, SRC_ARRAYS, MAP_LINEAR, uint64_t, false, true, true, true>), n_tiles, TILE_NT, be,
+                                        psd, P, n_words, tbase, src_key, src_sa, rsrc, (const BucketParams*)bk.params, (const uint64_t*)bk.bstart, sub_start,
+                                        (uint64_t)cap, static_cast<idx_t*>(bk.cursor), okey, osa, fbps, gfirst, o.knots, (const uint16_t*)nullptr,
+                                        (const uint32_t*)nullptr, 1u, o.knots_per_parent, o.sub, (const uint16_t*)bid, Spill<idx_t>());
+                        if (o.scatter_issue_used) *o.scatter_issue_used |= 1u;
+                    } else if (o.scatter_issue & 1u) {
                         CAPS_LAUNCH((bucket_scatter_kernel<idx_t, BITS, SRC_ARRAYS, MAP_LINEAR, uint64_t, false, true, true>), n_tiles, TILE_NT, be, psd,
                                     P, n_words, tbase, src_key, src_sa, rsrc, (const BucketParams*)bk.params, (const uint64_t*)bk.bstart, sub_start,
                                     (uint64_t)cap, static_cast<idx_t*>(bk.cursor), okey, osa, fbps, gfirst, o.knots, (const uint16_t*)nullptr,
@@ -693,6 +763,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
                               oth.region_bytes >= slot_elems * ((o.k32 ? sizeof(uint32_t) : sizeof(uint64_t)) + sizeof(idx_t)) &&
                               slot_elems + TILE_E < (uint64_t)std::numeric_limits<idx_t>::max();
         if (o.k32 && !can_slot) { r.failed = true; return r; }          // 32-bit keys exist in slots only
+        slot32 = slot32 && can_slot;
         if (can_slot) {
             slot_key = oth.key;
             slot_sa = reinterpret_cast<idx_t*>(reinterpret_cast<char*>(oth.key) + slot_elems * sizeof(uint64_t));
@@ -709,12 +780,13 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
                 BackendEvent s1 = be.record();
                 if (o.scatter_clock) { o.scatter_clock->spans.push_back({s0, s1}); o.scatter_clock->elems.push_back(n_elems); }
             } else
-            scatter(nullptr, TILE_E, slot_key, slot_sa);
+            scatter(nullptr, TILE_E, slot_key, slot_sa, false, slot32);     // (slot32: records in slot_key; slot_sa, behind them, stays idle)
             CAPS_LAUNCH((widen_kernel<idx_t>), (bk.nb_cap + 255) / 256, 256, be, (const idx_t*)static_cast<idx_t*>(bk.cursor),
                         (uint64_t)bk.nb_cap, bk.count);
             adopt_buckets();
             bucket_tiles();
             slots = out2[1] <= TILE_E;
+            slot32 = slot32 && slots;
             if (o.slot_stats) ++o.slot_stats[slots ? 0 : 1];
             if (o.k32 && !slots) { r.failed = true; return r; }
             if (dbg) std::fprintf(stderr, "[sort] slot split: largest bucket %llu -> %s\n", (unsigned long long)out2[1], slots ? "kept" : "redone");
@@ -855,7 +927,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
                             (const uint64_t*)bk.fsegB, (const uint64_t*)bk.fstart, (const uint64_t*)bk.fcount, bk.count, bk.gfirst);
                 CAPS_LAUNCH(bucket_ranges_kernel, (bk.nb_cap + 255) / 256, 256, be, (const uint64_t*)bk.bstart, s.G,
                             (const BucketParams*)bk.params, o.pkey, o.range_mode, o.part_off, o.part_total ? o.part_total : s.G, o.sub,
-                            bk.tile_map, (const BucketParams*)bk.fparams, (const uint32_t*)bk.gfirst, o.gshift, bk.kshift);
+                            bk.tile_map, (const BucketParams*)bk.fparams, (const uint32_t*)bk.gfirst, o.gshift, bk.kshift, 0u);
             }
             BackendEvent c1 = be.record();
             if (o.count_clock) { o.count_clock->spans.push_back({c0, c1}); o.count_clock->elems.push_back(n_elems); }
@@ -882,7 +954,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
         r.skip_finished = true;
         r.segs = segs;
         r.n_tiles = n_tiles;
-    }
+    } else slot32 = false;
     const SegDesc sd = segs.desc();
     // the kernels at the head of the queue chain (tile_sort_kernel, the plain builds of tile_sort_eq_kernel) get a tile table in which
     // the tiles of outgrown buckets are empty (kernels.h hot_tiles_kernel): they pass those on, the rest of the chain has `sd`
@@ -942,6 +1014,8 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
     const idx_t* in_sa = slot_cap ? slot_sa : (o.in_key && segs.seg_start == s.seg_start) ? static_cast<const idx_t*>(o.in_sa) : cur.sa;
     const uint8_t* no_shift = nullptr;
     r.k32 = o.k32 && slot_cap != 0;
+    r.slot_keys = slot32;
+    if (o.slot_keys_used) *o.slot_keys_used = slot32 ? 1u : 0u;
     std::vector<uint64_t> dbg_ss;                          // dbg, bucket-indexed launch: the bounds of its buckets
     if (from_text) {
         CAPS_LAUNCH((tile_sort_kernel<idx_t, BITS, true>), n_tiles, TILE_NT, be, sd, P, n, o.text_base, lcp_mode, 0u,
@@ -981,6 +1055,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
             by_bucket = (o.tile_chain & 1u) != 0 && !all_queued && slot_grid != 0 && slot_cap == TILE_E && max_len <= TILE_E &&
                         seg_map != nullptr && sd_hot.tile_rec == sd.tile_rec && slot_grid <= segs.G;
         if (o.tile_chain_used) *o.tile_chain_used = by_bucket ? 1u : 0u;
+        if (slot32 && !by_bucket) throw std::logic_error("slots of slot-key records are read by the bucket-indexed launch only");
         if (dbg && !by_bucket && (o.tile_chain & 1u) != 0)          // asked for and not taken: the stage log says why
             std::fprintf(stderr, "[sort] table launch although the bucket-indexed one was asked for: idx bytes %u, all queued %d, slots %u of capacity %u "
                          "(a tile: %u), longest bucket %llu, bin maps %d, second tile table %d, segments %u\n", (unsigned)sizeof(idx_t), all_queued ? 1 : 0,
@@ -1007,8 +1082,17 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
                          "%u buckets below %u elements, %u below %u, smallest %llu\n", slot_grid, n_tiles, inner, last,
                          (unsigned long long)(ss[last + 1] - ss[last]), small, TILE_NT, cut, (TILE_EPT - 1) * TILE_NT, (unsigned long long)least);
         }
+        // keys_from_text of the queue kernels: behind slots of slot-key records they cut their keys from the text (as behind 32-bit keys)
+        const uint32_t kft = slot32 ? 1u : 0u;
         if (all_queued && !per_tile) CAPS_LAUNCH(queue_all_tiles_kernel, (n_tiles + 255) / 256, 256, be, sd, redo);
-        else if (by_bucket) {
+        else if (by_bucket && slot32) {
+            if constexpr (sizeof(idx_t) == 4 && BITS == 2) {
+                CAPS_LAUNCH((tile_sort_kernel<idx_t, BITS, false, uint64_t, 1, true>), slot_grid, TILE_NT, be, sd, P, n, (uint64_t)0, lcp_mode, slot_cap,
+                            in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, seg_map, redo, (const uint8_t*)o.bk->kshift);
+                // the queued tiles' indices, out of their records into the (idle) index array behind the records
+                CAPS_LAUNCH(slot_unpack_kernel, ggrid, 256, be, sd, (const uint32_t*)redo, slot_cap, in_key, slot_sa);
+            }
+        } else if (by_bucket) {
             if constexpr (sizeof(idx_t) == 4)
                 CAPS_LAUNCH((tile_sort_kernel<idx_t, BITS, false, uint64_t, 1>), slot_grid, TILE_NT, be, sd, P, n, (uint64_t)0, lcp_mode, slot_cap,
                             in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, seg_map, redo, no_shift);
@@ -1042,9 +1126,9 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
                             in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, (const uint32_t*)redo3, 0u, bflag);
         } else {
             if (eq_tiles) CAPS_LAUNCH((tile_sort_eq_kernel<idx_t, BITS, false>), ggrid, TILE_NT, be, sd_hot, P, n, (uint64_t)0, lcp_mode, slot_cap,
-                        in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, seg_map, (const uint32_t*)redo, redo3, 0u | drop, redo2);
+                        in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, seg_map, (const uint32_t*)redo, redo3, kft | drop, redo2);
             if (eq_tiles) CAPS_LAUNCH((tile_sort_eq_kernel<idx_t, BITS, false, true>), ggrid, TILE_NT, be, sd, P, n, (uint64_t)0, lcp_mode, slot_cap,
-                        in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, seg_map, (const uint32_t*)redo2, redo3, 0u, (uint32_t*)nullptr);
+                        in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, seg_map, (const uint32_t*)redo2, redo3, kft, (uint32_t*)nullptr);
             if (bflag) {                                  // (one round trip, only where ties may be deferred)
                 uint32_t ng = 0;
                 be.d2h(&ng, redo3, sizeof ng);
@@ -1052,7 +1136,7 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
                 defer_check(ng);
             }
             CAPS_LAUNCH_RUNS(tile_sort_general_kernel, (idx_t, BITS, false), ggrid, TILE_NT, be, sd, P, n, (uint64_t)0, lcp_mode, slot_cap,
-                        in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, (const uint32_t*)redo3, 0u, bflag);
+                        in_key, in_sa, cur.key, cur.sa, cur.lcp, fin, (const uint32_t*)redo3, kft, bflag);
         }
         }
     }
@@ -1077,6 +1161,8 @@ SortResult<idx_t> segmented_sort(Backend& be, const uint32_t* P, uint64_t n, Til
             }
             std::fprintf(stderr, "[sort] bucket-indexed launch: %u tiles queued, %u behind an empty slot, %u not tiles of the launch\n", q[0], moved, bad);
         }
+        if constexpr (sizeof(idx_t) == 4 && BITS == 2)
+            if (slot32 && !dbg_ss.empty()) describe_slot_keys<idx_t, BITS>(be, P, *o.bk, segs.seg_start, dbg_ss, slot_grid, s.G, fin.sa);
     }
     if (o.tile_clock) { o.tile_clock->spans.push_back({t0, t1}); o.tile_clock->elems.push_back(n_elems); }
     const uint32_t grid = n_tiles < be.persistent_blocks() ? n_tiles : be.persistent_blocks();
@@ -1403,7 +1489,7 @@ void finalize(Backend& be, const uint32_t* P, uint64_t n, const SortResult<idx_t
                         r.passes & 1u, dSA, dLCP, r.fin);
         if (r.fin.sa != nullptr)
             CAPS_LAUNCH((head_lcp_kernel<idx_t, BITS>), (r.segs.G + 255) / 256, 256, be, P, n, (const uint64_t*)r.segs.seg_start, r.segs.G,
-                        r.fin, r.k32 ? 1u : 0u);
+                        r.fin, r.k32 || r.slot_keys ? 1u : 0u);
     });
     if (!r.run_buckets.empty()) timed(r.runb_clock, 0, [&] { sort_run_buckets<idx_t, BITS>(be, P, n, r, dSA, dLCP); });
     // deferred ties last: the neighbours of a group never change their LCP with it (all members share the key, and a member
@@ -1540,7 +1626,7 @@ private:
     uint32_t passes1_ = 0, passes2_ = 0, passesS_ = 0;
     BackendEvent e2_, e3_, e4_, e5_, e6_, e7_, la0_, la1_;
     uint64_t max_part_ = 0;
-    uint32_t path_direct_ = 0, path_fallback_ = 0, direct_groups_ = 0, direct_quantile_ = 0, direct_k32_ = 0, direct_records_ = 0, tile_chain_ = 0, scatter_issue_ = 0, run_buckets_ = 0;
+    uint32_t path_direct_ = 0, path_fallback_ = 0, direct_groups_ = 0, direct_quantile_ = 0, direct_k32_ = 0, direct_records_ = 0, tile_chain_ = 0, scatter_issue_ = 0, slot_keys_ = 0, run_buckets_ = 0;
     uint64_t direct_max_group_ = 0;
     uint64_t tie_groups_ = 0, tie_elems_ = 0;
     uint32_t tie_levels_ = 0;
@@ -1875,6 +1961,12 @@ private:
         const bool may_wave = !(k32 || waves_ < 2 || !wave_scratch_.key);
         const uint32_t issue_want = rec_a && !quantile && !may_wave ? (issue_env ? (uint32_t)std::atoi(issue_env) : DIRECT_SCATTER_ISSUE_DEFAULT) & 1u : 0u;
         scatter_issue_ = 0;
+        // Slot keys (kernels.h "slot keys"; CAPS_SA_SLOT_KEYS, a mask read here, once per build: bit 0 = level B hands the tile sort
+        // 8-byte records of bucket-relative 32-bit keys, 0 = today's slots; bit 1, the sort itself on 32 bits, is not built).  The
+        // builds that take BOTH the ISSUE scatter and the bucket-indexed launch, 2-bit texts; what the sort ran with: slot_keys_.
+        const char* slot_env = std::getenv("CAPS_SA_SLOT_KEYS");
+        const uint32_t slot_want = BITS == 2 && issue_want && (chain_want & 1u) ? (slot_env ? (uint32_t)std::atoi(slot_env) : DIRECT_SLOT_KEYS_DEFAULT) & 1u : 0u;
+        slot_keys_ = 0;
         if (k32) CAPS_LAUNCH(group_shift_kernel, (K1 + 255) / 256, 256, be_, (const uint64_t*)pl_.gkey, K1, pl_.gshift);
         if (quantile) {
             // more samples, sorted in the (still idle) big buffers; their quantiles are the bucket boundaries and, every KPG-th, the group keys
@@ -2076,6 +2168,7 @@ private:
             }
             set_final(ow, dSA + base, dLCP + base);
             if (W == 1) { ow.tile_chain = chain_want; ow.tile_chain_used = &tile_chain_; }       // (one sort: the last word stands)
+            if (W == 1) { ow.slot_keys = slot_want; ow.slot_keys_used = &slot_keys_; }
             ow.scatter_issue = issue_want;
             ow.scatter_issue_used = &scatter_issue_;
             if (elems_w) {
@@ -2196,6 +2289,7 @@ private:
             st->direct_records = path_direct_ ? direct_records_ : 0u;
             st->tile_chain = path_direct_ ? tile_chain_ : 0u;
             st->scatter_issue = path_direct_ ? scatter_issue_ : 0u;
+            st->slot_keys = path_direct_ ? slot_keys_ : 0u;
             st->direct_max_group = direct_max_group_;
             st->level_a_ms = direct_groups_ ? be_.elapsed_ms(la0_, la1_) : 0.0;
             st->slot_splits = slot_stats_[0];

@@ -119,6 +119,11 @@ typedef struct caps_sa_stats {
      * The environment variable CAPS_SA_SCATTER_ISSUE chooses, 0 = the plain kernels; always 0 in quantile mode, with
      * 64-bit indices, with 32-bit keys, without records, for a build that leaves in waves, and off the direct path */
     uint32_t scatter_issue;
+    /* direct path: what level B handed to the final sort in its slots -- a mask, bit 0 = 8-byte records of a bucket-relative 32-bit key
+     * and the index instead of a 64-bit key array and an index array (csrc/kernels.h "slot keys"; the only stage built so, the other
+     * bits are 0).  The environment variable CAPS_SA_SLOT_KEYS chooses, 0 = the two arrays; always 0 where tile_chain or scatter_issue
+     * is 0, on 8-bit texts, when a slot overflowed and the split was redone, and off the direct path */
+    uint32_t slot_keys;
 } caps_sa_stats;
 
 /* sizeof(caps_sa_stats) / sizeof(caps_sa_shard_info) of THIS library.  Both structs grow at their end from release to release and
